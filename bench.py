@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- ALS iterations/sec of the MI355X TRMF solver on BASELINE.json's headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--no-cpu-baseline] [--cg replicate|timeshard|p2p|persist]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-one-shot]]
+                    [--cg replicate|timeshard|p2p|persist]
+
+A plain run sets up, runs W warm-up iterations (plus a quarter second of heat-up iterations that are rewound on the device
+afterwards), times ONE window of exactly K iterations without phase events, downloads the
+factors (written as DIR/W.npy, DIR/H.npy, DIR/lag_val.npy under --dump-outputs) and prints the result line.  Everything else
+below -- phase events and the roofline objects built from them, the window repeated until the timed region is >= 2 s, SURVEY's
+2 + 10 protocol, the one-shot c_trmf_train leg, the CPU baselines with their parity figure -- runs only under --full.
 
 A "step" is one ALS iteration (F-solve, X-solve, Theta-solve every 2nd iteration; trmf.cpp:647-693)
 over the synthetic config-3 problem (100k x 10k, 1% dense, k=40, |L|=16, fp32),
@@ -10,7 +17,7 @@ launches this file under torch.distributed.run, one rank per GPU; the item rows 
 the timestamp rows of the X-side Gram build are partitioned across ranks inside the library (RCCL
 all-gathers over xGMI), so total work is fixed: "scaling": "strong".
 
-Rank 0 prints ONE JSON line.  `roofline` describes the F-solve kernel (HBM-bound under the
+Rank 0 prints ONE JSON line.  Under --full, `roofline` describes the F-solve kernel (HBM-bound under the
 gather-inclusive algorithmic byte model B_F of SURVEY.md 8(d) / BASELINE.md section 3), timed with HIP
 events recorded on the solver's own stream around that kernel -- on every third iteration of the timed window (--timing 3: an
 iteration's seven phase events are barrier packets that cost ~25 us, so they are sampled; `value` is wall clock over ALL iterations;
@@ -233,30 +240,61 @@ def measure_one_shot(prob, cfg, hyper, missing, dtype, iters, calls=4):
             'note': 'wall clock around the C entry on host (NumPy) arrays; PyMatrix construction (the Python wrapper\'s CSR/CSC conversion) is outside'}
 
 
+kDumpBytes = 64 << 20      # --dump-outputs: budget of all files together
+kHeatS = 0.25              # heat-up of a plain run before its timed window (main)
+
+
+def dump_outputs(dirname, arrays):
+    """Write every array as <dirname>/<name>.npy in its own dtype (float32 / float64).  Arrays are taken smallest first, each
+    whole if it fits its share of what is left of kDumpBytes, else as a fixed sample of its rows (RandomState(0), sorted row
+    indices): the same rows in every run with the same arguments, so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left = kDumpBytes - 4096 * len(arrays)      # room for the .npy headers
+    items = sorted(arrays.items(), key=lambda kv: kv[1].nbytes)
+    for i, (name, a) in enumerate(items):
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            row_bytes = a.nbytes // a.shape[0]
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], max(1, share // row_bytes), replace=False))
+            a = a[rows]
+        a = np.ascontiguousarray(a)
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        left -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--config', default='c3')
-    ap.add_argument('--timing', type=int, default=3,
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: phase events and rooflines (--timing 3), repeated windows '
+                         '(--repeat 0), SURVEY\'s 2 + 10 protocol, the one-shot c_trmf_train leg and the CPU baselines')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps write the factors the timed session holds after its last step (W, H, lag_val, in the '
+                         'problem\'s dtype) as DIR/<name>.npy; at most 64 MB in all (larger factors: a fixed, seeded sample of their rows)')
+    ap.add_argument('--timing', type=int, default=None,
                     help='phase events (F / X / Theta split, kernel times of the roofline objects) on every N-th iteration of the timed '
-                         'window; 1 = every iteration.  The seven event records of an iteration cost 21-26 us (2.5 %% of a config-3 '
-                         'iteration, 22 %% of a config-2 one): the default samples every third iteration, which alternates between '
+                         'window; 1 = every iteration, 0 = none.  The seven event records of an iteration cost 21-26 us (2.5 %% of a config-3 '
+                         'iteration, 22 %% of a config-2 one).  Default: 0, under --full 3 -- every third iteration, which alternates between '
                          'iterations with and without a Theta-solve')
-    ap.add_argument('--repeat', type=int, default=0,
+    ap.add_argument('--repeat', type=int, default=None,
                     help='run the timed window of --steps iterations R times, every time from the SAME post-warm-up state (the session is rewound '
                          'on the device between windows, outside the timed regions); `value` is over all windows, `windows` lists the median / '
-                         'min / max of the individual ones.  0 (default): as many windows as make the timed region >= --min-timed-s seconds '
-                         '(a 17 ms window is invisible to an external utilisation sampler); 1: a single window')
+                         'min / max of the individual ones.  0: as many windows as make the timed region >= --min-timed-s seconds '
+                         '(a 17 ms window is invisible to an external utilisation sampler); 1: a single window.  Default: 1, under --full 0')
     ap.add_argument('--min-timed-s', type=float, default=2.0)
     ap.add_argument('--devices', default=None,
                     help='without a launcher: the device list of the in-process multi-GPU mode (TRMF_DEVICES; default for --gpus N: 0..N-1).  A device '
                          'may be listed several times ("0,0": virtual ranks on one GPU -- a dry run of the multi-GPU path on a one-GPU box)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='under --full: skip the CPU baselines')
     ap.add_argument('--cg', default=None, choices=['replicate', 'timeshard', 'p2p', 'persist', 'shard'],
                     help='multi-GPU CG form (sets TRMF_CG; default: the library measures replicated vs time-sharded)')
-    ap.add_argument('--no-one-shot', action='store_true', help='skip the c_trmf_train (upload + train + download) leg')
+    ap.add_argument('--no-one-shot', action='store_true', help='under --full: skip the c_trmf_train (upload + train + download) leg')
     ap.add_argument('--one-shot-iters', type=int, default=10)
     ap.add_argument('--cpu-iters', type=int, default=10)
     ap.add_argument('--cpu-threads', type=int, default=0)
@@ -267,6 +305,12 @@ def main():
     if args.cpu_baseline_worker:
         return cpu_baseline_worker(args.config, args.cpu_iters, args.cpu_baseline_worker, args.cpu_threads, args.cpu_state,
                                    args.cpu_gpu_result)
+    if args.timing is None:
+        args.timing = 3 if args.full else 0
+    if args.repeat is None:
+        args.repeat = 0 if args.full else 1
+    if not args.full:                           # the extra legs run under --full only
+        args.no_cpu_baseline = args.no_one_shot = True
 
     if args.cg:
         os.environ['TRMF_CG'] = args.cg
@@ -350,9 +394,9 @@ def main():
 
     t_up = time.perf_counter()
     # verbose=0 run of the reference: no ||.||^2 log lines (trmf.cpp:659-688 evaluates them only under verbose)
-    if args.steps < 2 * max(1, args.timing):       # a window too short to hold two sampled iterations: events on every iteration
+    if 0 < args.timing and args.steps < 2 * args.timing:     # a window too short to hold two sampled iterations: events on every iteration
         args.timing = 1
-    s = session.Session(prob['Y'], model, missing=missing, log_norms=False, timing=max(1, args.timing), **hyper)
+    s = session.Session(prob['Y'], model, missing=missing, log_norms=False, timing=max(0, args.timing), **hyper)
     t_up = time.perf_counter() - t_up
     s.run(args.warmup)
     device_sync(s)
@@ -373,6 +417,18 @@ def main():
         args.repeat = 1                         # a library from before round 6 (A/B runs): one window
     if args.repeat != 1:
         s.mark()
+    elif can_rewind and not args.full:
+        # Heat-up of a plain run: a window right behind a short warm-up starts at idle clocks and runs ~6 % below the ones after
+        # it (config 3: 1144 against 1214 iter/s, first_window_iter_per_s of a --full line).  Iterations from the post-warm-up
+        # state for kHeatS seconds, then rewound on the device: the timed window starts from exactly the state --warmup left.
+        s.mark()
+        t1 = time.perf_counter()
+        while True:
+            s.run(min(args.steps, 20))
+            device_sync(s)
+            if max_over_ranks(time.perf_counter() - t1) >= kHeatS:
+                break
+        s.rewind()
     windows = []
     repeat = max(1, args.repeat)
     w = 0
@@ -422,11 +478,13 @@ def main():
     cg_steps = float(np.mean([x['cg_iter'] for x in timed]))   # of the same iterations (us per pass = their CG time / their passes)
     s.download()
     s.close()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'W': model.W, 'H': model.H, 'lag_val': model.lag_val})
 
     # SURVEY.md 8(d)'s protocol beside the driver's flags: 2 warm-up + 10 timed iterations FROM THE RANDOM START (the early iterations
     # run their CG to the 20-step cap, later ones stop at 12-14: a different mix of work from a window after --warmup iterations)
     survey = None
-    if world == 1 and can_rewind:
+    if args.full and world == 1 and can_rewind:
         m_s = synth.initial_model(prob['Y'], prob['lag_set'], cfg['k'], seed=0)
         with session.Session(prob['Y'], m_s, missing=missing, log_norms=False, timing=0, **hyper) as s_s:
             s_s.run(2).sync()
@@ -501,7 +559,8 @@ def main():
                           'timed_iterations': len(timed) if have_events else 0, 'of': len(st),
                           'note': 'HIP events of the iterations that carried them (every %d-th of the window; each such iteration pays seven event '
                                   'records, ~25 us, the others none -- value / ms_per_step are wall clock over ALL iterations); F / X / Theta '
-                                  'overlap where the Theta-solve runs on its own stream under the next F-solve' % max(1, args.timing)},
+                                  'overlap where the Theta-solve runs on its own stream under the next F-solve' % max(1, args.timing)
+                                  if args.timing > 0 else 'no phase events in this run (--timing 0); --full records them'},
             'setup_s': {'generate': t_gen, 'upload_and_alloc': t_up},
         }
         if not args.no_cpu_baseline and world == 1 and not inproc:

@@ -11,7 +11,7 @@ cp gpurun_out/test_evidence.txt $O/test_evidence.txt 2>/dev/null
 bash scripts/ab_builds.sh $R/exp-trmf-nips16_amd/build/old > $O/ab_c3.txt 2>&1; cat $O/ab_c3.txt
 line() { python -c "import json,sys; d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); print('$1', round(d['value'],1), 'iter/s  F', round(d['phases_ms']['F'],4), 'X', round(d['phases_ms']['X'],4), 'Fkernel ms', round(d['roofline']['avg_kernel_ms'],4), 'frac', round(d['roofline']['frac'],3), 'Xgram', (d.get('roofline_x') or {}).get('gram',{}).get('avg_ms'), 'cg', d['phases_ms']['cg_iter'][:6])"; }
 for cfg in imp zipf imp60; do
-  python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-one-shot 2>$O/bench_$cfg.err | tee $O/bench_$cfg.json | line $cfg
+  python bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-one-shot 2>$O/bench_$cfg.err | tee $O/bench_$cfg.json | line $cfg
 done
 for cfg in imp zipf; do
   LINES_OUT=14 bash scripts/trace_config.sh $TAG/$cfg $cfg --no-one-shot > $O/trace_$cfg.txt 2>&1; cut -c1-150 $O/trace_$cfg.txt

@@ -12,6 +12,6 @@ timeout 3300 python -m pytest tests -x -q -s -m gpu --deselect tests/test_gpu_de
 cp gpurun_out/test_evidence.txt $O/test_evidence.txt 2>/dev/null
 line() { python -c "import json,sys; d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); print('$1', round(d['value'],1), 'iter/s', d['windows'], 'F', d['phases_ms']['F'], 'X', d['phases_ms']['X'], 'Fkernel ms', d['roofline']['avg_kernel_ms'], 'frac', round(d['roofline']['frac'],3), 'Xgram', (d.get('roofline_x') or {}).get('gram',{}).get('avg_ms'), 'survey', (d.get('value_survey_protocol') or {}).get('iter_per_s'))"; }
 for cfg in c3 imp zipf; do
-  python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-one-shot 2>$O/bench_$cfg.err | tee $O/bench_$cfg.json | line $cfg
+  python bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-one-shot 2>$O/bench_$cfg.err | tee $O/bench_$cfg.json | line $cfg
 done
 bash scripts/pmc_fsolve.sh $TAG/pmc_c3 c3 > $O/pmc_fsolve_c3.txt 2>&1; tail -30 $O/pmc_fsolve_c3.txt

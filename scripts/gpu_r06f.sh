@@ -12,10 +12,10 @@ diff $O/digest_old.txt $O/digest_new.txt > /dev/null && echo "DIGESTS IDENTICAL 
 timeout 1800 python -m pytest tests/test_gpu_devices.py tests/test_gpu_split.py tests/test_gpu_persist.py -x -q -m gpu -k "not full_size" > $O/pytest_new.log 2>&1; echo "pytest exit $?" >> $O/pytest_new.log; tail -4 $O/pytest_new.log
 line() { python -c "import json,sys; d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); w=d['windows']; print('$1', round(d['value'],1), 'iter/s median', round(w['iter_per_s_median'],1), 'F', d['phases_ms']['F'], 'X', d['phases_ms']['X'], 'Fk', d['roofline']['avg_kernel_ms'], 'frac', round(d['roofline']['frac'],3), 'Xgram', (d.get('roofline_x') or {}).get('gram',{}).get('avg_ms'))"; }
 for cfg in zipf imp; do
-  python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-one-shot 2>$O/bench_$cfg.err | tee $O/bench_$cfg.json | line $cfg
+  python bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-one-shot 2>$O/bench_$cfg.err | tee $O/bench_$cfg.json | line $cfg
 done
 LINES_OUT=12 bash scripts/trace_config.sh $TAG/zipf zipf --no-one-shot --repeat 1 > $O/trace_zipf.txt 2>&1; cut -c1-165 $O/trace_zipf.txt
-python bench.py --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err; tail -c 300 $O/bench_c3.json; echo
+python bench.py --full --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err; tail -c 300 $O/bench_c3.json; echo
 LINES_OUT=16 bash scripts/trace_config.sh $TAG/c3 c3 --no-one-shot --repeat 1 > $O/trace_c3.txt 2>&1; cut -c1-165 $O/trace_c3.txt
 bash scripts/pmc_fsolve.sh $TAG/pmc_c3 c3 > $O/pmc_fsolve_c3.txt 2>&1; grep -E "FETCH_SIZE|WRITE_SIZE|TCC_" $O/pmc_fsolve_c3.txt
 bash scripts/pmc_fsolve.sh $TAG/pmc_c5 c5 > $O/pmc_fsolve_c5.txt 2>&1; grep -E "FETCH_SIZE|WRITE_SIZE|TCC_" $O/pmc_fsolve_c5.txt

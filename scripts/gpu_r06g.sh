@@ -9,4 +9,4 @@ rm -f gpurun_out/test_evidence.txt
 timeout 1500 python -m pytest tests/test_gpu_split.py tests/test_dist.py tests/test_bench_contract.py -x -q -s -m gpu -k "full_size or split or bench" > $O/pytest.log 2>&1; echo "pytest exit $?" >> $O/pytest.log; tail -4 $O/pytest.log
 cp gpurun_out/test_evidence.txt $O/test_evidence.txt 2>/dev/null
 timeout 1200 bash scripts/asan_gpu.sh $O/ubsan_gpu_run.txt; tail -3 $O/ubsan_gpu_run.txt
-python bench.py --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err; tail -c 300 $O/bench_c3.json; echo
+python bench.py --full --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err; tail -c 300 $O/bench_c3.json; echo

@@ -30,20 +30,20 @@ for CFG in ${CFGS:-c3 c5}; do
   for N in $NS; do
     if [ "${DRY:-0}" = 1 ]; then DEVS=$(python -c "print(','.join(['0'] * $N))"); else DEVS=$(python -c "print(','.join(str(i) for i in range($N)))"); fi
     if [ $N -gt 1 ] && [ "${DRY:-0}" != 1 ] && [ $N -le $NDEV ]; then
-      python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --config $CFG \
+      python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --full --config $CFG \
         --steps $STEPS --warmup $WARM --no-cpu-baseline --no-one-shot > $OUT/spmd_${CFG}_$N.json 2> $OUT/spmd_${CFG}_$N.err
       summ $OUT/spmd_${CFG}_$N.json "spmd $CFG N=$N" | tee -a $OUT/summary.txt
       for FORM in replicate timeshard p2p persist; do          # every candidate by itself: what the measure-once rule chose FROM
-        python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --gpus $N --config $CFG \
+        python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --gpus $N --full --config $CFG \
           --steps $STEPS --warmup $WARM --no-cpu-baseline --no-one-shot --cg $FORM > $OUT/spmd_${CFG}_${N}_$FORM.json 2> $OUT/spmd_${CFG}_${N}_$FORM.err
         summ $OUT/spmd_${CFG}_${N}_$FORM.json "spmd $CFG N=$N $FORM" | tee -a $OUT/summary.txt
       done
     fi
     if [ $N -eq 1 ]; then
-      python bench.py --config $CFG --steps $STEPS --warmup $WARM --no-cpu-baseline --no-one-shot > $OUT/one_${CFG}.json 2> $OUT/one_${CFG}.err
+      python bench.py --full --config $CFG --steps $STEPS --warmup $WARM --no-cpu-baseline --no-one-shot > $OUT/one_${CFG}.json 2> $OUT/one_${CFG}.err
       summ $OUT/one_${CFG}.json "one GPU $CFG" | tee -a $OUT/summary.txt
     elif [ "${DRY:-0}" = 1 ] || [ $N -le $NDEV ]; then
-      python bench.py --gpus $N --devices $DEVS --config $CFG --steps $STEPS --warmup $WARM --no-cpu-baseline --no-one-shot > $OUT/inproc_${CFG}_$N.json 2> $OUT/inproc_${CFG}_$N.err
+      python bench.py --full --gpus $N --devices $DEVS --config $CFG --steps $STEPS --warmup $WARM --no-cpu-baseline --no-one-shot > $OUT/inproc_${CFG}_$N.json 2> $OUT/inproc_${CFG}_$N.err
       summ $OUT/inproc_${CFG}_$N.json "in-process $CFG N=$N" | tee -a $OUT/summary.txt
     fi
   done

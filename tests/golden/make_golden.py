@@ -8,7 +8,8 @@ inputs (sparse Y, lag_set, initial W/H/Theta, hyper-parameters) and outputs (fin
 per-half-step norms it prints on stderr at verbose>=1, and the CG step count / objective of the TRON
 line it prints on stdout at verbose>=2).
 
-    python tests/golden/make_golden.py          # rewrites tests/golden/*.npz
+    python tests/golden/make_golden.py             # rewrites tests/golden/*.npz
+    python tests/golden/make_golden.py ref_build   # rewrites tests/golden/ref_build/*.npz only
 """
 import os
 import re
@@ -148,9 +149,27 @@ def make_cold_case(name, dtype, n=90, T=120, k=6, lag_set=(1, 2, 5), density=0.2
     print('{:>14s}: cold start {} F {} X {} LV {}'.format(name, np.dtype(dtype).name, normF.tolist(), normX.tolist(), normLV.tolist()))
 
 
+def make_ref_build_case(dtype):
+    """The fresh-seed case of tests/test_oracle_golden.py::test_port_matches_reference_build (same generator calls, same
+    arguments): the reference's final W, H and Theta after 5 iterations, in tests/golden/ref_build/ (outside the solver cases
+    that golden_names() lists)."""
+    p = synth.sparse_problem(n=350, T=260, k=12, nlag=5, density=0.07, dtype=dtype, seed=11)
+    m = synth.initial_model(p['Y'], p['lag_set'], 12, seed=11)
+    W, H, Th = m.W.copy(), m.H.copy(), np.asfortranarray(m.lag_val.copy())
+    O.train_ref(p['Y'], p['lag_set'], W, H, Th, synth.HYPER, max_iter=5)
+    os.makedirs(os.path.join(OUT, 'ref_build'), exist_ok=True)
+    path = os.path.join(OUT, 'ref_build', 'seed11_{}.npz'.format(np.dtype(dtype).name))
+    np.savez_compressed(path, W=W, H=H, Th=Th)
+    print('{:>14s}: 350 x 260, k=12, 5 iterations ({} KB)'.format(os.path.basename(path), os.path.getsize(path) // 1024))
+
+
 def main():
     if O.ref(np.float32) is None:
         sys.exit('oracle/_ref is missing: run `make -C oracle ref` first (build container only)')
+    if 'ref_build' in sys.argv:                 # only the fresh-seed outputs of test_port_matches_reference_build
+        make_ref_build_case(np.float32)
+        make_ref_build_case(np.float64)
+        return
     make_case('tiny_f32', n=300, T=200, k=8, lag_set=[1, 2, 3], density=0.05, dtype=np.float32, max_iter=6)
     make_case('tiny_f64', n=300, T=200, k=8, lag_set=[1, 2, 3], density=0.05, dtype=np.float64, max_iter=6)
     # ragged: empty timestamps and empty items; lag 0 in the lag set (legal, trmf.py:354); k not a multiple of 8

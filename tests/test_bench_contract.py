@@ -53,6 +53,26 @@ def test_cpu_baseline_worker_protocol():
     assert all(r[key] > 0 for key in ('seconds', 's_per_F', 's_per_X', 's_per_Theta'))
 
 
+
+def test_dump_outputs_keeps_small_factors_whole_and_samples_large_ones_the_same_way(tmp_path):
+    """--dump-outputs: every array in its own dtype, at most 64 MB in all; an array beyond its share is a seeded sample of its rows,
+    the same rows on every call."""
+    import numpy as np
+    import bench
+    rng = np.random.RandomState(1)
+    arrays = {'lag_val': rng.rand(32, 64), 'W': rng.rand(50000, 64), 'H': rng.rand(200000, 64).astype(np.float32)}   # 80 MB in all
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {name: np.load(str(tmp_path / 'a' / (name + '.npy'))) for name in arrays}
+    assert sum((tmp_path / 'a' / (name + '.npy')).stat().st_size for name in arrays) <= 64 << 20
+    assert np.array_equal(got['lag_val'], arrays['lag_val']) and np.array_equal(got['W'], arrays['W'])
+    assert got['H'].dtype == np.float32 and 0 < got['H'].shape[0] < 200000 and got['H'].shape[1] == 64
+    rows = [int(np.flatnonzero((arrays['H'] == r).all(axis=1))[0]) for r in got['H'][:50]]
+    assert rows == sorted(rows)                                                  # sampled rows, in their original order
+    for name in arrays:
+        assert np.array_equal(got[name], np.load(str(tmp_path / 'b' / (name + '.npy'))))
+
+
 import pytest  # noqa: E402
 
 
@@ -68,7 +88,7 @@ def test_bench_through_the_launcher_line_with_one_rank():
     env = dict(os.environ, TRMF_BENCH_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
-           '--config', 'c2', '--no-cpu-baseline']
+           '--config', 'c2', '--full', '--no-cpu-baseline']
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [l for l in res.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, res.stdout[-2000:] + res.stderr[-3000:]
@@ -102,7 +122,7 @@ def test_bench_without_a_launcher_runs_the_in_process_multi_gpu_mode_and_repeats
     """python bench.py --gpus 2 (no torchrun): TRMF_DEVICES inside one process (here two virtual ranks on the one device), the timed
     window repeated from the same state -- every window does the same work."""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--devices', '0,0', '--steps', '4', '--warmup', '2', '--repeat', '3',
-           '--config', 'c2', '--no-cpu-baseline', '--no-one-shot']
+           '--config', 'c2', '--full', '--no-cpu-baseline', '--no-one-shot']
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [l for l in res.stdout.splitlines() if l.startswith('{"metric"')]
@@ -112,3 +132,33 @@ def test_bench_without_a_launcher_runs_the_in_process_multi_gpu_mode_and_repeats
     assert '2 ranks' in r['config']['parallelism'] and 'threads of this process' in r['config']['parallelism']
     assert abs(r['ms_per_step'] * 4 * 3 / 1e3 - r['windows']['timed_region_s']) < 1e-9
     assert r['value_survey_protocol']['steps'] == 10 and r['value_survey_protocol']['iter_per_s'] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_exactly_its_steps_and_dumps_what_the_session_computed(tmp_path):
+    """A plain run: one window of exactly --steps iterations, none of the --full legs, and --dump-outputs writes the factors after
+    the last timed step -- the same W, H, lag_val as a session that runs warm-up + steps from the same seeded start."""
+    import numpy as np
+    from trmf import session, synth
+    out = tmp_path / 'out'
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--config', 'c2',
+           '--dump-outputs', str(out)]
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    lines = [l for l in res.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1, res.stdout[-2000:] + res.stderr[-3000:]
+    r = json.loads(lines[0])
+    assert r['steps'] == 3 and r['windows']['repeat'] == 1 and len(r['phases_ms']['cg_iter']) == 3
+    assert abs(r['ms_per_step'] * 3 / 1e3 - r['windows']['timed_region_s']) < 1e-9 and abs(r['value'] - 1e3 / r['ms_per_step']) < 1e-6
+    assert r['value_survey_protocol'] is None and r['one_shot'] is None and 'cpu_baseline' not in r and r['roofline'] is None
+    assert (r['metric'], r['unit'], r['higher_is_better'], r['dtype']) == ('als_iterations_per_sec', 'iter/s', True, 'f32')
+    cfg = synth.CONFIGS['c2']
+    prob = synth.make(cfg, seed=0)
+    m = synth.initial_model(prob['Y'], prob['lag_set'], cfg['k'], seed=0)
+    with session.Session(prob['Y'], m, missing=True, log_norms=False, timing=0, **synth.HYPER) as s:
+        s.run(1).sync()
+        s.run(3).download()
+    for name, want in (('W', m.W), ('H', m.H), ('lag_val', m.lag_val)):
+        got = np.load(str(out / (name + '.npy')))
+        assert got.dtype == np.float32 and got.shape == want.shape, name
+        assert np.array_equal(got, want), name

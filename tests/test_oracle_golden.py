@@ -1,6 +1,6 @@
 """CPU: the C restatement (oracle/trmf_oracle.c) against the golden vectors captured from the real
-reference (tests/golden/make_golden.py), and -- when oracle/_ref exists -- against the reference
-itself on fresh seeds.  This is what pins the oracle."""
+reference (tests/golden/make_golden.py), and against the reference's outputs on a fresh seed (captured, and live
+where oracle/_ref exists).  This is what pins the oracle."""
 import numpy as np
 import pytest
 
@@ -31,17 +31,24 @@ def test_port_matches_golden(name):
 
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])
 def test_port_matches_reference_build(dtype):
-    if O.ref(dtype) is None:
-        pytest.skip('oracle/_ref not built here (reference sources only exist in the build container)')
+    """A fresh seed against the reference build: its outputs as captured in tests/golden/ref_build/ (make_golden.py ref_build,
+    same problem), and the build itself where oracle/_ref exists."""
+    import os
+    from helpers import GOLDEN_DIR
     from trmf import synth
     p = synth.sparse_problem(n=350, T=260, k=12, nlag=5, density=0.07, dtype=dtype, seed=11)
     m = synth.initial_model(p['Y'], p['lag_set'], 12, seed=11)
-    W1, H1, T1 = m.W.copy(), m.H.copy(), np.asfortranarray(m.lag_val.copy())
     W2, H2, T2 = m.W.copy(), m.H.copy(), np.asfortranarray(m.lag_val.copy())
-    O.train_ref(p['Y'], p['lag_set'], W1, H1, T1, synth.HYPER, max_iter=5)
     O.train_port(p['Y'], p['lag_set'], W2, H2, T2, synth.HYPER, max_iter=5)
+    g = np.load(os.path.join(GOLDEN_DIR, 'ref_build', 'seed11_{}.npz'.format(np.dtype(dtype).name)))
+    refs = [(g['W'], g['H'], g['Th'])]
+    if O.ref(dtype) is not None:
+        W1, H1, T1 = m.W.copy(), m.H.copy(), np.asfortranarray(m.lag_val.copy())
+        O.train_ref(p['Y'], p['lag_set'], W1, H1, T1, synth.HYPER, max_iter=5)
+        refs.append((W1, H1, T1))
     tol = 1e-9 if dtype == np.float64 else 2e-4
-    assert relfro(W2, W1) < tol and relfro(H2, H1) < tol and relfro(T2, T1) < tol * 10
+    for W1, H1, T1 in refs:
+        assert relfro(W2, W1) < tol and relfro(H2, H1) < tol and relfro(T2, T1) < tol * 10
 
 
 def test_fsolve_is_ridge_regression():

@@ -19,7 +19,13 @@ def test_host_threads_are_race_free_under_tsan(tmp_path):
     exe = str(tmp_path / 'tsan_host')
     subprocess.run(['g++', '-std=c++17', '-O1', '-g', '-fsanitize=thread', '-DTSAN_POOL_HEADER="pool_part.hpp"', '-DTSAN_COMM_HEADER="comm_part.hpp"',
                     '-I', str(tmp_path), os.path.join(ROOT, 'tests', 'tsan_host.cpp'), '-o', exe, '-pthread'], check=True)
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(os.environ, TSAN_OPTIONS='halt_on_error=0 report_signal_unsafe=0'))
+    # ThreadSanitizer's shadow layout assumes the address-space randomisation of older kernels: where mmap randomisation is wider
+    # (vm.mmap_rnd_bits = 32) the runtime stops with "unexpected memory mapping".  The race-checked binary runs with randomisation
+    # off for itself alone (setarch -R: a personality flag of that process, no host setting).
+    import platform
+    import shutil
+    runner = ['setarch', platform.machine(), '-R'] if shutil.which('setarch') else []
+    res = subprocess.run(runner + [exe], capture_output=True, text=True, timeout=900, env=dict(os.environ, TSAN_OPTIONS='halt_on_error=0 report_signal_unsafe=0'))
     report = res.stdout + res.stderr
     out = os.path.join(ROOT, 'gpurun_out')
     if os.path.isdir(out):
