@@ -12,12 +12,13 @@
 //   unit_gram.hip      fsolve_quad / fsolve_mfma (8), gram_x_kernel (16), loss_kernel (4)
 //   unit_split.hip     the split path of long rows (round 6): gram_part_kernel (8), fsolve_*_long_kernel (8), gram_x_long_kernel (16)
 //   unit_full.hip      the MFMA kernels of the full-observation path (20)
+//   unit_heldout.hip   heldout_eval_kernel (5): the model at a resident set of held-out positions (trmf_session_eval_heldout)
 //
 // A unit defines TRMF_UNIT before including this file; the non-template kernels of the shared headers are compiled by the main
 // unit only (#if !defined(TRMF_UNIT) around them).
 #pragma once
 
-// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full; the kernels of these families
+// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out; the kernels of these families
 // have their BODIES only where TRMF_UNIT_BODIES is defined -- the main unit sees declarations, so that it neither compiles them
 // nor runs them through the optimiser as `extern template` would (available_externally bodies: 3 of its 3.5 minutes))
 #if defined(TRMF_UNIT) || defined(TRMF_SINGLE_UNIT)
@@ -33,6 +34,9 @@
 #include "cg_kernels.hpp"
 #include "gram_kernels.hpp"
 #include "full_kernels.hpp"
+#endif
+#if !defined(TRMF_UNIT) || TRMF_UNIT == 5
+#include "heldout_kernels.hpp"
 #endif
 #if !defined(TRMF_UNIT)
 #include "cg_persist_args.hpp"     // the declaration only: the body is unit_persist.hip's business
@@ -117,6 +121,11 @@ namespace trmf {
     X void chol_wave_kernel<NT>(const real *, real *, int);                                                                             \
     X void apply_shared_mfma_kernel<NT> TRMF_APPLY_SHARED_SIG;
 #define TRMF_UNIT_FULL(X) TRMF_FULL_NT(X, 1) TRMF_FULL_NT(X, 2) TRMF_FULL_NT(X, 3) TRMF_FULL_NT(X, 4)
+
+// held-out evaluation (heldout_kernels.hpp): NT = 1..4 for k <= 64, NT = 0 the generic instantiation for 64 < k <= 1024
+#define TRMF_UNIT_HELDOUT(X)                                                                                                 \
+    X void heldout_eval_kernel<0>(HeldoutArgs); X void heldout_eval_kernel<1>(HeldoutArgs); X void heldout_eval_kernel<2>(HeldoutArgs); \
+    X void heldout_eval_kernel<3>(HeldoutArgs); X void heldout_eval_kernel<4>(HeldoutArgs);
 
 #define TRMF_DEFINE_KERNEL template __global__
 

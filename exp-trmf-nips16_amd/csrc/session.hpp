@@ -894,6 +894,59 @@ struct TrmfSessionImpl : SessionXPhase {
         const double h2 = host_double(&st->gs);
         return 0.5 * l + 0.5 * lambdaI * (w2 + h2) + 0.5 * lambdaAR * ar;
     }
+
+    // ---- held-out evaluation (trmf_session_set_heldout / _eval_heldout; heldout_kernels.hpp) ---------------------------
+    // Yt has been validated by the caller (sparse, n columns, rows <= T, indices in range); `rows` is its row index per entry.
+    int set_heldout(const PyMatrix *Yt, const std::vector<uint32_t> &rows) {
+        ho_set = false; ho_m = 0;
+        ho_row.release(); ho_col.release(); ho_val.release(); ho_pred.release(); ho_part.release(); ho_sums.release();
+        if (!Yt) return 0;
+        FillStreamScope fill(stream);
+        const uint64_t m = Yt->nnz;
+        if (ho_row.upload(rows.data(), m) || ho_col.upload(Yt->col_idx, m) || ho_val.upload((const real *)Yt->val_t, m)) return kFail;
+        // equal contiguous chunks, a multiple of one workgroup step each: the work of a workgroup does not depend on row lengths
+        ho_nb = (int)std::max<uint64_t>(1, std::min<uint64_t>(kHoMaxBlocks, (m + 255) / 256));
+        ho_chunk = ((m + ho_nb - 1) / ho_nb + kHoStep - 1) / kHoStep * kHoStep;
+        if (ho_chunk == 0) ho_chunk = kHoStep;
+        ho_nb = (int)std::max<uint64_t>(1, (m + ho_chunk - 1) / ho_chunk);
+        if (ho_part.alloc((size_t)kHoSums * ho_nb, false) || ho_sums.alloc(kHoSums, false)) return kFail;
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        ho_m = m; ho_set = true;
+        return 0;
+    }
+    // Reads W and H only, in stream order after everything enqueued before (the caller has synchronised the session).
+    int eval_heldout(TrmfHeldoutSums *out, real *pred) {
+        if (!ho_set) { set_error("eval_heldout: no held-out set (trmf_session_set_heldout)"); return kFail; }
+        double h[kHoSums] = {0, 0, 0, 0, 0, 0};
+        if (ho_m > 0) {
+            FillStreamScope fill(stream);
+            if (pred && ho_pred.alloc(ho_m, false)) return kFail;
+            HeldoutArgs a{ho_row.p, ho_col.p, ho_val.p, W.p, H.p, pred ? ho_pred.p : nullptr, ho_part.p, ho_m, ho_chunk, KP, NT};
+            switch (generic ? 0 : NT) {
+                case 1: hipLaunchKernelGGL(heldout_eval_kernel<1>, dim3(ho_nb), dim3(256), 0, stream, a); break;
+                case 2: hipLaunchKernelGGL(heldout_eval_kernel<2>, dim3(ho_nb), dim3(256), 0, stream, a); break;
+                case 3: hipLaunchKernelGGL(heldout_eval_kernel<3>, dim3(ho_nb), dim3(256), 0, stream, a); break;
+                case 4: hipLaunchKernelGGL(heldout_eval_kernel<4>, dim3(ho_nb), dim3(256), 0, stream, a); break;
+                default: hipLaunchKernelGGL(heldout_eval_kernel<0>, dim3(ho_nb), dim3(256), 0, stream, a); break;
+            }
+            hipLaunchKernelGGL(heldout_reduce_kernel, dim3(1), dim3(256), 0, stream, ho_part.p, ho_nb, ho_sums.p);
+            TRMF_HIP_CHECK(hipGetLastError());
+            TRMF_HIP_CHECK(hipMemcpyAsync(h, ho_sums.p, sizeof h, hipMemcpyDeviceToHost, stream));
+            if (pred) TRMF_HIP_CHECK(hipMemcpyAsync(pred, ho_pred.p, ho_m * sizeof(real), hipMemcpyDeviceToHost, stream));
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        out->count = (uint64_t)h[0]; out->count_nonzero = (uint64_t)h[1];
+        out->sq_err = h[2]; out->abs_err = h[3]; out->abs_truth = h[4]; out->rel_err = h[5];
+        return 0;
+    }
+    // New regularisation weights for the iterations enqueued from now on: the session's own copies (F-solve, Theta-solve, the
+    // full-observation path's shared Gram) and the X-side parameter block every X-solve kernel receives by value.
+    int set_lambdas(double lI, double lAR, double lLag) {
+        if (sync()) return kFail;                 // (a recovery of a timed-out persistent kernel repeats iterations with the OLD weights)
+        lambdaI = lI; lambdaAR = lAR; lambdaLag = lLag;
+        xp.lambdaI = lI; xp.lambdaAR = lAR;
+        return 0;
+    }
 };
 
 }  // namespace trmf

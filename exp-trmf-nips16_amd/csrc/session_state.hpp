@@ -187,6 +187,15 @@ struct SessionState {
     DevBuf<real> tr_a, tr_b;
     DevBuf<double> tr_part;
     bool has_transform = false;
+
+    // ---- held-out positions (trmf_session_set_heldout / _eval_heldout; heldout_kernels.hpp) -------------------------------------
+    // COO in the caller's CSR order, resident until replaced; rows only ever grow (append_rows), so the set stays valid.
+    bool ho_set = false;
+    uint64_t ho_m = 0, ho_chunk = kHoStep;
+    int ho_nb = 1;                            // workgroups of one evaluation: kHoSums partials each in ho_part
+    DevBuf<uint32_t> ho_row, ho_col;
+    DevBuf<real> ho_val, ho_pred;
+    DevBuf<double> ho_part, ho_sums;
     // fp32: four systems per wavefront (fsolve_quad_kernel); fp64: one system per wavefront, factorised in the MFMA
     // accumulator layout (fsolve_mfma_kernel)
     // X-side Gram build across ranks: sharded rows + all-gather of G (64 MB at config 3) pays only when a

@@ -423,6 +423,51 @@ void trmf_session_destroy(TrmfSession *s) {
     delete HND(s);
 }
 
+// Held-out set and weights: every argument is checked here, on the calling thread, before any rank's worker runs -- a rejected
+// call must not break the barrier of a TRMF_DEVICES group (a failed worker task poisons it).
+int32_t trmf_session_set_heldout(TrmfSession *s, const PyMatrix *Yt) {
+    if (!s) { set_error("null session"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    std::vector<uint32_t> rows;
+    if (Yt) {
+        if (Yt->type != TRMF_SPARSE) { set_error("set_heldout: Ytest must be a sparse PyMatrix"); return kFail; }
+        if (Yt->cols != (uint64_t)f->n) { set_error("set_heldout: Ytest has " + std::to_string(Yt->cols) + " columns, the session " + std::to_string(f->n)); return kFail; }
+        if (Yt->rows > (uint64_t)f->T) { set_error("set_heldout: Ytest has more rows than the session's W (" + std::to_string(f->T) + ")"); return kFail; }
+        if (Yt->nnz >= (1ull << 32)) { set_error("set_heldout: Ytest exceeds 32-bit entry indices"); return kFail; }
+        if (!Yt->row_ptr || (Yt->nnz && (!Yt->col_idx || !Yt->val_t))) { set_error("set_heldout: Ytest lacks its CSR arrays"); return kFail; }
+        if (Yt->row_ptr[0] != 0 || Yt->row_ptr[Yt->rows] != Yt->nnz) { set_error("set_heldout: Ytest row pointers do not span its entries"); return kFail; }
+        rows.resize(Yt->nnz);
+        for (uint64_t i = 0; i < Yt->rows; i++) {
+            const size_t p0 = Yt->row_ptr[i], p1 = Yt->row_ptr[i + 1];
+            if (p1 < p0 || p1 > Yt->nnz) { set_error("set_heldout: Ytest row pointers are not ascending"); return kFail; }
+            for (size_t e = p0; e < p1; e++) rows[e] = (uint32_t)i;
+        }
+        for (uint64_t e = 0; e < Yt->nnz; e++)
+            if (Yt->col_idx[e] >= (uint32_t)f->n) { set_error("set_heldout: Ytest column index " + std::to_string(Yt->col_idx[e]) + " out of range"); return kFail; }
+    }
+    DeviceGuard guard;
+    return guard.ok ? HND(s)->all([&](TrmfSessionImpl *t) { return t->set_heldout(Yt, rows); }) : kFail;
+}
+int32_t trmf_session_eval_heldout(TrmfSession *s, TrmfHeldoutSums *out, void *pred) {
+    if (!s || !out) { set_error("null session or output"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (!f->ho_set) { set_error("eval_heldout: no held-out set (trmf_session_set_heldout)"); return kFail; }
+    if (f->has_transform) { set_error("eval_heldout: the session trains on a series transform; held-out truths would be in another scale"); return kFail; }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    if (HND(s)->all([&](TrmfSessionImpl *t) { return t->sync(); })) return kFail;       // every rank holds the same factors: rank 0 answers
+    TrmfHeldoutSums sums{};
+    const int rc = HND(s)->rank0([&](TrmfSessionImpl *t) { return t->eval_heldout(&sums, (real *)pred); });
+    if (rc == 0) *out = sums;
+    return rc;
+}
+int32_t trmf_session_set_lambdas(TrmfSession *s, double lambdaI, double lambdaAR, double lambdaLag) {
+    if (!s) { set_error("null session"); return kFail; }
+    if (!std::isfinite(lambdaI) || !std::isfinite(lambdaAR) || !std::isfinite(lambdaLag)) { set_error("set_lambdas: weights must be finite"); return kFail; }
+    DeviceGuard guard;
+    return guard.ok ? HND(s)->all([&](TrmfSessionImpl *t) { return t->set_lambdas(lambdaI, lambdaAR, lambdaLag); }) : kFail;
+}
+
 // ---- multi-GPU ----------------------------------------------------------------------------------
 int32_t trmf_dist_get_unique_id(void *out_id) {
     RcclApi &api = rccl_api();

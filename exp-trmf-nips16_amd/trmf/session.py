@@ -9,6 +9,7 @@ import ctypes
 from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int32, c_uint32, c_uint64, c_void_p
 
 import numpy as np
+import scipy.sparse as smat
 
 from ._corelib import get_clib
 from .rf_util import PyMatrix
@@ -21,6 +22,15 @@ class TrmfIterStats(ctypes.Structure):
                 ('cg_iter', c_int32), ('accepted', c_int32),
                 ('ms_F', c_float), ('ms_X', c_float), ('ms_LV', c_float), ('ms_F_kernel', c_float),
                 ('delta', c_double), ('cg_rnorm_direct', c_double), ('ms_X_gram', c_float), ('reserved_', c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TrmfHeldoutSums(ctypes.Structure):
+    """Sums of a held-out evaluation (include/trmf_abi.h); ``ImputeMetrics.from_sums`` turns them into scores."""
+    _fields_ = [('count', c_uint64), ('count_nonzero', c_uint64), ('sq_err', c_double), ('abs_err', c_double),
+                ('abs_truth', c_double), ('rel_err', c_double)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -73,6 +83,12 @@ def bind(lib):
     lib.trmf_session_fsolve_bytes.argtypes = [c_void_p]; lib.trmf_session_fsolve_bytes.restype = c_double
     lib.trmf_session_describe.argtypes = [c_void_p, ctypes.c_char_p, c_int32]; lib.trmf_session_describe.restype = c_int32
     lib.trmf_session_destroy.argtypes = [c_void_p]; lib.trmf_session_destroy.restype = None
+    if hasattr(lib, 'trmf_session_set_heldout'):      # (absent from libraries built before held-out evaluation)
+        lib.trmf_session_set_heldout.argtypes = [c_void_p, P]; lib.trmf_session_set_heldout.restype = c_int32
+        lib.trmf_session_eval_heldout.argtypes = [c_void_p, POINTER(TrmfHeldoutSums), c_void_p]
+        lib.trmf_session_eval_heldout.restype = c_int32
+        lib.trmf_session_set_lambdas.argtypes = [c_void_p, c_double, c_double, c_double]
+        lib.trmf_session_set_lambdas.restype = c_int32
     lib.trmf_dist_get_unique_id.argtypes = [c_void_p]; lib.trmf_dist_get_unique_id.restype = c_int32
     lib.trmf_dist_init.argtypes = [c_int32, c_int32, c_void_p]; lib.trmf_dist_init.restype = c_int32
     lib.trmf_dist_init_callback.argtypes = [c_int32, c_int32, ALLGATHERV_FN, c_void_p]
@@ -164,6 +180,49 @@ class Session(object):
 
     def rows(self):
         return self._check(self.lib.trmf_session_rows(self.handle), 'trmf_session_rows')
+
+    def set_lambdas(self, lambdaI, lambdaAR, lambdaLag):
+        """New regularisation weights for the iterations run from now on (with ``rewind()``: a grid over the weights
+        from one resident problem and one initial model)."""
+        self._check(self.lib.trmf_session_set_lambdas(self.handle, lambdaI, lambdaAR, lambdaLag), 'trmf_session_set_lambdas')
+        return self
+
+    def set_heldout(self, Ytest):
+        """Upload the held-out positions and truths: a sparse T' x n matrix (T' <= rows()) whose STORED entries, explicit
+        zeros included, are the cells to score, in the scale the session trains on.  ``None`` drops the set."""
+        if Ytest is None:
+            self._check(self.lib.trmf_session_set_heldout(self.handle, None), 'trmf_session_set_heldout')
+            self._heldout_nnz = None
+            return self
+        if isinstance(Ytest, PyMatrix):
+            pyT = Ytest
+        elif smat.issparse(Ytest):
+            pyT = PyMatrix(Ytest, dtype=self.model.W.dtype)
+        else:
+            raise TypeError('set_heldout: a scipy.sparse matrix is required (its stored entries are the held-out cells)')
+        self._check(self.lib.trmf_session_set_heldout(self.handle, byref(pyT)), 'trmf_session_set_heldout')
+        self._heldout_nnz = int(pyT.nnz)
+        return self
+
+    def eval_heldout_sums(self, predictions=False):
+        """The six sums of the held-out set (a dict), plus the predictions in the set's CSR order if asked for."""
+        sums = TrmfHeldoutSums()
+        pred = None
+        if predictions:
+            nnz = getattr(self, '_heldout_nnz', None)
+            pred = np.empty(nnz or 0, dtype=self.model.W.dtype)
+        self._check(self.lib.trmf_session_eval_heldout(self.handle, byref(sums), pred.ctypes.data if pred is not None and pred.size else None),
+                    'trmf_session_eval_heldout')
+        return (sums.as_dict(), pred) if predictions else sums.as_dict()
+
+    def eval_heldout(self, predictions=False):
+        """``ImputeMetrics`` of the current model on the held-out set (computed on the device); with ``predictions=True`` a
+        pair (metrics, predictions in the set's CSR order)."""
+        from .impute import ImputeMetrics
+        if predictions:
+            sums, pred = self.eval_heldout_sums(True)
+            return ImputeMetrics.from_sums(sums), pred
+        return ImputeMetrics.from_sums(self.eval_heldout_sums())
 
     def download(self):
         m = self.model

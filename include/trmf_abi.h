@@ -232,6 +232,35 @@ TRMF_API double trmf_session_fsolve_bytes(TrmfSession *s);
 TRMF_API int32_t trmf_session_describe(TrmfSession *s, char *buf, int32_t cap);
 TRMF_API void trmf_session_destroy(TrmfSession *s);
 
+/* --- held-out evaluation (the paper's imputation protocol; no reference counterpart) -------------------------------------
+ * The model W.H^T at a resident set of positions that were NOT trained on, scored on the device: predictions y^ = W[i].H[j]
+ * in the element type (the products of one dot product are summed in an order of this library's choosing), and six fp64
+ * sums over the set, each formed in a fixed order (repeated calls are bit-identical):
+ *   count          entries                          count_nonzero  entries whose truth y != 0
+ *   sq_err         sum (y^ - y)^2                   abs_err        sum |y^ - y|
+ *   abs_truth      sum |y|                          rel_err        sum over y != 0 of |y^ - y| / |y|
+ * The truths must be in the scale the model trains on: a session with an active series transform
+ * (trmf_session_set_series_transform) refuses the evaluation.  With TRMF_DEVICES every rank holds the same factors and
+ * rank 0 evaluates; with a communicator (trmf_dist_init*) every process evaluates its own copy. */
+typedef struct {
+    uint64_t count, count_nonzero;
+    double sq_err, abs_err, abs_truth, rel_err;
+} TrmfHeldoutSums;
+/* Ytest: TRMF_SPARSE PyMatrix of THIS library's element type, the same number of columns as the session's Y and at most
+ * trmf_session_rows() rows; its stored CSR entries (row_ptr, col_idx, val_t -- explicit zeros included) are the held-out
+ * positions and truths.  Uploaded once and resident until replaced; it stays valid across append_rows (rows only grow).
+ * NULL drops it.  0, or -1 with trmf_last_error() (wrong shape or type, an index out of range; the session is unchanged). */
+TRMF_API int32_t trmf_session_set_heldout(TrmfSession *s, const PyMatrix *Ytest);
+/* Blocking, ordered after every run() enqueued before; reads the factors only (the trajectory, the iteration statistics,
+ * the mark and the measured decisions are untouched).  out: the sums above; pred: NULL or Ytest.nnz reals of the element
+ * type, in Ytest's CSR order (row-major by timestamp).  0, or -1 (no held-out set, an active series transform, a device
+ * failure) with the outputs untouched. */
+TRMF_API int32_t trmf_session_eval_heldout(TrmfSession *s, TrmfHeldoutSums *out, void *pred);
+/* Replace lambdaI / lambdaAR / lambdaLag of a live session (every rank) for the iterations enqueued from now on; blocks
+ * until the work already enqueued has finished.  mark(); run(n); rewind(); set_lambdas(l'); run(n) gives the same bits as
+ * a session created with l' from the marked model.  0, or -1 for a value that is not finite. */
+TRMF_API int32_t trmf_session_set_lambdas(TrmfSession *s, double lambdaI, double lambdaAR, double lambdaLag);
+
 /* --- multi-GPU (one process per GPU; RCCL all-gathers over xGMI) ---------------------------- */
 #define TRMF_UNIQUE_ID_BYTES 128
 /* Rank 0: create an RCCL unique id; the caller broadcasts the bytes to all ranks
