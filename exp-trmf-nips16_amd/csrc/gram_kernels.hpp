@@ -732,10 +732,16 @@ template <int NT> __device__ __forceinline__ constexpr int quad_slab_col_offset(
 // v_mfma_f32_4x4x1_16b_f32 is 16 independent 4x4 outer products -- block = 4 neighbouring lanes, result VGPR i
 // of lane 4b+jj = C + A[lane 4b+i] * B[lane 4b+jj] -- which in this layout (lane = column, VGPR = row) is exactly
 //     A[4R+i][16q+c] -= u[4R+i] * u[16q+c]      for i = 0..3, all 16 columns c of block q, all four systems,
-// with the B operand the lane's own u[q] and the A operand one ds_swizzle (the quad holding u[4R..4R+3]
-// replicated to every quad of the 16-lane row).  One swizzle + (NT - q(R)) MFMAs per row quad replace four
-// swizzles + 4 (NT - q) FMAs, and an MFMA issues 512 flops in 8 cycles where four v_fma_f32 take 16
-// (scripts/ubench/mfma4x4.hip); the product is rounded once like fmaf, so the arithmetic is unchanged.
+// with the B operand the lane's own u[q] and the A operand the quad holding u[4R..4R+3] replicated to every quad
+// of the 16-lane row.  That replication is part of the instruction: cbsz:2 makes each group of 2^2 = 4 consecutive
+// blocks (= one 16-lane row = one system) read the A operand of ONE of its blocks, abid:(R & 3) names it
+// (scripts/ubench/mfma4x4.hip checks the mapping on the device and that the modifiers cost no issue cycles), so
+// the A operand is the lane's own -u[qs] and a step has no LDS-pipe instruction on its chain
+// (profiles/fsolve_trail_abid.txt).  TRMF_TRAIL_ABID=0 builds the form used until then: one ds_swizzle per row
+// quad (row_quad_bcast, ~100 cycles through the LDS pipe and an s_waitcnt) in front of plain MFMAs; same
+// multiplicands, same single rounding, same order -- the factors are bit-identical.  (NT - q(R)) MFMAs per row
+// quad replace 4 (NT - q) FMAs fed by four broadcasts, and an MFMA issues 512 flops in 8 cycles where four
+// v_fma_f32 take 16; the product is rounded once like fmaf, so the arithmetic is unchanged.
 // Rows <= j inside the first quad see u = 0 and stay as they are.
 //
 // RHS_IN: the right-hand side sits in column KP-1 of the matrix (the pad column the Gram MFMAs accumulated
@@ -744,6 +750,21 @@ template <int NT> __device__ __forceinline__ constexpr int quad_slab_col_offset(
 // treats it as one more unknown fixed at -1:  x_j = -(sum_{t>j} U[j][t] x_t) / U[j][j]  with  x_{KP-1} = -1.
 typedef float quad_f4 __attribute__((ext_vector_type(4)));
 
+// A operand of the trailing update: 1 = broadcast inside the MFMA (cbsz:2 abid:Q), 0 = a ds_swizzle in front of it (see above)
+#ifndef TRMF_TRAIL_ABID
+#define TRMF_TRAIL_ABID 1
+#endif
+// With the swizzles and their waits gone nothing bounds the instruction scheduler's reach inside the unrolled factorisation: it moves
+// work across many elimination steps, <4,64> (exactly 256 VGPRs) spills, and the other instantiations get no faster than the swizzle
+// form.  A scheduling barrier after every TRMF_TRAIL_FENCE steps (NT <= 3) / TRMF_TRAIL_FENCE4 steps (NT = 4) keeps a step's
+// instructions together (0: none).  Measured per spacing, profiles/fsolve_trail_abid.txt: every step is the fastest for both
+// (config 3 F phase 0.364 -> 0.355 ms, k = 64: 0.703 -> 0.679 ms; no barrier: 0.364, and <4,64> does not build).
+#ifndef TRMF_TRAIL_FENCE4
+#define TRMF_TRAIL_FENCE4 1
+#endif
+#ifndef TRMF_TRAIL_FENCE
+#define TRMF_TRAIL_FENCE 1
+#endif
 // value of the quad Q (lanes 4Q..4Q+3) of the caller's 16-lane row, replicated to all four quads of that row
 template <int Q> __device__ __forceinline__ float row_quad_bcast(float v) {
     constexpr int pattern = ((Q << 2) << 5) | 0x13;      // and_mask = 0b10011, or_mask = 4Q, xor_mask = 0
@@ -779,11 +800,21 @@ __device__ __forceinline__ void quad_factor_solve(quad_f4 (&a4)[NT][KMAX / 4], f
             static_for<NR>([&](auto Rx) {
                 constexpr int R = decltype(Rx)::value, qs = (4 * R) >> 4;
                 if constexpr (4 * R + 3 > j) {
+#if TRMF_TRAIL_ABID
+                    // A = -u[4R + (lane & 3)]: quad R & 3 of the lane's own 16-lane row, picked by the instruction
+#pragma unroll
+                    for (int q = qs; q < NT; q++) a4[q][R] = __builtin_amdgcn_mfma_f32_4x4x1f32(nu[qs], u[q], a4[q][R], 2, R & 3, 0);
+#else
                     const float nus = row_quad_bcast<R & 3>(nu[qs]);     // -u[4R + (lane & 3)]
 #pragma unroll
                     for (int q = qs; q < NT; q++) a4[q][R] = __builtin_amdgcn_mfma_f32_4x4x1f32(nus, u[q], a4[q][R], 0, 0, 0);
+#endif
                 }
             });
+#if TRMF_TRAIL_ABID
+            constexpr int fence = NT >= 4 ? TRMF_TRAIL_FENCE4 : TRMF_TRAIL_FENCE;
+            if constexpr (fence > 0 && j % (fence > 0 ? fence : 1) == fence - 1) __builtin_amdgcn_sched_barrier(0);
+#endif
         }
     });
     // back substitution U x = z, row-oriented, reduction inside the 16-lane row (DPP)
