@@ -2,11 +2,12 @@
 """Rolling-window forecast evaluation with the settings of the paper's experiment scripts
 (python/exp-scripts/run_electricity.py / run_traffic.py of the reference), through this package's front end.
 
-    python examples/rolling_forecast.py [--data electricity.npy] [--preset electricity|traffic] [--windows 7] [--iters 40]
+    python examples/rolling_forecast.py [--data electricity.npy] [--preset electricity|traffic] [--windows 7] [--iters 40] [--device-forecast]
 
 Without --data a synthetic low-rank + autoregressive matrix of the data set's shape is generated (the data sets are
 not redistributable).  Every window is trained on ONE resident GPU session: the series are uploaded once, each window
-appends its 24 new timestamps and re-applies the per-series normalisation on the device."""
+appends its 24 new timestamps and re-applies the per-series normalisation on the device.  With --device-forecast the
+forecasts and their scoring stay on the device too: no factor is downloaded between windows."""
 import argparse
 import os
 import sys
@@ -30,6 +31,7 @@ def main():
     ap.add_argument('--preset', default='electricity', choices=sorted(PRESETS))
     ap.add_argument('--windows', type=int, default=7)
     ap.add_argument('--iters', type=int, default=40)
+    ap.add_argument('--device-forecast', action='store_true', help='forecast and score every window on the device')
     args = ap.parse_args()
     cfg = PRESETS[args.preset]
     if args.data:
@@ -41,7 +43,8 @@ def main():
         Y = np.ascontiguousarray((d['Y'] + 0.05 * np.random.RandomState(1).randn(T, n)) * level + 2.0 * level)
     t0 = time.time()
     metrics = trmf.rolling_validate(Y, LAGS, cfg['k'], 24, args.windows, cfg['lambdaI'], cfg['lambdaAR'], cfg['lambdaLag'],
-                                    max_iter=args.iters, threshold=None, transform=True, seed=0, missing=False)
+                                    max_iter=args.iters, threshold=None, transform=True, seed=0, missing=False,
+                                    forecast_on_device=args.device_forecast)
     print('{} x {} series, {} windows x {} iterations: {:.2f} s'.format(Y.shape[0], Y.shape[1], args.windows, args.iters, time.time() - t0))
     print(metrics)
 

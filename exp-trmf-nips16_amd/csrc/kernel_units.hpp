@@ -13,12 +13,13 @@
 //   unit_split.hip     the split path of long rows (round 6): gram_part_kernel (8), fsolve_*_long_kernel (8), gram_x_long_kernel (16)
 //   unit_full.hip      the MFMA kernels of the full-observation path (20)
 //   unit_heldout.hip   heldout_eval_kernel (5): the model at a resident set of held-out positions (trmf_session_eval_heldout)
+//   unit_forecast.hip  forecast_rollout_kernel, forecast_score_kernel (5): the next timestamps forecast and scored (trmf_session_forecast)
 //
 // A unit defines TRMF_UNIT before including this file; the non-template kernels of the shared headers are compiled by the main
 // unit only (#if !defined(TRMF_UNIT) around them).
 #pragma once
 
-// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out; the kernels of these families
+// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast; the kernels of these families
 // have their BODIES only where TRMF_UNIT_BODIES is defined -- the main unit sees declarations, so that it neither compiles them
 // nor runs them through the optimiser as `extern template` would (available_externally bodies: 3 of its 3.5 minutes))
 #if defined(TRMF_UNIT) || defined(TRMF_SINGLE_UNIT)
@@ -37,6 +38,9 @@
 #endif
 #if !defined(TRMF_UNIT) || TRMF_UNIT == 5
 #include "heldout_kernels.hpp"
+#endif
+#if !defined(TRMF_UNIT) || TRMF_UNIT == 6
+#include "forecast_kernels.hpp"
 #endif
 #if !defined(TRMF_UNIT)
 #include "cg_persist_args.hpp"     // the declaration only: the body is unit_persist.hip's business
@@ -126,6 +130,12 @@ namespace trmf {
 #define TRMF_UNIT_HELDOUT(X)                                                                                                 \
     X void heldout_eval_kernel<0>(HeldoutArgs); X void heldout_eval_kernel<1>(HeldoutArgs); X void heldout_eval_kernel<2>(HeldoutArgs); \
     X void heldout_eval_kernel<3>(HeldoutArgs); X void heldout_eval_kernel<4>(HeldoutArgs);
+
+// forecasting (forecast_kernels.hpp): the score kernel as NT = 1..4 for k <= 64 and NT = 0 for 64 < k <= 1024.  The roll-out is
+// not a template: its body is compiled where TRMF_UNIT_BODIES is defined, i.e. by unit_forecast.hip alone among the units.
+#define TRMF_UNIT_FORECAST(X)                                                                                                \
+    X void forecast_score_kernel<0>(ScoreArgs); X void forecast_score_kernel<1>(ScoreArgs); X void forecast_score_kernel<2>(ScoreArgs); \
+    X void forecast_score_kernel<3>(ScoreArgs); X void forecast_score_kernel<4>(ScoreArgs);
 
 #define TRMF_DEFINE_KERNEL template __global__
 

@@ -504,8 +504,12 @@ struct TrmfSessionImpl : SessionXPhase {
         {   // W: T0 rows kept, Tn rows rolled out by the AR model, one all-zero row at the end
             if (W2.alloc((size_t)(T1 + 1) * KP)) return kFail;
             TRMF_HIP_CHECK(hipMemcpyAsync(W2.p, W.p, (size_t)T0 * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-            hipLaunchKernelGGL(latent_forecast_kernel, dim3(1), dim3(64), 0, stream, W2.p, T0, T1, KP, NT, k, lag_set.p, nlag, theta.p);
-            TRMF_HIP_CHECK(hipGetLastError());
+            // rank <= 64: the one-wavefront kernel this path has always used (its digests stay); above: the forecast's roll-out,
+            // which covers every rank (the one-wavefront kernel rolled only the first 64 columns forward)
+            if (k <= kMaxRank) {
+                hipLaunchKernelGGL(latent_forecast_kernel, dim3(1), dim3(64), 0, stream, W2.p, T0, T1, KP, NT, k, lag_set.p, nlag, theta.p);
+                TRMF_HIP_CHECK(hipGetLastError());
+            } else if (launch_rollout(W.p, T0, Tn, W2.p + (size_t)T0 * KP, nullptr)) return kFail;
             TRMF_HIP_CHECK(hipStreamSynchronize(stream));
         }
         // ---- commit ----
@@ -937,6 +941,96 @@ struct TrmfSessionImpl : SessionXPhase {
         }
         out->count = (uint64_t)h[0]; out->count_nonzero = (uint64_t)h[1];
         out->sq_err = h[2]; out->abs_err = h[3]; out->abs_truth = h[4]; out->rel_err = h[5];
+        return 0;
+    }
+    // ---- forecasting (trmf_session_forecast / _forecast_scores / _forecast_reset; forecast_kernels.hpp) -------------------------
+    // Rows [T0, T0 + steps) of the AR roll-out of Wsrc (T0 rows) into `roll` (steps x KP, column-interleaved; the caller has zeroed
+    // the pads) and, if asked for, into `flat` (steps x k row-major).  Any rank 1..1024: one thread per latent dimension.
+    int launch_rollout(const real *Wsrc, int T0, int steps, real *roll, real *flat) {
+        RolloutArgs a{Wsrc, roll, flat, lag_set.p, theta.p, T0, steps, KP, NT, k, nlag, 0};
+        const size_t lds = rollout_lds_bytes(nlag, midx);           // lags, Theta and the last `midx` rows of a workgroup's 64 columns
+        if (midx > 0 && midx <= T0 && lds <= kLdsMax && !test_env("TRMF_FORECAST_GLOBAL")) {      // (the knob: the global-memory form where the LDS form would fit)
+            if (allow_dyn_lds(forecast_rollout_kernel, lds, "forecast roll-out")) return kFail;
+            a.reach = midx;
+        }
+        hipLaunchKernelGGL(forecast_rollout_kernel, dim3((k + 63) / 64), dim3(64), a.reach ? lds : 0, stream, a);
+        TRMF_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    // Reads W, H, Theta and the transform coefficients, in stream order after everything enqueued before (the caller has validated
+    // the arguments and synchronised the session); the rolled rows live in scratch.  The outputs and the score table change only
+    // when every step has succeeded.
+    int forecast(int steps, bool clip, double threshold, const PyMatrix *truth, real *Ynew, real *Wnew) {
+        FillStreamScope fill(stream);
+        const size_t NY = (size_t)steps * n, NW = (size_t)steps * k, NT6 = (size_t)n * kFcSums;
+        const bool score = truth != nullptr;
+        DevBuf<real> roll, flat, tru, yd;
+        std::vector<real> blk;
+        SyncStreamOnExit drain(stream);
+        if (roll.alloc((size_t)steps * KP) || (Wnew && flat.alloc(NW, false)) || (Ynew && yd.alloc(NY, false))) return kFail;
+        if (score) {
+            const real *src = (const real *)truth->val;
+            if (truth->type != TRMF_DENSE_ROWMAJOR) { (void)dense_rows_to_rowmajor(truth, blk); src = blk.data(); }
+            if (tru.upload(src, NY)) return kFail;
+            if (fc_table[0].n != NT6 || fc_table[1].n != NT6 || fc_prev[0].n != (size_t)n || fc_prev[1].n != (size_t)n) {     // first scored call since a reset
+                if (fc_table[0].alloc(NT6) || fc_table[1].alloc(NT6) || fc_prev[0].alloc(n) || fc_prev[1].alloc(n)) return kFail;
+                fc_cur = 0; fc_rows = 0;
+            }
+        }
+        if (launch_rollout(W.p, T, steps, roll.p, Wnew ? flat.p : nullptr)) return kFail;
+        if (score || Ynew) {
+            const int in = fc_cur, out = 1 - fc_cur;
+            ScoreArgs a{H.p, roll.p, score ? tru.p : nullptr, Ynew ? yd.p : nullptr, has_transform ? tr_a.p : nullptr, has_transform ? tr_b.p : nullptr,
+                        score ? fc_table[in].p : nullptr, score ? fc_table[out].p : nullptr, score ? fc_prev[in].p : nullptr, score ? fc_prev[out].p : nullptr,
+                        (real)threshold, clip ? 1 : 0, fc_rows > 0 ? 1 : 0, n, steps, KP, NT, forecast_rows_per_pass(KP, generic)};
+            const dim3 grid((n + 255) / 256);
+            switch (generic ? 0 : NT) {
+                case 1: hipLaunchKernelGGL(forecast_score_kernel<1>, grid, dim3(256), 0, stream, a); break;
+                case 2: hipLaunchKernelGGL(forecast_score_kernel<2>, grid, dim3(256), 0, stream, a); break;
+                case 3: hipLaunchKernelGGL(forecast_score_kernel<3>, grid, dim3(256), 0, stream, a); break;
+                case 4: hipLaunchKernelGGL(forecast_score_kernel<4>, grid, dim3(256), 0, stream, a); break;
+                default: hipLaunchKernelGGL(forecast_score_kernel<0>, grid, dim3(256), 0, stream, a); break;
+            }
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        // the outputs come back through host staging (pinned memory of the library when they fit) and are copied out together
+        const size_t bY = Ynew ? NY * sizeof(real) : 0, bW = Wnew ? NW * sizeof(real) : 0;
+        std::unique_lock<std::mutex> lease;
+        std::vector<unsigned char> fallback;
+        unsigned char *base = nullptr;
+        if (bY + bW) {
+            base = HostStager::current().staging(bY + bW, lease);
+            if (!base) {
+                try { fallback.resize(bY + bW); } catch (const std::bad_alloc &) { set_error("host staging of the forecast: out of memory"); return kFail; }
+                base = fallback.data();
+            }
+            if (bY) TRMF_HIP_CHECK(hipMemcpyAsync(base, yd.p, bY, hipMemcpyDeviceToHost, stream));
+            if (bW) TRMF_HIP_CHECK(hipMemcpyAsync(base + bY, flat.p, bW, hipMemcpyDeviceToHost, stream));
+        }
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        // ---- commit ----
+        if (bY) HostStager::parallel_copy(Ynew, base, bY);
+        if (bW) std::memcpy(Wnew, base + bY, bW);
+        if (score) { fc_cur = 1 - fc_cur; fc_rows += (uint64_t)steps; }
+        return 0;
+    }
+    int forecast_scores(uint64_t *rows_scored, double *per_series) {
+        const size_t NT6 = (size_t)n * kFcSums;
+        if (per_series) {
+            std::vector<double> h(NT6, 0.0);
+            if (fc_table[fc_cur].n == NT6) {
+                TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+                TRMF_HIP_CHECK(hipMemcpy(h.data(), fc_table[fc_cur].p, NT6 * sizeof(double), hipMemcpyDeviceToHost));
+            }
+            std::memcpy(per_series, h.data(), NT6 * sizeof(double));
+        }
+        if (rows_scored) *rows_scored = fc_rows;
+        return 0;
+    }
+    int forecast_reset() {
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        for (int q = 0; q < 2; q++) { fc_table[q].release(); fc_prev[q].release(); }      // the next scored call starts from zeroed ones
+        fc_cur = 0; fc_rows = 0;
         return 0;
     }
     // New regularisation weights for the iterations enqueued from now on: the session's own copies (F-solve, Theta-solve, the

@@ -196,6 +196,16 @@ struct SessionState {
     DevBuf<uint32_t> ho_row, ho_col;
     DevBuf<real> ho_val, ho_pred;
     DevBuf<double> ho_part, ho_sums;
+
+    // ---- forecast scores (trmf_session_forecast / _forecast_scores / _forecast_reset; forecast_kernels.hpp) -------------------
+    // Six fp64 sums per series, accumulated over every scored forecast since the last reset, and the last truth row of the
+    // previous scored call (the naive-forecast term of MASE runs across calls).  Two generations of each: a call reads one and
+    // writes the other, and fc_cur moves only once the whole call has succeeded.  append_rows, rewind, set_lambdas and
+    // set_series_transform leave them alone -- a rolling evaluation does all of them between windows.
+    DevBuf<double> fc_table[2];
+    DevBuf<real> fc_prev[2];
+    int fc_cur = 0;
+    uint64_t fc_rows = 0;                     // forecast rows scored since the last reset
     // fp32: four systems per wavefront (fsolve_quad_kernel); fp64: one system per wavefront, factorised in the MFMA
     // accumulator layout (fsolve_mfma_kernel)
     // X-side Gram build across ranks: sharded rows + all-gather of G (64 MB at config 3) pays only when a

@@ -461,6 +461,42 @@ int32_t trmf_session_eval_heldout(TrmfSession *s, TrmfHeldoutSums *out, void *pr
     if (rc == 0) *out = sums;
     return rc;
 }
+// Forecast: like the held-out calls, every argument is checked on the calling thread before any rank's worker runs.
+int32_t trmf_session_forecast(TrmfSession *s, int32_t steps, int32_t clip, double threshold, const PyMatrix *truth, void *Ynew, void *Wnew) {
+    if (!s) { set_error("null session"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (steps < 1) { set_error("forecast: steps must be at least 1"); return kFail; }
+    if ((uint64_t)f->T + (uint64_t)steps + 1 >= (1ull << 24) || (uint64_t)steps * (uint64_t)f->n >= (1ull << 32)) {
+        set_error("forecast: the window would exceed 32-bit device indices"); return kFail;
+    }
+    if (clip && !std::isfinite(threshold)) { set_error("forecast: the threshold must be finite"); return kFail; }
+    if (truth) {
+        if (truth->type != TRMF_DENSE_ROWMAJOR && truth->type != TRMF_DENSE_COLMAJOR) { set_error("forecast: the truth must be a dense PyMatrix"); return kFail; }
+        if (truth->rows != (uint64_t)steps || truth->cols != (uint64_t)f->n) {
+            set_error("forecast: the truth is " + std::to_string(truth->rows) + " x " + std::to_string(truth->cols) + ", the forecast " + std::to_string(steps) +
+                      " x " + std::to_string(f->n));
+            return kFail;
+        }
+        if (!truth->val) { set_error("forecast: the truth lacks its values"); return kFail; }
+    }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    if (HND(s)->all([&](TrmfSessionImpl *t) { return t->sync(); })) return kFail;       // every rank holds the same factors: rank 0 answers
+    return HND(s)->rank0([&](TrmfSessionImpl *t) { return t->forecast(steps, clip != 0, threshold, truth, (real *)Ynew, (real *)Wnew); });
+}
+int32_t trmf_session_forecast_scores(TrmfSession *s, uint64_t *rows_scored, TrmfSeriesSums *per_series) {
+    if (!s) { set_error("null session"); return kFail; }
+    static_assert(sizeof(TrmfSeriesSums) == kFcSums * sizeof(double), "the resident table is an array of TrmfSeriesSums");
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    return HND(s)->rank0([&](TrmfSessionImpl *t) { return t->forecast_scores(rows_scored, reinterpret_cast<double *>(per_series)); });
+}
+int32_t trmf_session_forecast_reset(TrmfSession *s) {
+    if (!s) { set_error("null session"); return kFail; }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    return HND(s)->rank0([&](TrmfSessionImpl *t) { return t->forecast_reset(); });
+}
 int32_t trmf_session_set_lambdas(TrmfSession *s, double lambdaI, double lambdaAR, double lambdaLag) {
     if (!s) { set_error("null session"); return kFail; }
     if (!std::isfinite(lambdaI) || !std::isfinite(lambdaAR) || !std::isfinite(lambdaLag)) { set_error("set_lambdas: weights must be finite"); return kFail; }

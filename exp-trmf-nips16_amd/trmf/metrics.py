@@ -60,3 +60,31 @@ class Metrics(collections.namedtuple('Metrics', _FIELDS)):
             observed = truth != 0
             scores['mape'] = _mean_of_finite(np.abs(err[observed]) / np.abs(truth[observed]))
         return cls(**scores)
+
+    @classmethod
+    def from_series_sums(cls, rows, table):
+        """The seven fields from the per-series sums of ``rows`` scored forecast rows (``Session.forecast_series_sums``:
+        an n x 6 table of sum|e|, sum e^2, sum|y|, sum|y_i - y_{i-1}|, sum_{y != 0} |e|/|y| and the count of y != 0).  Pooled
+        sums are the per-series sums added in series order; a mean over R rows (R - 1 differences) of one series is its sum
+        over R (R - 1), pooled over R n (R - 1) n) values."""
+        table = np.asarray(table, dtype=np.float64)
+        R, n = int(rows), table.shape[0]
+        abs_err, sq_err, abs_truth, abs_dtruth, rel_err, nonzero = (table[:, q] for q in range(6))
+
+        def pooled(column):
+            total = 0.0
+            for v in column:
+                total += float(v)
+            return np.float64(total)
+
+        scores = {}
+        with np.errstate(divide='ignore', invalid='ignore'):
+            N, D = np.float64(R * n), np.float64((R - 1) * n)
+            scores['nd'] = pooled(abs_err) / pooled(abs_truth)
+            scores['nrmse'] = np.sqrt(pooled(sq_err) / N) / (pooled(abs_truth) / N)
+            scores['mase'] = (pooled(abs_err) / N) / (pooled(abs_dtruth) / D)
+            scores['m_nd'] = _mean_of_finite(abs_err / abs_truth)
+            scores['m_nrmse'] = _mean_of_finite(np.sqrt(sq_err / R) / (abs_truth / R))
+            scores['m_mase'] = _mean_of_finite((abs_err / R) / (abs_dtruth / np.float64(R - 1)))
+            scores['mape'] = pooled(rel_err) / pooled(nonzero)
+        return cls(**scores)

@@ -36,6 +36,15 @@ class TrmfHeldoutSums(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TrmfSeriesSums(ctypes.Structure):
+    """One series' sums over the scored forecasts (include/trmf_abi.h); ``Metrics.from_series_sums`` turns the table into scores."""
+    _fields_ = [('abs_err', c_double), ('sq_err', c_double), ('abs_truth', c_double), ('abs_dtruth', c_double),
+                ('rel_err', c_double), ('count_nonzero', c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class TrmfTrainProfile(ctypes.Structure):
     """Split of the last c_trmf_train call of this process (include/trmf_abi.h)."""
     _fields_ = [('total_s', c_double), ('setup_s', c_double), ('upload_s', c_double), ('compute_s', c_double),
@@ -89,6 +98,12 @@ def bind(lib):
         lib.trmf_session_eval_heldout.restype = c_int32
         lib.trmf_session_set_lambdas.argtypes = [c_void_p, c_double, c_double, c_double]
         lib.trmf_session_set_lambdas.restype = c_int32
+    if hasattr(lib, 'trmf_session_forecast'):         # (absent from libraries built before on-device forecasting)
+        lib.trmf_session_forecast.argtypes = [c_void_p, c_int32, c_int32, c_double, P, c_void_p, c_void_p]
+        lib.trmf_session_forecast.restype = c_int32
+        lib.trmf_session_forecast_scores.argtypes = [c_void_p, POINTER(c_uint64), c_void_p]
+        lib.trmf_session_forecast_scores.restype = c_int32
+        lib.trmf_session_forecast_reset.argtypes = [c_void_p]; lib.trmf_session_forecast_reset.restype = c_int32
     lib.trmf_dist_get_unique_id.argtypes = [c_void_p]; lib.trmf_dist_get_unique_id.restype = c_int32
     lib.trmf_dist_init.argtypes = [c_int32, c_int32, c_void_p]; lib.trmf_dist_init.restype = c_int32
     lib.trmf_dist_init_callback.argtypes = [c_int32, c_int32, ALLGATHERV_FN, c_void_p]
@@ -223,6 +238,54 @@ class Session(object):
             sums, pred = self.eval_heldout_sums(True)
             return ImputeMetrics.from_sums(sums), pred
         return ImputeMetrics.from_sums(self.eval_heldout_sums())
+
+    def forecast(self, steps, threshold=None, truth=None, return_forecast=True, return_latent=False):
+        """The next ``steps`` timestamps from the current factors, on the device: W rolled forward by the AR model (the bits of
+        ``Model.latent_forecast``), times H, clipped from below at ``threshold`` if one is given, mapped back through the session's
+        series transform if one is active.  With ``truth`` (``steps x n``, raw values of the session's dtype) the forecast is also
+        scored into the resident per-series table (``forecast_scores``).  Returns ``Ynew``, ``(Ynew, Wnew)`` with
+        ``return_latent``, ``Wnew`` alone without ``return_forecast``, or ``None``.  Nothing the training sees is changed."""
+        dt = np.dtype(self.model.W.dtype)
+        n, k = self.model.n, self.model.k
+        steps = int(steps)
+        pyT = None
+        if truth is not None:
+            if isinstance(truth, PyMatrix):
+                pyT = truth
+            elif smat.issparse(truth):
+                pyT = PyMatrix(truth, dtype=dt)            # refused by the library: the truth of a forecast is dense
+            else:
+                truth = np.asarray(truth)
+                if truth.dtype != dt:
+                    raise TypeError('forecast: the truth is {}, the session forecasts in {}'.format(truth.dtype, dt))
+                if truth.ndim != 2:
+                    raise ValueError('forecast: the truth must be a steps x n array')
+                pyT = PyMatrix(truth, dtype=dt)
+        Ynew = np.empty((max(steps, 0), n), dtype=dt) if return_forecast else None
+        Wnew = np.empty((max(steps, 0), k), dtype=dt) if return_latent else None
+        self._check(self.lib.trmf_session_forecast(
+            self.handle, steps, int(threshold is not None), float(threshold) if threshold is not None else 0.0,
+            byref(pyT) if pyT is not None else None,
+            Ynew.ctypes.data if Ynew is not None else None, Wnew.ctypes.data if Wnew is not None else None), 'trmf_session_forecast')
+        if return_forecast and return_latent:
+            return Ynew, Wnew
+        return Ynew if return_forecast else Wnew
+
+    def forecast_series_sums(self):
+        """(rows scored since the last reset, n x 6 float64 table in ``TrmfSeriesSums`` order)."""
+        rows = c_uint64(0)
+        table = np.zeros((self.model.n, len(TrmfSeriesSums._fields_)), dtype=np.float64)
+        self._check(self.lib.trmf_session_forecast_scores(self.handle, byref(rows), table.ctypes.data), 'trmf_session_forecast_scores')
+        return int(rows.value), table
+
+    def forecast_scores(self):
+        """``Metrics`` of every forecast scored since the last reset (the sums were formed on the device)."""
+        from .metrics import Metrics
+        return Metrics.from_series_sums(*self.forecast_series_sums())
+
+    def reset_forecast_scores(self):
+        self._check(self.lib.trmf_session_forecast_reset(self.handle), 'trmf_session_forecast_reset')
+        return self
 
     def download(self):
         m = self.model

@@ -23,7 +23,7 @@ import numpy as np
 import scipy.sparse as smat
 
 from .metrics import Metrics
-from .model import Model
+from .model import Model, NormalizedTransform
 
 
 def _as_training_matrix(block, missing):
@@ -54,6 +54,26 @@ def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing,
             yield model
 
 
+def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose):
+    """The whole rolling evaluation from one resident session: every window is trained, forecast and scored on the device
+    (``Session.forecast`` with the window's truth), the next window's rows are appended and, if asked for, a transform
+    refitted on the grown prefix is handed over.  No factor is downloaded and no host model is rebuilt between windows."""
+    from .session import Session
+    model = Model.initialize(Y[:cuts[0]], lag_set, k, seed=seed, transform=transform)
+    with Session(_as_training_matrix(Y[:cuts[0]], missing), model, missing=missing, verbose=verbose,
+                 log_norms=bool(verbose), timing=0, **hyper) as sess:
+        if model.transform is not None:
+            sess.set_transform(model.transform)
+        for i, cut in enumerate(cuts):
+            if i > 0:
+                sess.append_rows(_as_training_matrix(Y[cuts[i - 1]:cut], missing))
+                if transform is not None:
+                    sess.set_transform(NormalizedTransform(Y[:cut]))
+            sess.run(max_iter)
+            sess.forecast(window_size, threshold=threshold, truth=np.ascontiguousarray(Y[cut:cut + window_size]), return_forecast=False)
+        return sess.forecast_scores()
+
+
 def _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, threads, verbose):
     """Yield the trained model of every window, each from its own upload (needed with a per-window transform)."""
     from .trmf import train
@@ -67,12 +87,25 @@ def _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, tr
 
 def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5, lambdaAR=50, lambdaLag=0.5,
                      max_iter=20, missing=True, threshold=0, transform=None, threads=16, verbose=0, seed=0,
-                     resident=True):
+                     resident=True, forecast_on_device=False):
+    """``forecast_on_device=True`` keeps the forecasts and their scoring on the device as well (one session, no download and no
+    host model per window); it needs the resident path and a dense ``Y``, and says so where that does not hold."""
     T, n = Y.shape
     horizon = nr_windows * window_size
     assert T > horizon, 'series too short for {} windows of {}'.format(nr_windows, window_size)
     cuts = [T - horizon + i * window_size for i in range(nr_windows)]        # training prefix of window i = Y[:cuts[i]]
     hyper = dict(lambdaI=lambdaI, lambdaAR=lambdaAR, lambdaLag=lambdaLag)
+    if forecast_on_device:
+        if not isinstance(Y, np.ndarray):
+            raise ValueError('forecast_on_device: needs a dense NumPy Y (a sparse Y has no resident rolling evaluation)')
+        if Y.dtype not in (np.float32, np.float64):
+            raise ValueError('forecast_on_device: Y is {}, the device forecasts in float32 or float64'.format(Y.dtype))
+        if not resident:
+            raise ValueError('forecast_on_device: needs the resident path (resident=True)')
+        if transform is not None and missing:
+            raise ValueError('forecast_on_device: a transform with missing=True is refitted on the host per window; '
+                             'the device applies one only to dense full-observation training (missing=False)')
+        return _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose)
     # resident: a NumPy Y, and a transform only where the device can apply it (dense full-observation training)
     if resident and isinstance(Y, np.ndarray) and (transform is None or (not missing and Y.dtype in (np.float32, np.float64))):
         models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose)

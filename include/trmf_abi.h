@@ -261,6 +261,40 @@ TRMF_API int32_t trmf_session_eval_heldout(TrmfSession *s, TrmfHeldoutSums *out,
  * a session created with l' from the marked model.  0, or -1 for a value that is not finite. */
 TRMF_API int32_t trmf_session_set_lambdas(TrmfSession *s, double lambdaI, double lambdaAR, double lambdaLag);
 
+/* --- forecasting: the next timestamps of a resident model, forecast and scored on the device ----------------------------
+ * The rolling evaluation of the paper (and of rolling_validate) forecasts a window from the current factors, scores it against
+ * the truth, appends the window and trains on.  These calls do the forecast and the scoring where the factors live.
+ *
+ * Six fp64 sums per series, accumulated over every scored forecast since the last reset (e = forecast - truth y, formed in
+ * fp64 from the two element-type values):
+ *   abs_err sum|e|   sq_err sum e^2   abs_truth sum|y|   abs_dtruth sum|y_i - y_{i-1}| over consecutive scored rows (across
+ *   calls too: the session keeps the last truth row; the very first scored row contributes nothing)
+ *   rel_err sum over y != 0 of |e|/|y|   count_nonzero the number of y != 0                                               */
+typedef struct {
+    double abs_err, sq_err, abs_truth, abs_dtruth, rel_err, count_nonzero;
+} TrmfSeriesSums;
+/* Blocking, ordered after every run() enqueued before; reads W, H, the lag weights and the series-transform coefficients and
+ * changes nothing a later run() can see (W is not extended; the iteration counter, the statistics, the mark and the measured
+ * decisions are untouched).
+ *   roll-out   Wnew[i][t] = sum_l W[i - lag_l][t] * lag_val(l, t) for i = rows .. rows + steps - 1: each product rounded to the
+ *              element type, summed over the lags in ascending order -- the bits of the front end's Model.latent_forecast,
+ *              for every rank 1..1024
+ *   forecast   y = Wnew[i] . H[j] in the element type; clip != 0: y = max(y, threshold); with an active series transform
+ *              y -> (y - b_j) / a_j (otherwise the forecast is in the training scale)
+ *   truth      NULL, or a dense steps x n PyMatrix of THIS library's element type (a PyMatrix does not carry its element type:
+ *              the caller answers for it), finite, in the scale of the value just produced: every series' sums grow by the
+ *              steps rows in timestamp order, one thread per series, no atomics -- the same bits every time
+ *   Ynew       NULL, or steps x n reals, row-major;  Wnew: NULL, or steps x k reals, row-major
+ * 0, or -1 with trmf_last_error() (steps < 1, a truth that is not dense or not steps x n, a window beyond 32-bit device indices, a
+ * device failure) with Ynew, Wnew, the sums and the session as they were.  With TRMF_DEVICES every rank holds the same factors
+ * and rank 0 forecasts; with a communicator every process forecasts from its own copy. */
+TRMF_API int32_t trmf_session_forecast(TrmfSession *s, int32_t steps, int32_t clip, double threshold, const PyMatrix *truth,
+                                       void *Ynew, void *Wnew);
+/* rows_scored: NULL, or the number of forecast rows scored since the last reset; per_series: NULL, or n records. */
+TRMF_API int32_t trmf_session_forecast_scores(TrmfSession *s, uint64_t *rows_scored, TrmfSeriesSums *per_series);
+/* Zero the sums, the row count and the kept truth row.  append_rows, rewind, set_lambdas and set_series_transform leave them. */
+TRMF_API int32_t trmf_session_forecast_reset(TrmfSession *s);
+
 /* --- multi-GPU (one process per GPU; RCCL all-gathers over xGMI) ---------------------------- */
 #define TRMF_UNIQUE_ID_BYTES 128
 /* Rank 0: create an RCCL unique id; the caller broadcasts the bytes to all ranks
