@@ -478,9 +478,6 @@ __global__ __launch_bounds__(kArThreads) void ar_tile_kernel(XParams p, XState *
 // are in flight under the previous group's products), and thread (row, t) reads column t above the diagonal and row t
 // beyond it, in the same order s = 0 .. k-1 as the full form: the results are bit-identical.
 __host__ __device__ inline size_t packed_gram_elems(int k) { return (((size_t)k * (k + 1) / 2) + 1) & ~(size_t)1; }
-#ifndef TRMF_APPLY_ABL
-#define TRMF_APPLY_ABL 0              // scripts/ubench/apply_packed.hip: 1 = no products, 2 = no LDS copy either
-#endif
 // STAGES = 16-byte loads per thread and row group >= rpb * packed_gram_elems(k) / 512 (17 at k = 64), a template
 // parameter because the loads and the LDS copy must be straight-line code: with a (uniform) branch per load the
 // compiler waits for each load before issuing the next (measured: 10.9 us per row group, 296 us per launch at config 5,
@@ -499,7 +496,7 @@ __global__ __launch_bounds__(256, 2) void apply_kernel(XParams p, const XState *
                                                     real *__restrict__ out, int dot_mode,
                                                     double *__restrict__ Pdot, int rpb,
                                                     int row0, int nrows, int slot0) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char apply_smem[];   // k*k reals when the Gram is shared (gstride == 0)
+    extern __shared__ __attribute__((aligned(16))) unsigned char apply_smem[];   // PACKED: the packed Grams of a row group (STAGES * 512 reals)
     __shared__ double smem[256];
     __shared__ real vs[256];
     // cg_it >= 0: this is H d of CG iteration cg_it (d = v, residual = rvec): nothing to do once the CG has stopped at
@@ -508,12 +505,7 @@ __global__ __launch_bounds__(256, 2) void apply_kernel(XParams p, const XState *
     const bool cg = cg_it >= 0;
     if (cg && st->stop_it <= cg_it) return;
     const int k = p.k, KP = p.KP;
-    const bool shared_gram = !PACKED && p.gstride == 0;          // full-observation path: one H^T H for every timestamp
-    real *Gs = reinterpret_cast<real *>(apply_smem);
-    if (shared_gram) {
-        for (int e = threadIdx.x; e < k * k; e += 256) Gs[e] = G[e];
-        __syncthreads();
-    }
+    real *Gs = reinterpret_cast<real *>(apply_smem);    // (a shared Gram -- full observation -- never comes here: apply_shared_mfma_kernel / apply_wide_kernel)
     const int lr = threadIdx.x / k, t = threadIdx.x - lr * k;     // t: logical column
     const int tp = colpos(t, p.NT);                                 // its position in a vector row
     const bool active_lane = lr < rpb;
@@ -550,10 +542,7 @@ __global__ __launch_bounds__(256, 2) void apply_kernel(XParams p, const XState *
         vs[threadIdx.x] = x;
         if constexpr (PACKED) {
 #pragma unroll
-            for (int j = 0; j < STAGES; j++) {
-                if (TRMF_APPLY_ABL == 2) { asm volatile("" ::"v"(stage[j])); continue; }
-                *reinterpret_cast<Pair *>(Gs + 2 * threadIdx.x + 512 * j) = stage[j];
-            }
+            for (int j = 0; j < STAGES; j++) *reinterpret_cast<Pair *>(Gs + 2 * threadIdx.x + 512 * j) = stage[j];
         }
         __syncthreads();
         if constexpr (PACKED)
@@ -566,8 +555,7 @@ __global__ __launch_bounds__(256, 2) void apply_kernel(XParams p, const XState *
                 const real *U = Gs + lr * Lp;
                 int up = t;                                         // (s, t) for s <= t: s k - s (s - 1) / 2 + t - s
                 const int across = t * k - t * (t - 1) / 2 - t;     // (t, s) for s > t: this + s
-                if (TRMF_APPLY_ABL) acc = (double)U[t];
-                for (int s0 = 0; s0 < (TRMF_APPLY_ABL ? 0 : k); s0 += 8) {   // eight LDS reads in flight, then their products in order
+                for (int s0 = 0; s0 < k; s0 += 8) {   // eight LDS reads in flight, then their products in order
                     real u[8], w[8];
 #pragma unroll
                     for (int j = 0; j < 8; j++) {
@@ -580,9 +568,6 @@ __global__ __launch_bounds__(256, 2) void apply_kernel(XParams p, const XState *
                     for (int j = 0; j < 8; j++)
                         if (s0 + j < k) acc += (double)u[j] * (double)w[j];
                 }
-            } else if (shared_gram) {
-#pragma unroll 8
-                for (int s = 0; s < k; s++) acc += (double)Gs[s * k + t] * (double)vi[s];
             } else {
                 const real *Gi = G + (size_t)i * p.gstride + t;
 #pragma unroll 8
@@ -643,15 +628,9 @@ __host__ __device__ inline size_t hv_tile_lds_bytes(int TI, int midx, int KP, in
     return a + b + c + (size_t)nlag * KP * (sizeof(double) + sizeof(real)) + (size_t)nlag * sizeof(int);  // + lambdaAR*Theta, Theta, lag_set
 }
 constexpr int kHvThetaRegs = 3;                  // Theta elements per thread loaded ahead of the scalar prologue
-#ifndef TRMF_HV_RESU
-#define TRMF_HV_RESU 2
-#endif
-constexpr int kHvResU = TRMF_HV_RESU;                       // AR residual work items (4 columns each) a thread carries through the lag loop
+constexpr int kHvResU = 2;                       // AR residual work items (4 columns each) a thread carries through the lag loop
 constexpr int kHvOperandRegs = 12;               // operand elements per thread requested ahead of the Gram
-#ifndef TRMF_HV_UPFRONT
-#define TRMF_HV_UPFRONT 96
-#endif
-constexpr int kHvGramUpfront = TRMF_HV_UPFRONT;  // registers of the Gram slice requested before the LDS phases
+constexpr int kHvGramUpfront = 96;               // registers of the Gram slice requested before the LDS phases
 constexpr int kHvGramPad = 4;                    // elements allocated past the Gram cache (vector tail reads)
 // Gram columns per thread: one 16-byte load per Gram row up to rank 40, 8-byte loads above (the thread's
 // slice, KQ loads, has to stay within ~160 of the 256 registers)
@@ -682,9 +661,6 @@ __device__ __forceinline__ void buffer_store_real(__amdgpu_buffer_rsrc_t rsrc, i
 template <int VEC> struct GramVec { real c[VEC]; };
 template <int VEC>
 __device__ __forceinline__ GramVec<VEC> gram_load(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-#if defined(TRMF_HV_ABL) && (TRMF_HV_ABL & 1)
-    GramVec<VEC> z; for (int c = 0; c < VEC; c++) z.c[c] = (real)voff; return z;
-#endif
     if constexpr (VEC * sizeof(real) == 16)
         return __builtin_bit_cast(GramVec<VEC>, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0));
     else
@@ -1174,11 +1150,7 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? 2 : 1) void hv_tile_kernel(XParam
                 MODE == HV_CG_STEP ? buffer_load_real(s_rsrc, ob) : real(0));
     }
     if (MODE == HV_CG_FIRST && stopped) return;             // the gradient already meets the tolerance: s = 0 is written, no product
-#if defined(TRMF_HV_ABL) && (TRMF_HV_ABL & 2)
-    const bool ar_on = false;
-#else
     const bool ar_on = nlag > 0 && p.lambdaAR > 0;
-#endif
     __syncthreads();
     // (2) AR residuals of rows [i0, i0+TI+midx)  (trmf.cpp:110-113 / 136-139), stored to rs in LOGICAL
     //     column order.  A work item is (row, 4 neighbouring positions): per lag it costs two 16-byte LDS

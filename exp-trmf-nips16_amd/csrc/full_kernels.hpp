@@ -259,39 +259,17 @@ __global__ __launch_bounds__(256) void small_gram_reduce_kernel(const double *__
 #endif
 
 // ---- shared-matrix solve: H[i][:] = GS^-1 b_i for every row (posv with n right-hand sides, trmf.cpp:333) ----
-// chol_shared_kernel: ONE workgroup factorises the k x k matrix in LDS (upper Cholesky in val_type, as posv 'U')
-// and leaves U in global memory.  solve_rows_kernel: every workgroup copies U to LDS; a wavefront owns one
+// chol_wave_kernel: ONE wavefront factorises the k x k matrix without LDS or barriers (upper Cholesky in val_type, as posv 'U')
+// and leaves U in global memory.  Lane c keeps column c of the matrix in registers (KMAX values; rows and columns >= k padded
+// with the identity, so no step needs a guard); step j scales row j and subtracts u_js * u_jc from every later row s, u_js
+// arriving as a scalar through v_readlane with a compile-time lane -- the loops are fully unrolled.  Per element: sqrt, divide,
+// one fused multiply-subtract.  (A one-workgroup version with the matrix in LDS -- a chain of 3 k barriers and LDS round trips --
+// took 70 us at k = 60 against 18 us and was removed.)  Writes U (upper part, zeros below).
+// solve_rows_kernel: every workgroup copies U to LDS; a wavefront owns one
 // right-hand side at a time with one unknown per lane, and both substitutions are column-oriented -- after step q
 // every remaining lane has had its U(.,.) * z_q term removed -- so a row costs 2k broadcast + FMA steps on 64 lanes
 // instead of k^2 dependent LDS round trips on one thread.  Forward: the same subtractions in the same order as the
 // row-oriented loop; backward: a row's terms are subtracted in descending instead of ascending order (last bit).
-#if !defined(TRMF_UNIT)      // compiled by the main translation unit only (kernel_units.hpp)
-__global__ __launch_bounds__(256) void chol_shared_kernel(const real *__restrict__ GS, real *__restrict__ Uout, int k) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char ss_raw[];
-    real *U = reinterpret_cast<real *>(ss_raw);          // k x k
-    for (int e = threadIdx.x; e < k * k; e += 256) U[e] = GS[e];
-    __syncthreads();
-    for (int j = 0; j < k; j++) {                        // same loop as theta_solve_kernel
-        const real ajj = sqrt(U[j * k + j]);
-        __syncthreads();
-        for (int c = j + threadIdx.x; c < k; c += 256) U[j * k + c] = (c == j) ? ajj : U[j * k + c] / ajj;
-        __syncthreads();
-        const int m = k - 1 - j;                        // trailing dimension: all (s, c) pairs at once, 256 per pass
-        for (int e = threadIdx.x; e < m * m; e += 256) {
-            const int s = j + 1 + e / m, c = j + 1 + e % m;
-            if (c >= s) U[s * k + c] -= U[j * k + s] * U[j * k + c];
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < k * k; e += 256) Uout[e] = U[e];
-}
-#endif
-// chol_wave_kernel: the same factorisation by ONE wavefront without LDS or barriers.  Lane c keeps column c of the
-// matrix in registers (KMAX values; rows and columns >= k padded with the identity, so no step needs a guard); step
-// j scales row j and subtracts u_js * u_jc from every later row s, u_js arriving as a scalar through v_readlane
-// with a compile-time lane -- the loops are fully unrolled.  Same operations per element as chol_shared_kernel
-// (sqrt, divide, one fused multiply-subtract), ~4x faster at k = 60 (70 -> 18 us): the workgroup version is a chain
-// of 3 k barriers and LDS round trips.  Writes U (upper part, zeros below).
 #if !defined(TRMF_UNIT_BODIES)     // the main translation unit sees the declaration only (kernel_units.hpp)
 template <int NT>
 __global__ void chol_wave_kernel(const real *__restrict__ GS, real *__restrict__ Uout, int k);

@@ -426,42 +426,18 @@ __device__ __forceinline__ void wave_lds_sync() {       // LDS operations of one
 //     read and one FMA.
 // posv('U') of the reference (rf_matrix.h:3008-3014) and this differ by rounding only (fp64 gate 1e-6, tests/).
 #if !defined(TRMF_F32)
-#ifndef TRMF_MFMA_WAVES
-#define TRMF_MFMA_WAVES 2
-#endif
-#ifndef TRMF_RCP_NEWTON
-#define TRMF_RCP_NEWTON 2
-#endif
+constexpr int kMfmaWaves = 2;      // wavefronts per SIMD the fp64 F-solve is built for
+constexpr int kRcpNewton = 2;      // Newton steps behind v_rcp_f64
 __device__ __forceinline__ double recip_pivot(double d) {
     double r = __builtin_amdgcn_rcp(d);
 #pragma unroll
-    for (int i = 0; i < TRMF_RCP_NEWTON; i++) { const double e = fma(-d, r, 1.0); r = fma(r, e, r); }
+    for (int i = 0; i < kRcpNewton; i++) { const double e = fma(-d, r, 1.0); r = fma(r, e, r); }
     return r;
 }
 __host__ __device__ constexpr int upper_tile_index(int ti, int tj, int NT) { return ti * NT - ti * (ti - 1) / 2 + (tj - ti); }
 
-// acc += sum_p (lane BC of the caller's 16-lane row: S.v[p]) * R.v[p] -- four v_fmac_f64 with a DPP row broadcast on the first
-// factor.  Inline assembly: the compiler keeps the broadcast as a separate v_mov_b64_dpp (one more fp64-rate instruction
-// per product).  The leading s_nop covers the two wait states a DPP read needs after a VALU write of its source.
-template <int BC>
-__device__ __forceinline__ void fmac4_row_bcast(double &acc, const Quad<double> &S, const Quad<double> &R) {
-    asm("s_nop 1\n\t"
-        "v_fmac_f64_dpp %0, %1, %5 row_newbcast:%9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %0, %2, %6 row_newbcast:%9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %0, %3, %7 row_newbcast:%9 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %0, %4, %8 row_newbcast:%9 row_mask:0xf bank_mask:0xf"
-        : "+v"(acc)
-        : "v"(S.v[0]), "v"(S.v[1]), "v"(S.v[2]), "v"(S.v[3]), "v"(R.v[0]), "v"(R.v[1]), "v"(R.v[2]), "v"(R.v[3]), "n"(BC));
-}
-#ifndef TRMF_MFMA_TAIL
-#define TRMF_MFMA_TAIL 1       // the Gram's last iteration issues its non-empty groups only (gram_ring TAIL): config 5 rows have ~50 entries
-#endif
-#ifndef TRMF_TRAIL_MFMA
-#define TRMF_TRAIL_MFMA 1      // measured at config 5: 12.6-12.8 ms with the MFMA trailing update, 13.0 ms with the DPP-fused FMAs (7b)
-#endif
-
 #if !defined(TRMF_UNIT_BODIES)     // the main translation unit sees the declaration only (kernel_units.hpp)
-template <int NT, int KMAX, bool TRAIL_MFMA = (TRMF_TRAIL_MFMA != 0)>
+template <int NT, int KMAX>
 __global__ void fsolve_mfma_kernel(const uint32_t *__restrict__ ptr,
                                                                           const uint32_t *__restrict__ idx,
                                                                           const real *__restrict__ val,
@@ -469,11 +445,11 @@ __global__ void fsolve_mfma_kernel(const uint32_t *__restrict__ ptr,
                                                                           real *__restrict__ F, uint32_t row_begin,
                                                                           uint32_t row_end, int k, real lambda,
                                                                           uint32_t zero_row, uint32_t long_m1);
-template <int NT, int KMAX, bool TRAIL_MFMA = (TRMF_TRAIL_MFMA != 0)>
+template <int NT, int KMAX>
 __global__ void fsolve_mfma_long_kernel(SplitRows sp, real *__restrict__ F, int k, real lambda);
 #else
 // LONG: the system of a split row -- one wavefront per long row, its Gram and right-hand side are the sum of the row's partials
-template <int NT, int KMAX, bool TRAIL_MFMA, bool LONG>
+template <int NT, int KMAX, bool LONG>
 __device__ __forceinline__ void fsolve_mfma_body(const uint32_t *__restrict__ ptr,
                                                                           const uint32_t *__restrict__ idx,
                                                                           const real *__restrict__ val,
@@ -510,8 +486,9 @@ __device__ __forceinline__ void fsolve_mfma_body(const uint32_t *__restrict__ pt
         real nowq[NT];
 #pragma unroll
         for (int q = 0; q < NT; q++) nowq[q] = 0;
-        gram_ring<NT, kRingDepth, true, false, false, TRMF_MFMA_TAIL != 0>(st, idx, val, X, zero_row, 4u, lane, nowq, GramDesc{p0, p1, 0},
-                                                                          SingleRowStream{4u * kRingDepth}, [](int) {});
+        // TAIL: the Gram's last iteration issues its non-empty groups only -- config 5 rows have ~50 entries
+        gram_ring<NT, kRingDepth, true, false, false, true>(st, idx, val, X, zero_row, 4u, lane, nowq, GramDesc{p0, p1, 0},
+                                                            SingleRowStream{4u * kRingDepth}, [](int) {});
     }
     // right-hand side: fold the 4 lane groups, then lane l = 16 q + c keeps b[l]
     real y = 0, dinv = 1;
@@ -587,52 +564,21 @@ __device__ __forceinline__ void fsolve_mfma_body(const uint32_t *__restrict__ pt
         // (6) lane group g reads its row back (the final pivot row stays in the accumulators for the back substitution)
 #pragma unroll
         for (int tj = tp; tj < NT; tj++) st.acc[upper_tile_index(tp, tj, NT)][r0] = ps[(kTile * tj + c) * CP + g];
-        if constexpr (TRAIL_MFMA) {
-            // (7a) trailing update on the matrix pipe: the scaled copy of the lane group's row is the A operand, the pivot
-            //      row itself the B operand of ONE v_mfma_f64_16x16x4 per trailing tile
-            real aop[NT];
+        // (7) trailing update on the matrix pipe: the scaled copy of the lane group's row is the A operand, the pivot
+        //     row itself the B operand of ONE v_mfma_f64_16x16x4 per trailing tile.  (Measured at config 5: 12.6-12.8 ms; DPP-fused
+        //     v_fmac_f64 on the vector ALUs instead took 13.0 ms and were removed.)
+        real aop[NT];
 #pragma unroll
-            for (int tj = tp; tj < NT; tj++) aop[tj] = ps[(kTile * tj + c) * CP + 4 + g];
-            if (c <= 4 * r0 + 3) aop[tp] = 0;            // rows at and above the panel are final: the update leaves them alone
-            wave_lds_sync();
+        for (int tj = tp; tj < NT; tj++) aop[tj] = ps[(kTile * tj + c) * CP + 4 + g];
+        if (c <= 4 * r0 + 3) aop[tp] = 0;                // rows at and above the panel are final: the update leaves them alone
+        wave_lds_sync();
 #pragma unroll
-            for (int ti = tp; ti < NT; ti++)
+        for (int ti = tp; ti < NT; ti++)
 #pragma unroll
-                for (int tj = ti; tj < NT; tj++) {
-                    acc_t &C = st.acc[upper_tile_index(ti, tj, NT)];
-                    C = Mfma16<real>::mma(aop[ti], st.acc[upper_tile_index(tp, tj, NT)][r0], C);
-                }
-        } else {
-            // (7b) trailing update on the vector ALUs.  v_mfma_f64_16x16x4 issues in ~100 cycles per SIMD on gfx950
-            //      (scripts/ubench/f64_pipe.hip: 20 flop/clk against 26-32 of v_fma_f64), and a whole-tile update cannot skip
-            //      the rows of a tile row that are already final; here register r of tile (ti, tj) takes
-            //          A[16 ti + g + 4 r][16 tj + c] += sum_p S_p[16 ti + g + 4 r] R'_p[16 tj + c]
-            //      as four v_fmac_f64 whose row operand is a DPP row broadcast (row_newbcast is the one DPP mode fp64 has): the
-            //      lane reads the scaled rows of the column its 16-lane row is ROTATED to, column 16 ti + (c + g) mod 16, so
-            //      that lane 4 r of every row holds S_p[16 ti + g + 4 r].  Rows at and above the panel (registers r <= r0 of
-            //      tile row tp) are skipped: 880 FMAs per rank-64 system, no masks, no MFMA hazard nops.
-            Quad<real> Rq[NT];
-#pragma unroll
-            for (int tj = tp; tj < NT; tj++) Rq[tj] = *reinterpret_cast<const Quad<real> *>(ps + (kTile * tj + c) * CP);
-            static_for<NT>([&](auto Ti) {
-                constexpr int ti = decltype(Ti)::value;
-                if constexpr (ti >= tp) {
-                    const Quad<real> Sq = *reinterpret_cast<const Quad<real> *>(ps + (kTile * ti + ((c + g) & 15)) * CP + 4);
-                    static_for<4>([&](auto Rr) {
-                        constexpr int r = decltype(Rr)::value;
-                        if constexpr (ti > tp || r > r0) {
-#pragma unroll
-                            for (int tj = ti; tj < NT; tj++) {
-                                real a = st.acc[upper_tile_index(ti, tj, NT)][r];
-                                fmac4_row_bcast<4 * r>(a, Sq, Rq[tj]);
-                                st.acc[upper_tile_index(ti, tj, NT)][r] = a;
-                            }
-                        }
-                    });
-                }
-            });
-            wave_lds_sync();
-        }
+            for (int tj = ti; tj < NT; tj++) {
+                acc_t &C = st.acc[upper_tile_index(ti, tj, NT)];
+                C = Mfma16<real>::mma(aop[ti], st.acc[upper_tile_index(tp, tj, NT)][r0], C);
+            }
     });
 
     // ---- back substitution (D L^T) x = z', column oriented, lane = row ----
@@ -667,19 +613,19 @@ __device__ __forceinline__ void fsolve_mfma_body(const uint32_t *__restrict__ pt
     });
     if (lane < k) F[(size_t)row * KP + colpos(lane, NT)] = y * dinv;
 }
-template <int NT, int KMAX, bool TRAIL_MFMA = (TRMF_TRAIL_MFMA != 0)>
-__global__ __launch_bounds__(256, TRMF_MFMA_WAVES) void fsolve_mfma_kernel(const uint32_t *__restrict__ ptr,
+template <int NT, int KMAX>
+__global__ __launch_bounds__(256, kMfmaWaves) void fsolve_mfma_kernel(const uint32_t *__restrict__ ptr,
                                                                           const uint32_t *__restrict__ idx,
                                                                           const real *__restrict__ val,
                                                                           const real *__restrict__ X,
                                                                           real *__restrict__ F, uint32_t row_begin,
                                                                           uint32_t row_end, int k, real lambda,
                                                                           uint32_t zero_row, uint32_t long_m1) {
-    fsolve_mfma_body<NT, KMAX, TRAIL_MFMA, false>(ptr, idx, val, X, F, row_begin, row_end, k, lambda, zero_row, long_m1, SplitRows{});
+    fsolve_mfma_body<NT, KMAX, false>(ptr, idx, val, X, F, row_begin, row_end, k, lambda, zero_row, long_m1, SplitRows{});
 }
-template <int NT, int KMAX, bool TRAIL_MFMA = (TRMF_TRAIL_MFMA != 0)>
-__global__ __launch_bounds__(256, TRMF_MFMA_WAVES) void fsolve_mfma_long_kernel(SplitRows sp, real *__restrict__ F, int k, real lambda) {
-    fsolve_mfma_body<NT, KMAX, TRAIL_MFMA, true>(nullptr, nullptr, nullptr, nullptr, F, 0u, 0u, k, lambda, 0u, 0u, sp);
+template <int NT, int KMAX>
+__global__ __launch_bounds__(256, kMfmaWaves) void fsolve_mfma_long_kernel(SplitRows sp, real *__restrict__ F, int k, real lambda) {
+    fsolve_mfma_body<NT, KMAX, true>(nullptr, nullptr, nullptr, nullptr, F, 0u, 0u, k, lambda, 0u, 0u, sp);
 }
 #endif
 #endif  // !TRMF_F32
@@ -690,7 +636,7 @@ __global__ __launch_bounds__(256, TRMF_MFMA_WAVES) void fsolve_mfma_long_kernel(
 // lanes.  With one system per wavefront (round 1) every broadcast is a v_readlane that
 // feeds a single FMA per lane, and the kernel is VALU-issue bound (~3000 of its ~3500 instructions).
 // Here the four 16-lane rows of a wavefront each own one system: lane (grp, c) holds columns
-// {c, 16+c, 32+c, ...} of system `grp`, one ds_swizzle row-broadcast serves all four systems and
+// {c, 16+c, 32+c, ...} of system `grp`, one row broadcast (row_bcast) serves all four systems and
 // feeds up to NT FMAs per lane, and the back substitution reduces inside the 16-lane row with DPP.
 // The four Grams are accumulated one after the other by ONE gram_ring() stream that runs across the
 // row boundaries (the rows are adjacent in CSR), so the gather pipeline never drains inside a quad.
@@ -699,16 +645,8 @@ __global__ __launch_bounds__(256, TRMF_MFMA_WAVES) void fsolve_mfma_long_kernel(
 // instruction with a few cycles of latency) instead of ds_swizzle, which travels through the LDS pipe (~100 cycles): the pivot
 // broadcast heads the dependent chain of every elimination step (broadcast -> rsq -> scale -> quad broadcast -> MFMA), 40 steps per
 // system, and with three wavefronts per SIMD that latency is not hidden (profiles/r06_fsolve_chain.txt).  Same value either way.
-#ifndef TRMF_ROW_BCAST_DPP
-#define TRMF_ROW_BCAST_DPP 1
-#endif
 template <int SRC> __device__ __forceinline__ float row_bcast(float v) {
-#if TRMF_ROW_BCAST_DPP
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + SRC, 0xf, 0xf, true));
-#else
-    constexpr int pattern = (SRC << 5) | 0x10;          // and_mask = 0x10, or_mask = SRC, xor_mask = 0
-    return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), pattern));
-#endif
 }
 
 template <int NT> __device__ __forceinline__ constexpr int quad_slab_floats() {
@@ -737,9 +675,9 @@ template <int NT> __device__ __forceinline__ constexpr int quad_slab_col_offset(
 // blocks (= one 16-lane row = one system) read the A operand of ONE of its blocks, abid:(R & 3) names it
 // (scripts/ubench/mfma4x4.hip checks the mapping on the device and that the modifiers cost no issue cycles), so
 // the A operand is the lane's own -u[qs] and a step has no LDS-pipe instruction on its chain
-// (profiles/fsolve_trail_abid.txt).  TRMF_TRAIL_ABID=0 builds the form used until then: one ds_swizzle per row
-// quad (row_quad_bcast, ~100 cycles through the LDS pipe and an s_waitcnt) in front of plain MFMAs; same
-// multiplicands, same single rounding, same order -- the factors are bit-identical.  (NT - q(R)) MFMAs per row
+// (profiles/fsolve_trail_abid.txt).  The form used until then had one ds_swizzle per row quad (~100 cycles
+// through the LDS pipe and an s_waitcnt) in front of plain MFMAs; same multiplicands, same single rounding,
+// same order -- the factors were bit-identical.  (NT - q(R)) MFMAs per row
 // quad replace 4 (NT - q) FMAs fed by four broadcasts, and an MFMA issues 512 flops in 8 cycles where four
 // v_fma_f32 take 16; the product is rounded once like fmaf, so the arithmetic is unchanged.
 // Rows <= j inside the first quad see u = 0 and stay as they are.
@@ -750,34 +688,17 @@ template <int NT> __device__ __forceinline__ constexpr int quad_slab_col_offset(
 // treats it as one more unknown fixed at -1:  x_j = -(sum_{t>j} U[j][t] x_t) / U[j][j]  with  x_{KP-1} = -1.
 typedef float quad_f4 __attribute__((ext_vector_type(4)));
 
-// A operand of the trailing update: 1 = broadcast inside the MFMA (cbsz:2 abid:Q), 0 = a ds_swizzle in front of it (see above)
-#ifndef TRMF_TRAIL_ABID
-#define TRMF_TRAIL_ABID 1
-#endif
 // With the swizzles and their waits gone nothing bounds the instruction scheduler's reach inside the unrolled factorisation: it moves
 // work across many elimination steps, <4,64> (exactly 256 VGPRs) spills, and the other instantiations get no faster than the swizzle
-// form.  A scheduling barrier after every TRMF_TRAIL_FENCE steps (NT <= 3) / TRMF_TRAIL_FENCE4 steps (NT = 4) keeps a step's
-// instructions together (0: none).  Measured per spacing, profiles/fsolve_trail_abid.txt: every step is the fastest for both
-// (config 3 F phase 0.364 -> 0.355 ms, k = 64: 0.703 -> 0.679 ms; no barrier: 0.364, and <4,64> does not build).
-#ifndef TRMF_TRAIL_FENCE4
-#define TRMF_TRAIL_FENCE4 1
-#endif
-#ifndef TRMF_TRAIL_FENCE
-#define TRMF_TRAIL_FENCE 1
-#endif
-// value of the quad Q (lanes 4Q..4Q+3) of the caller's 16-lane row, replicated to all four quads of that row
-template <int Q> __device__ __forceinline__ float row_quad_bcast(float v) {
-    constexpr int pattern = ((Q << 2) << 5) | 0x13;      // and_mask = 0b10011, or_mask = 4Q, xor_mask = 0
-    return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), pattern));
-}
-
-template <int NT, int KMAX, bool RHS_IN, int ABL = 0>
+// form.  A scheduling barrier at the end of every elimination step keeps a step's instructions together.  Measured per spacing,
+// profiles/fsolve_trail_abid.txt: every step is the fastest for NT <= 3 and NT = 4 alike (config 3 F phase 0.364 -> 0.355 ms,
+// k = 64: 0.703 -> 0.679 ms; no barrier: 0.364, and <4,64> does not build).
+template <int NT, int KMAX, bool RHS_IN>
 __device__ __forceinline__ void quad_factor_solve(quad_f4 (&a4)[NT][KMAX / 4], float (&bz)[NT], float (&x)[NT], int c) {
     constexpr int NR = KMAX / 4;                         // row quads
     float dinv[NT];
 #pragma unroll
     for (int q = 0; q < NT; q++) dinv[q] = 0;
-    if constexpr (!(ABL & 2))
     static_for<KMAX>([&](auto J) {
         constexpr int j = decltype(J)::value, qj = j >> 4, cj = j & 15, Rj = j >> 2, ij = j & 3;
         {   // one straight-line block: the scheduler can software-pipeline across steps
@@ -800,21 +721,12 @@ __device__ __forceinline__ void quad_factor_solve(quad_f4 (&a4)[NT][KMAX / 4], f
             static_for<NR>([&](auto Rx) {
                 constexpr int R = decltype(Rx)::value, qs = (4 * R) >> 4;
                 if constexpr (4 * R + 3 > j) {
-#if TRMF_TRAIL_ABID
                     // A = -u[4R + (lane & 3)]: quad R & 3 of the lane's own 16-lane row, picked by the instruction
 #pragma unroll
                     for (int q = qs; q < NT; q++) a4[q][R] = __builtin_amdgcn_mfma_f32_4x4x1f32(nu[qs], u[q], a4[q][R], 2, R & 3, 0);
-#else
-                    const float nus = row_quad_bcast<R & 3>(nu[qs]);     // -u[4R + (lane & 3)]
-#pragma unroll
-                    for (int q = qs; q < NT; q++) a4[q][R] = __builtin_amdgcn_mfma_f32_4x4x1f32(nus, u[q], a4[q][R], 0, 0, 0);
-#endif
                 }
             });
-#if TRMF_TRAIL_ABID
-            constexpr int fence = NT >= 4 ? TRMF_TRAIL_FENCE4 : TRMF_TRAIL_FENCE;
-            if constexpr (fence > 0 && j % (fence > 0 ? fence : 1) == fence - 1) __builtin_amdgcn_sched_barrier(0);
-#endif
+            __builtin_amdgcn_sched_barrier(0);
         }
     });
     // back substitution U x = z, row-oriented, reduction inside the 16-lane row (DPP)
@@ -825,7 +737,6 @@ __device__ __forceinline__ void quad_factor_solve(quad_f4 (&a4)[NT][KMAX / 4], f
 #pragma unroll
         for (int q = 0; q < NT; q++) bz[q] = 0;
     }
-    if constexpr (!(ABL & 4))
     static_for<KMAX>([&](auto Jr) {
         constexpr int j = KMAX - 1 - decltype(Jr)::value, qj = j >> 4, cj = j & 15, Rj = j >> 2, ij = j & 3;
         {
@@ -866,17 +777,14 @@ struct QuadStream {
     }
 };
 
-// ABL: compile-time ablation mask for profiling (bit0 skip Gram, bit1 skip factorisation, bit2 skip back solve)
 // 3 wavefronts per SIMD (<= 168 VGPRs): measured 551 -> 481 us at config 3 versus the unconstrained 192
-#ifndef TRMF_QUAD_WAVES
-#define TRMF_QUAD_WAVES 3
-#endif
+constexpr int kQuadWaves = 3;
 // Four column tiles (rank 49..64) need more than the 168 registers of three wavefronts per SIMD: at that bound the <4,56> and
 // <4,64> instantiations spilled 296 / 460 bytes per lane; they are built for two wavefronts per SIMD instead.
 // (profiles/r04_fsolve_k64_fp32.txt has the comparison).
-constexpr int quad_waves(int NT) { return NT >= 4 ? 2 : TRMF_QUAD_WAVES; }
+constexpr int quad_waves(int NT) { return NT >= 4 ? 2 : kQuadWaves; }
 #if !defined(TRMF_UNIT_BODIES)     // the main translation unit sees the declaration only (kernel_units.hpp)
-template <int NT, int KMAX, int ABL = 0>
+template <int NT, int KMAX>
 __global__ void fsolve_quad_kernel(const uint32_t *__restrict__ ptr,
                                                           const uint32_t *__restrict__ idx,
                                                           const float *__restrict__ val,
@@ -889,7 +797,7 @@ __global__ void fsolve_quad_long_kernel(SplitRows sp, float *__restrict__ F, int
 #else
 // LONG: four SPLIT rows per wavefront (positions 4 q .. 4 q + 3 of the long-row list): each system is the sum of its row's partials
 // (split_reduce_kernel -> load_row_sum) instead of a stream of entries; finalisation, factorisation and substitutions are the same code.
-template <int NT, int KMAX, int ABL, bool LONG>
+template <int NT, int KMAX, bool LONG>
 __device__ __forceinline__ void fsolve_quad_body(const uint32_t *__restrict__ ptr,
                                                           const uint32_t *__restrict__ idx,
                                                           const float *__restrict__ val,
@@ -984,7 +892,7 @@ __device__ __forceinline__ void fsolve_quad_body(const uint32_t *__restrict__ pt
             load_row_sum<NT, !PAD>(st, sp, stream.row_ptr_at(sys), lane);
             finalize(sys);
         }
-    } else if constexpr (!(ABL & 1)) {
+    } else {
         float nowq[NT];
 #pragma unroll
         for (int q = 0; q < NT; q++) nowq[q] = 0;
@@ -993,7 +901,7 @@ __device__ __forceinline__ void fsolve_quad_body(const uint32_t *__restrict__ pt
     }
 
     float x[NT];
-    quad_factor_solve<NT, KMAX, PAD, ABL>(a4, bz, x, c);
+    quad_factor_solve<NT, KMAX, PAD>(a4, bz, x, c);
     if (mine) {     // logical columns {c, 16+c, ...} are adjacent in the interleaved layout: one vector store
         RealVec<NT> o;
 #pragma unroll
@@ -1002,7 +910,7 @@ __device__ __forceinline__ void fsolve_quad_body(const uint32_t *__restrict__ pt
         *reinterpret_cast<RealVec<NT> *>(F + (size_t)orow * KP + NT * c) = o;
     }
 }
-template <int NT, int KMAX, int ABL = 0>
+template <int NT, int KMAX>
 __global__ __launch_bounds__(256, quad_waves(NT)) void fsolve_quad_kernel(const uint32_t *__restrict__ ptr,
                                                           const uint32_t *__restrict__ idx,
                                                           const float *__restrict__ val,
@@ -1010,13 +918,13 @@ __global__ __launch_bounds__(256, quad_waves(NT)) void fsolve_quad_kernel(const 
                                                           float *__restrict__ F, uint32_t row_begin,
                                                           uint32_t row_end, int k, float lambda,
                                                           uint32_t zero_row, uint32_t long_m1) {
-    fsolve_quad_body<NT, KMAX, ABL, false>(ptr, idx, val, X, F, row_begin, row_end, k, lambda, zero_row, long_m1, SplitRows{});
+    fsolve_quad_body<NT, KMAX, false>(ptr, idx, val, X, F, row_begin, row_end, k, lambda, zero_row, long_m1, SplitRows{});
 }
 // (one wavefront per SIMD less than the row kernel: the partial sums want registers beside the four systems, and a launch of this
 // kernel is a few hundred wavefronts at most)
 template <int NT, int KMAX>
 __global__ __launch_bounds__(256, quad_waves(NT) - 1) void fsolve_quad_long_kernel(SplitRows sp, float *__restrict__ F, int k, float lambda) {
-    fsolve_quad_body<NT, KMAX, 0, true>(nullptr, nullptr, nullptr, nullptr, F, 0u, 0u, k, lambda, 0u, 0u, sp);
+    fsolve_quad_body<NT, KMAX, true>(nullptr, nullptr, nullptr, nullptr, F, 0u, 0u, k, lambda, 0u, 0u, sp);
 }
 #endif
 

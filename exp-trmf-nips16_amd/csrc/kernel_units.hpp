@@ -81,7 +81,7 @@ namespace trmf {
 #define TRMF_FSOLVE_SIG (const uint32_t *, const uint32_t *, const real *, const real *, real *, uint32_t, uint32_t, int, real, uint32_t, uint32_t)
 #define TRMF_FSOLVE_LONG_SIG (SplitRows, real *, int, real)
 #if defined(TRMF_F32)
-#define TRMF_FSOLVE_ONE(X, NT, KMAX) X void fsolve_quad_kernel<NT, KMAX, 0> TRMF_FSOLVE_SIG;
+#define TRMF_FSOLVE_ONE(X, NT, KMAX) X void fsolve_quad_kernel<NT, KMAX> TRMF_FSOLVE_SIG;
 #define TRMF_FSOLVE_LONG_ONE(X, NT, KMAX) X void fsolve_quad_long_kernel<NT, KMAX> TRMF_FSOLVE_LONG_SIG;
 #else
 #define TRMF_FSOLVE_ONE(X, NT, KMAX) X void fsolve_mfma_kernel<NT, KMAX> TRMF_FSOLVE_SIG;

@@ -138,7 +138,6 @@ struct TrmfSessionImpl : SessionXPhase {
         generic = k > kMaxRank;
         nlag = (int)lag_size; midx = nlag ? (int)lags[nlag - 1] : 0;
         comm = active_comm();
-        if (const char *e = test_env("TRMF_DEBUG_ABLATE")) dbg_flags = atoi(e);
         if (StreamCache::acquire(&stream)) return kFail;
         FillStreamScope fill(stream);
         dense = Y->type != TRMF_SPARSE;
@@ -256,12 +255,7 @@ struct TrmfSessionImpl : SessionXPhase {
             nba = std::max(1, (blocks + passes - 1) / passes);
             const size_t need = apply_shared_lds_bytes(KP);
             int rc = 0;
-            switch (NT) {
-                case 1: rc = allow_dyn_lds(apply_shared_mfma_kernel<1>, need, "shared-Gram product"); break;
-                case 2: rc = allow_dyn_lds(apply_shared_mfma_kernel<2>, need, "shared-Gram product"); break;
-                case 3: rc = allow_dyn_lds(apply_shared_mfma_kernel<3>, need, "shared-Gram product"); break;
-                default: rc = allow_dyn_lds(apply_shared_mfma_kernel<4>, need, "shared-Gram product"); break;
-            }
+            if (!with_nt(NT, [&](auto N) { rc = allow_dyn_lds(apply_shared_mfma_kernel<decltype(N)::value>, need, "shared-Gram product"); })) return unsupported_rank();
             if (rc) return kFail;
         }
         tile_TI = 0; nbt = 1; persist_state = 0; persist_shard_state = 0; persist_failed = false; persist_note.clear(); snap_iter = -1;
@@ -388,12 +382,7 @@ struct TrmfSessionImpl : SessionXPhase {
             part_stride = (uint32_t)KP;
             return part_slab.alloc((size_t)items * part_stride, false);
         }
-        switch (NT) {
-            case 1: part_stride = split_part_reals<1>(true); break;
-            case 2: part_stride = split_part_reals<2>(true); break;
-            case 3: part_stride = split_part_reals<3>(true); break;
-            default: part_stride = split_part_reals<4>(true); break;
-        }
+        if (!with_nt(NT, [&](auto N) { part_stride = split_part_reals<decltype(N)::value>(true); })) return unsupported_rank();
         return part_slab.alloc((size_t)items * part_stride, false);
     }
     int set_series_transform(const real *a, const real *b) {
@@ -926,13 +915,8 @@ struct TrmfSessionImpl : SessionXPhase {
             FillStreamScope fill(stream);
             if (pred && ho_pred.alloc(ho_m, false)) return kFail;
             HeldoutArgs a{ho_row.p, ho_col.p, ho_val.p, W.p, H.p, pred ? ho_pred.p : nullptr, ho_part.p, ho_m, ho_chunk, KP, NT};
-            switch (generic ? 0 : NT) {
-                case 1: hipLaunchKernelGGL(heldout_eval_kernel<1>, dim3(ho_nb), dim3(256), 0, stream, a); break;
-                case 2: hipLaunchKernelGGL(heldout_eval_kernel<2>, dim3(ho_nb), dim3(256), 0, stream, a); break;
-                case 3: hipLaunchKernelGGL(heldout_eval_kernel<3>, dim3(ho_nb), dim3(256), 0, stream, a); break;
-                case 4: hipLaunchKernelGGL(heldout_eval_kernel<4>, dim3(ho_nb), dim3(256), 0, stream, a); break;
-                default: hipLaunchKernelGGL(heldout_eval_kernel<0>, dim3(ho_nb), dim3(256), 0, stream, a); break;
-            }
+            if (!with_nt0(generic ? 0 : NT, [&](auto N) { hipLaunchKernelGGL(heldout_eval_kernel<decltype(N)::value>, dim3(ho_nb), dim3(256), 0, stream, a); }))
+                return unsupported_rank();
             hipLaunchKernelGGL(heldout_reduce_kernel, dim3(1), dim3(256), 0, stream, ho_part.p, ho_nb, ho_sums.p);
             TRMF_HIP_CHECK(hipGetLastError());
             TRMF_HIP_CHECK(hipMemcpyAsync(h, ho_sums.p, sizeof h, hipMemcpyDeviceToHost, stream));
@@ -984,13 +968,8 @@ struct TrmfSessionImpl : SessionXPhase {
                         score ? fc_table[in].p : nullptr, score ? fc_table[out].p : nullptr, score ? fc_prev[in].p : nullptr, score ? fc_prev[out].p : nullptr,
                         (real)threshold, clip ? 1 : 0, fc_rows > 0 ? 1 : 0, n, steps, KP, NT, forecast_rows_per_pass(KP, generic)};
             const dim3 grid((n + 255) / 256);
-            switch (generic ? 0 : NT) {
-                case 1: hipLaunchKernelGGL(forecast_score_kernel<1>, grid, dim3(256), 0, stream, a); break;
-                case 2: hipLaunchKernelGGL(forecast_score_kernel<2>, grid, dim3(256), 0, stream, a); break;
-                case 3: hipLaunchKernelGGL(forecast_score_kernel<3>, grid, dim3(256), 0, stream, a); break;
-                case 4: hipLaunchKernelGGL(forecast_score_kernel<4>, grid, dim3(256), 0, stream, a); break;
-                default: hipLaunchKernelGGL(forecast_score_kernel<0>, grid, dim3(256), 0, stream, a); break;
-            }
+            if (!with_nt0(generic ? 0 : NT, [&](auto N) { hipLaunchKernelGGL(forecast_score_kernel<decltype(N)::value>, grid, dim3(256), 0, stream, a); }))
+                return unsupported_rank();
             TRMF_HIP_CHECK(hipGetLastError());
         }
         // the outputs come back through host staging (pinned memory of the library when they fit) and are copied out together

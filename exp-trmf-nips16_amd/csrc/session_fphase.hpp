@@ -52,23 +52,8 @@ struct SessionFPhase : SessionTransport {
         }
         if (longF.any()) { uint32_t lo, hi; longF.range(rb, re, lo, hi); if (hi - lo == rows) return 0; }     // every row of the range is split: nothing left for the row kernel
         const dim3 grid((rows + 15) / 16), block(256);
-#define TRMF_LAUNCH_QUAD(ABL)                                                                          \
-        hipLaunchKernelGGL((fsolve_quad_kernel<NT_, KMAX_, ABL>), grid, block, 0, stream, Yc_ptr.p,    \
-                           Yc_idx.p, Yc_val.p, W.p, H.p, rb, re, k, (real)lambdaI, (uint32_t)T, longF.thresh - 1u)
-#if defined(TRMF_ABLATION)
-        if (NT_ == 3 && KMAX_ == 40 && dbg_flags) {
-            switch (dbg_flags) {
-                case 1: TRMF_LAUNCH_QUAD(1); break;
-                case 2: TRMF_LAUNCH_QUAD(2); break;
-                case 4: TRMF_LAUNCH_QUAD(4); break;
-                case 6: TRMF_LAUNCH_QUAD(6); break;
-                default: TRMF_LAUNCH_QUAD(7); break;
-            }
-            return 0;
-        }
-#endif
-        TRMF_LAUNCH_QUAD(0);
-#undef TRMF_LAUNCH_QUAD
+        hipLaunchKernelGGL((fsolve_quad_kernel<NT_, KMAX_>), grid, block, 0, stream, Yc_ptr.p,
+                           Yc_idx.p, Yc_val.p, W.p, H.p, rb, re, k, (real)lambdaI, (uint32_t)T, longF.thresh - 1u);
 #endif
         return 0;
     }
@@ -79,22 +64,11 @@ struct SessionFPhase : SessionTransport {
                                    Yc_ptr.p, Yc_idx.p, Yc_val.p, W.p, rb, re, k, KP, NT, (real)lambdaI, gen_scratch.p, (size_t)0, H.p);
             return 0;
         }
-#define TRMF_FSOLVE_SWITCH(FN)                                                       \
-        switch (KMAX) {                                                              \
-            case 8:  FN<1, 8>(rb, re); break;                                        \
-            case 16: FN<1, 16>(rb, re); break;                                       \
-            case 24: FN<2, 24>(rb, re); break;                                       \
-            case 32: FN<2, 32>(rb, re); break;                                       \
-            case 40: FN<3, 40>(rb, re); break;                                       \
-            case 48: FN<3, 48>(rb, re); break;                                       \
-            case 56: FN<4, 56>(rb, re); break;                                       \
-            case 64: FN<4, 64>(rb, re); break;                                       \
-            default: set_error("unsupported rank"); return kFail;                    \
-        }
-        if (sizeof(real) == 4) { TRMF_FSOLVE_SWITCH(launch_fsolve_quad) }
-        else { TRMF_FSOLVE_SWITCH(launch_fsolve_mfma) }
-#undef TRMF_FSOLVE_SWITCH
-        return 0;
+        return with_kq(KMAX, [&](auto KM) {
+            constexpr int KMAX_ = decltype(KM)::value, NT_ = (KMAX_ + kTile - 1) / kTile;
+            if (sizeof(real) == 4) launch_fsolve_quad<NT_, KMAX_>(rb, re);
+            else launch_fsolve_mfma<NT_, KMAX_>(rb, re);
+        }) ? 0 : unsupported_rank();
     }
     // The chunk count must be the SAME on every rank (each chunk is one collective): it is derived from the LARGEST block of
     // the partition, a number every rank computes from the same bounds -- not from the rank's own row count, which differs
@@ -225,27 +199,14 @@ struct SessionFPhase : SessionTransport {
             const uint32_t *ptr = transposed ? Yc_ptr.p : Yr_ptr.p, *idx = transposed ? Yc_idx.p : Yr_idx.p;
             const real *val = transposed ? Yc_val.p : Yr_val.p;
             const uint32_t zr = (uint32_t)(transposed ? T : n);
-            switch (NT) {
-                case 1: launch_spmm<1>(transposed ? longF : longX, ptr, idx, val, X, out, rb, re, zr); break;
-                case 2: launch_spmm<2>(transposed ? longF : longX, ptr, idx, val, X, out, rb, re, zr); break;
-                case 3: launch_spmm<3>(transposed ? longF : longX, ptr, idx, val, X, out, rb, re, zr); break;
-                default: launch_spmm<4>(transposed ? longF : longX, ptr, idx, val, X, out, rb, re, zr); break;
-            }
+            if (!with_nt(NT, [&](auto N) { launch_spmm<decltype(N)::value>(transposed ? longF : longX, ptr, idx, val, X, out, rb, re, zr); })) return unsupported_rank();
         } else {
             const real *A = transposed ? Yd_tn.p : Yd_nt.p;     // K x M row-major with K the contracted dim
             const int K = transposed ? T : n, M = transposed ? n : T;
-            switch (NT) {
-                case 1: launch_dense_tn<1>(A, K, M, X, out); break;
-                case 2: launch_dense_tn<2>(A, K, M, X, out); break;
-                case 3: launch_dense_tn<3>(A, K, M, X, out); break;
-                default: launch_dense_tn<4>(A, K, M, X, out); break;
-            }
+            if (!with_nt(NT, [&](auto N) { launch_dense_tn<decltype(N)::value>(A, K, M, X, out); })) return unsupported_rank();
         }
         TRMF_HIP_CHECK(hipGetLastError());
         return 0;
-    }
-    template <int NT_> void launch_small_gram(const real *A, int rows, int nb, hipStream_t stream) {
-        hipLaunchKernelGGL((small_gram_mfma_kernel<NT_>), dim3(nb), dim3(256), 0, stream, A, rows, k, sgram_part.p);
     }
     int small_gram(const real *A, int rows, real lambda, real *GS, hipStream_t stream) {
         if (generic) {
@@ -254,12 +215,9 @@ struct SessionFPhase : SessionTransport {
         }
         // one partial per wavefront (4 per workgroup), at least 64 rows each, kSmallGramBlocks slots in all
         const int nb = std::max(1, std::min(kSmallGramBlocks / 4, rows / 256));
-        switch (NT) {
-            case 1: launch_small_gram<1>(A, rows, nb, stream); break;
-            case 2: launch_small_gram<2>(A, rows, nb, stream); break;
-            case 3: launch_small_gram<3>(A, rows, nb, stream); break;
-            default: launch_small_gram<4>(A, rows, nb, stream); break;
-        }
+        if (!with_nt(NT, [&](auto N) {
+                hipLaunchKernelGGL((small_gram_mfma_kernel<decltype(N)::value>), dim3(nb), dim3(256), 0, stream, A, rows, k, sgram_part.p);
+            })) return unsupported_rank();
         hipLaunchKernelGGL(small_gram_reduce_kernel, dim3((k * k + 3) / 4), dim3(256), 0, stream, sgram_part.p, nb * 4, k, lambda, GS);
         return 0;
     }
@@ -270,7 +228,7 @@ struct SessionFPhase : SessionTransport {
         // not faster: the fork / join events cost more than the ~60 us chain they would hide; profiles/r05_streams.txt)
         hipStream_t gs = stream;
         if (y_times_factor(true, W.p, Bf.p, dense ? 0u : rb, dense ? (uint32_t)n : re)) return kFail;   // Y^T W
-        small_gram(W.p, T, (real)lambdaI, GSf.p, gs);                                                   // W^T W + lambda I
+        if (small_gram(W.p, T, (real)lambdaI, GSf.p, gs)) return kFail;                                 // W^T W + lambda I
         if (re > rb && generic) {
             hipLaunchKernelGGL(chol_generic_kernel, dim3(1), dim3(256), 0, stream, GSf.p, Uf.p, k);
             const int nrows = (int)(re - rb);
@@ -278,13 +236,7 @@ struct SessionFPhase : SessionTransport {
                                H.p + (size_t)rb * KP, nrows, k, KP, NT);
         } else if (re > rb) {
             const size_t ulds = (size_t)k * k * sizeof(real);          // <= 32 KB
-            if (test_env("TRMF_CHOL_WORKGROUP")) hipLaunchKernelGGL(chol_shared_kernel, dim3(1), dim3(256), ulds, gs, GSf.p, Uf.p, k);
-            else switch (NT) {
-                case 1: hipLaunchKernelGGL(chol_wave_kernel<1>, dim3(1), dim3(64), 0, gs, GSf.p, Uf.p, k); break;
-                case 2: hipLaunchKernelGGL(chol_wave_kernel<2>, dim3(1), dim3(64), 0, gs, GSf.p, Uf.p, k); break;
-                case 3: hipLaunchKernelGGL(chol_wave_kernel<3>, dim3(1), dim3(64), 0, gs, GSf.p, Uf.p, k); break;
-                default: hipLaunchKernelGGL(chol_wave_kernel<4>, dim3(1), dim3(64), 0, gs, GSf.p, Uf.p, k); break;
-            }
+            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(chol_wave_kernel<decltype(N)::value>, dim3(1), dim3(64), 0, gs, GSf.p, Uf.p, k); })) return unsupported_rank();
             const int nrows = (int)(re - rb), nblk = std::max(1, std::min(2048, (nrows + 3) / 4));
             hipLaunchKernelGGL(solve_rows_kernel, dim3(nblk), dim3(256), ulds, stream, Uf.p, Bf.p + (size_t)rb * KP,
                                H.p + (size_t)rb * KP, nrows, k, KP, NT);

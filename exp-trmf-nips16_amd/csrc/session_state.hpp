@@ -21,6 +21,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/trmf_abi.h"
@@ -34,6 +35,16 @@
 namespace trmf {
 
 std::shared_ptr<Comm> active_comm();   // trmf_abi.hip
+
+// ---- host-side dispatch on a rank bucket: run-time value -> template argument ------------------------------------------------
+// f(std::integral_constant<int, V>{}) for the V of the list that equals v.  Exact match only: returns false when none does, and
+// the caller reports that (SessionState::unsupported_rank) instead of running some other instantiation.
+template <int... Vs, class F> bool dispatch_int(int v, F &&f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+template <class F> bool with_nt(int nt, F &&f) { return dispatch_int<1, 2, 3, 4>(nt, f); }                        // column tiles of a rank <= 64
+template <class F> bool with_nt0(int nt, F &&f) { return dispatch_int<0, 1, 2, 3, 4>(nt, f); }                    // ... or 0: the generic ranks' bucket
+template <class F> bool with_kq(int kq, F &&f) { return dispatch_int<8, 16, 24, 32, 40, 48, 56, 64>(kq, f); }     // rank rounded up to 8 (KMAX, hv_kq)
 
 struct SessionState {
     // problem
@@ -116,9 +127,10 @@ struct SessionState {
     int ar_TI = 64, nbar = 1;                 // unfused path: timestamps per ar_tile_kernel workgroup, its partial-sum slots
     DevBuf<real> arbase;                      // lambdaI*v + lambdaAR*AR'(v) between ar_tile_kernel and apply_kernel
     XParams xp{};
-    // Knobs that exist for the tests and the measurement scripts (forced failures, forced forms, ablations) are read only when
+    // Knobs that exist for the tests and the measurement scripts (forced failures, forced forms) are read only when
     // TRMF_TEST is set; INTEGRATION.md lists the production knobs.
     static bool test_knobs() { static const bool on = getenv("TRMF_TEST") != nullptr; return on; }
+    static int unsupported_rank() { set_error("unsupported rank"); return kFail; }      // a dispatch_int() miss
     static const char *test_env(const char *name) {
         if (test_knobs()) return getenv(name);
         // a gated knob that is set but ignored says so, once per variable (a measurement script kept setting TRMF_FSHARD
@@ -216,7 +228,6 @@ struct SessionState {
     int gramx_mode = kGramxMeasure, gramx_calls = 0;
     hipEvent_t gx0 = nullptr, gx1 = nullptr, gx2 = nullptr;
     DevBuf<double> gramx_times;
-    int dbg_flags = 0;           // TRMF_DEBUG_ABLATE: bit0 skip Gram, bit1 skip factorisation, bit2 skip back-solve
     // Sharding a phase over the ranks pays only when the all-gather of its result costs less than the rows a rank no
     // longer computes (true for the F-solve at config 3 on 4 and 8 GPUs, not on 2).  Measure-once rule, shared by the
     // F-solve and the X-side Gram build: the first two calls run sharded, the second is timed on every rank (kernel, gather); the

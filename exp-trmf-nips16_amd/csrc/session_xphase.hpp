@@ -67,7 +67,7 @@ struct SessionXPhase : SessionFPhase {
         // the persistent kernel across ranks: measured in the set-up iterations only (a trial that times out -- workgroups of several
         // ranks that share ONE device and do not fit together -- costs the iteration it ran in, which autotune() undoes)
         const char *at = getenv("TRMF_AUTOTUNE");
-        if (fused_ts && p2p.on && !(at && atoi(at) == 0) && !test_env("TRMF_NO_PERSIST_SHARD") && persist_usable_shard()) {
+        if (fused_ts && p2p.on && !(at && atoi(at) == 0) && persist_usable_shard()) {
             if (max_ranks_per_device == 1) x_cands.push_back(kXTsPersist);
             else persist_note = std::to_string(max_ranks_per_device) + " ranks share one device: the persistent-kernel form is not tried";
         }
@@ -89,45 +89,34 @@ struct SessionXPhase : SessionFPhase {
         const dim3 lgrid((hi - lo + 3) / 4);
         // longest rows first (LongRows::d_order) when the launch covers every timestamp; a rank's block runs in index order
         const uint32_t *xorder = (longX.skewed && longX.d_order.p && rb == 0 && re == (uint32_t)T) ? longX.d_order.p : nullptr;
-#define TRMF_LAUNCH_GRAM_X(PAD, PACKED)                                                                                      \
-    do {                                                                                                                     \
-        if (hi > lo) {                                                                                                       \
-            launch_gram_part<NT_, PAD>(longX, lo, hi, Yr_idx.p, Yr_val.p, H.p, (uint32_t)n);                                 \
-            hipLaunchKernelGGL((gram_x_long_kernel<NT_, PAD, PACKED>), lgrid, lblock, 0, stream, split_view(longX, lo, hi), G.p, Bv.p, k, xp.gstride); \
-        }                                                                                                                    \
-        hipLaunchKernelGGL((gram_x_kernel<NT_, PAD, PACKED>), grid, block, 0, stream, Yr_ptr.p, Yr_idx.p, Yr_val.p, H.p, G.p, Bv.p, \
-                           rb, re, k, (uint32_t)n, xp.gstride, longX.thresh, xorder);                                        \
-    } while (0)
+        auto launch = [&](auto Pad, auto Packed) {
+            constexpr bool PAD = decltype(Pad)::value, PACKED = decltype(Packed)::value;
+            if (hi > lo) {
+                launch_gram_part<NT_, PAD>(longX, lo, hi, Yr_idx.p, Yr_val.p, H.p, (uint32_t)n);
+                hipLaunchKernelGGL((gram_x_long_kernel<NT_, PAD, PACKED>), lgrid, lblock, 0, stream, split_view(longX, lo, hi), G.p, Bv.p, k, xp.gstride);
+            }
+            hipLaunchKernelGGL((gram_x_kernel<NT_, PAD, PACKED>), grid, block, 0, stream, Yr_ptr.p, Yr_idx.p, Yr_val.p, H.p, G.p, Bv.p,
+                               rb, re, k, (uint32_t)n, xp.gstride, longX.thresh, xorder);
+        };
         if (rhs_pad_ok<NT_>(k)) {     // rhs accumulated by the MFMAs in the panel's pad columns
-            if (gpacked) TRMF_LAUNCH_GRAM_X(true, true); else TRMF_LAUNCH_GRAM_X(true, false);
+            if (gpacked) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{});
         } else {
-            if (gpacked) TRMF_LAUNCH_GRAM_X(false, true); else TRMF_LAUNCH_GRAM_X(false, false);
+            if (gpacked) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{});
         }
-#undef TRMF_LAUNCH_GRAM_X
     }
-    void launch_gram_x_rows(uint32_t rb, uint32_t re) {
+    int launch_gram_x_rows(uint32_t rb, uint32_t re) {
         if (generic) {
             if (re > rb)
                 hipLaunchKernelGGL(gram_generic_kernel<false>, dim3(std::min<uint32_t>(4096, re - rb)), dim3(256), gram_generic_lds(k), stream,
                                    Yr_ptr.p, Yr_idx.p, Yr_val.p, H.p, rb, re, k, KP, NT, real(0), G.p, xp.gstride, Bv.p);
-            return;
+            return 0;
         }
-        switch (NT) {
-            case 1: launch_gram_x<1>(rb, re); break;
-            case 2: launch_gram_x<2>(rb, re); break;
-            case 3: launch_gram_x<3>(rb, re); break;
-            default: launch_gram_x<4>(rb, re); break;
-        }
-    }
-    template <int NT_> void launch_loss(const real *Wv, uint32_t rb, uint32_t re) {
-        if (re > rb)
-            hipLaunchKernelGGL((loss_kernel<NT_>), dim3(re - rb), dim3(256), 0, stream, Yr_ptr.p, Yr_idx.p,
-                               Yr_val.p, H.p, Wv, lossrow.p, rb, re, (uint32_t)n);
+        return with_nt(NT, [&](auto N) { launch_gram_x<decltype(N)::value>(rb, re); }) ? 0 : unsupported_rank();
     }
     int gram_x(bool timeshard = false) {
         if (timeshard || uts) {     // time-sharded CG: a rank only ever reads the Grams / right-hand sides of its own timestamps
             const uint32_t rb = (uint32_t)(uts ? ush.row_b : tsh_rank.row_b), re = (uint32_t)(uts ? ush.row_e : tsh_rank.row_e);
-            launch_gram_x_rows(rb, re);
+            if (launch_gram_x_rows(rb, re)) return kFail;
             TRMF_HIP_CHECK(hipGetLastError());
             return 0;
         }
@@ -137,7 +126,7 @@ struct SessionXPhase : SessionFPhase {
         const uint32_t rb = replicate ? 0u : (uint32_t)xbounds[comm->rank];
         const uint32_t re = replicate ? (uint32_t)T : (uint32_t)xbounds[comm->rank + 1];
         if (measure) TRMF_HIP_CHECK(hipEventRecord(gx0, stream));
-        launch_gram_x_rows(rb, re);
+        if (launch_gram_x_rows(rb, re)) return kFail;
         TRMF_HIP_CHECK(hipGetLastError());
         gramx_calls++;
         if (replicate) return 0;                                    // every rank built every row: nothing to gather
@@ -161,13 +150,11 @@ struct SessionXPhase : SessionFPhase {
         const uint32_t re = all_rows ? (uint32_t)T : (uint32_t)xbounds[comm->rank + 1];
         if (generic) {
             if (re > rb) hipLaunchKernelGGL(loss_generic_kernel, dim3(re - rb), dim3(256), 0, stream, Yr_ptr.p, Yr_idx.p, Yr_val.p, H.p, Wv, lossrow.p, rb, re, KP);
-        } else
-        switch (NT) {
-            case 1: launch_loss<1>(Wv, rb, re); break;
-            case 2: launch_loss<2>(Wv, rb, re); break;
-            case 3: launch_loss<3>(Wv, rb, re); break;
-            default: launch_loss<4>(Wv, rb, re); break;
-        }
+        } else if (!with_nt(NT, [&](auto N) {
+                       if (re > rb)
+                           hipLaunchKernelGGL((loss_kernel<decltype(N)::value>), dim3(re - rb), dim3(256), 0, stream, Yr_ptr.p, Yr_idx.p,
+                                              Yr_val.p, H.p, Wv, lossrow.p, rb, re, (uint32_t)n);
+                   })) return unsupported_rank();
         TRMF_HIP_CHECK(hipGetLastError());
         return all_rows ? 0 : gather_rows(lossrow.p, xbounds, sizeof(double));
     }
@@ -175,40 +162,29 @@ struct SessionXPhase : SessionFPhase {
         const uint32_t rb = (uint32_t)xbounds[comm->rank], re = (uint32_t)xbounds[comm->rank + 1];
         if (y_times_factor(false, H.p, Bv.p, dense ? 0u : rb, dense ? (uint32_t)T : re)) return kFail;  // Y H
         if (!dense && gather_rows(Bv.p, xbounds, (size_t)KP * sizeof(real))) return kFail;
-        small_gram(H.p, n, real(0), GSx.p, stream);                                                     // H^T H
-        return 0;
+        return small_gram(H.p, n, real(0), GSx.p, stream);                                              // H^T H
     }
 
     // ---- X-solve (trmf.cpp:665-674 -> rf_tron.h:134-254) -----------------------------------------------
     // Fused path (the AR halo fits LDS): hv_tile_kernel in its four roles, one launch per CG iteration.
-    template <int MODE, bool SHARD> void launch_hv_tile_as(const HvVecs &a, int it, int last, const double *rec_in, double *rec_out) {
+    template <int MODE, bool SHARD> int launch_hv_tile_as(const HvVecs &a, int it, int last, const double *rec_in, double *rec_out) {
         const size_t lds = hv_tile_lds_bytes(tile_TI, midx, KP, nlag, k);
         const TileShard &sh = SHARD ? tsh_rank : tsh;
         const PeerTable *pt = (SHARD && p2p_use) ? peer_table.p : nullptr;
         const int mi = rec_out == xm[0] ? 0 : rec_out == xm[1] ? 1 : 2;
         // (wide tiles -- 512 threads, one rank only: session.hpp, choose_tile() -- have their own instantiations, unit_hv_wide.hip)
-#define TRMF_LAUNCH_HV_KQ(KQ)                                                                                        \
-        if (!SHARD && tile_nth == 512)                                                                               \
-            hipLaunchKernelGGL((hv_tile_kernel<MODE, KQ, false, 512>), dim3(sh.ntiles), dim3(512), lds, stream, xp, xstate.p, a, sh, it, last,  \
-                               lag_set.p, theta.p, Gmat(), rec_in, rec_out, pt, mi, tile_TI);                         \
-        else                                                                                                         \
-            hipLaunchKernelGGL((hv_tile_kernel<MODE, KQ, SHARD>), dim3(sh.ntiles), dim3(256), lds, stream, xp, xstate.p, a, sh, it, last,  \
-                               lag_set.p, theta.p, Gmat(), rec_in, rec_out, pt, mi, tile_TI)
-        switch (hv_kq(k) / 8) {
-            case 1: TRMF_LAUNCH_HV_KQ(8); break;
-            case 2: TRMF_LAUNCH_HV_KQ(16); break;
-            case 3: TRMF_LAUNCH_HV_KQ(24); break;
-            case 4: TRMF_LAUNCH_HV_KQ(32); break;
-            case 5: TRMF_LAUNCH_HV_KQ(40); break;
-            case 6: TRMF_LAUNCH_HV_KQ(48); break;
-            case 7: TRMF_LAUNCH_HV_KQ(56); break;
-            default: TRMF_LAUNCH_HV_KQ(64); break;
-        }
-#undef TRMF_LAUNCH_HV_KQ
+        return with_kq(hv_kq(k), [&](auto Kq) {
+            constexpr int KQ = decltype(Kq)::value;
+            if (!SHARD && tile_nth == 512)
+                hipLaunchKernelGGL((hv_tile_kernel<MODE, KQ, false, 512>), dim3(sh.ntiles), dim3(512), lds, stream, xp, xstate.p, a, sh, it, last,
+                                   lag_set.p, theta.p, Gmat(), rec_in, rec_out, pt, mi, tile_TI);
+            else
+                hipLaunchKernelGGL((hv_tile_kernel<MODE, KQ, SHARD>), dim3(sh.ntiles), dim3(256), lds, stream, xp, xstate.p, a, sh, it, last,
+                                   lag_set.p, theta.p, Gmat(), rec_in, rec_out, pt, mi, tile_TI);
+        }) ? 0 : unsupported_rank();
     }
-    template <int MODE> void launch_hv_tile(bool shard, const HvVecs &a, int it, int last, const double *rec_in, double *rec_out) {
-        if (shard) launch_hv_tile_as<MODE, true>(a, it, last, rec_in, rec_out);
-        else launch_hv_tile_as<MODE, false>(a, it, last, rec_in, rec_out);
+    template <int MODE> int launch_hv_tile(bool shard, const HvVecs &a, int it, int last, const double *rec_in, double *rec_out) {
+        return shard ? launch_hv_tile_as<MODE, true>(a, it, last, rec_in, rec_out) : launch_hv_tile_as<MODE, false>(a, it, last, rec_in, rec_out);
     }
     // The fused X-solve: gradient launch, CG launches (one per iteration, the closing one also forms w_new and the sums
     // of the acceptance test), plain launch H s, accept.  shard: every launch runs this rank's tiles only and is
@@ -221,11 +197,11 @@ struct SessionXPhase : SessionFPhase {
         double *mg = xm[2], *mc[2] = {xm[0], xm[1]};
         HvVecs a{};
         a.v = W.p; a.out = g.p; a.Bv = Bv.p;
-        launch_hv_tile<HV_GRAD>(shard, a, 0, 0, nullptr, mg);                  // gradient, <g,g>, AR/ridge sums
+        if (launch_hv_tile<HV_GRAD>(shard, a, 0, 0, nullptr, mg)) return kFail; // gradient, <g,g>, AR/ridge sums
         if (shard && exchange(2, -1, 1, g.p, nullptr, nullptr)) return kFail;
         a = HvVecs{};
         a.v = g.p; a.s = s.p; a.d_out = dbuf[0]; a.r_out = rbuf[0]; a.out = hbuf[0];
-        launch_hv_tile<HV_CG_FIRST>(shard, a, 0, 0, mg, mc[0]);                // f, |g|, cgtol; s = 0, r = d = -g; H d
+        if (launch_hv_tile<HV_CG_FIRST>(shard, a, 0, 0, mg, mc[0])) return kFail; // f, |g|, cgtol; s = 0, r = d = -g; H d
         if (shard && exchange(0, 0, 3, dbuf[0], rbuf[0], hbuf[0])) return kFail;
         // host-followed progress only where an exchange costs a collective; peer to peer (and on one rank) the launches of
         // iterations that will not run are no-ops on the device and everything is enqueued at once
@@ -234,7 +210,7 @@ struct SessionXPhase : SessionFPhase {
         for (int it = 1; it <= maxcg; it++) {                              // launch `maxcg` only closes the last iteration
             a.v = dbuf[(it - 1) & 1]; a.r_in = rbuf[(it - 1) & 1]; a.hd_in = hbuf[(it - 1) & 1];
             a.d_out = dbuf[it & 1]; a.r_out = rbuf[it & 1]; a.out = hbuf[it & 1];
-            launch_hv_tile<HV_CG_STEP>(shard, a, it, it == maxcg ? 1 : 0, mc[(it - 1) & 1], mc[it & 1]);
+            if (launch_hv_tile<HV_CG_STEP>(shard, a, it, it == maxcg ? 1 : 0, mc[(it - 1) & 1], mc[it & 1])) return kFail;
             if (!shard) continue;
             if (exchange(it & 1, it, 3, dbuf[it & 1], rbuf[it & 1], hbuf[it & 1])) return kFail;
             if (!follow) continue;
@@ -263,7 +239,7 @@ struct SessionXPhase : SessionFPhase {
         if (cg_direct) {                                                           // diagnostics: s^T H s by one more operator pass (session_state.hpp)
             a = HvVecs{};
             a.v = s.p; a.out = hbuf[0];
-            launch_hv_tile<HV_PLAIN>(shard, a, 0, 0, nullptr, mg);                 // H s, <s,Hs> (fields [0..2] of the same records)
+            if (launch_hv_tile<HV_PLAIN>(shard, a, 0, 0, nullptr, mg)) return kFail; // H s, <s,Hs> (fields [0..2] of the same records)
             if (shard && exchange(2, -1, 0, nullptr, nullptr, nullptr)) return kFail;
         }
         const int nb = (int)std::min<size_t>(kMaxPartials, ((size_t)(sh.row_e - sh.row_b) * KP + 255) / 256);
@@ -276,17 +252,6 @@ struct SessionXPhase : SessionFPhase {
         if (shard && gather_rows(W.p, tbounds, (size_t)KP * sizeof(real))) return kFail;   // the F-solve gathers rows of all of W
         return 0;
     }
-#define TRMF_PERSIST_SWITCH(CALL)                  \
-        switch (hv_kq(k) / 8) {                    \
-            case 1: CALL(8); break;                \
-            case 2: CALL(16); break;               \
-            case 3: CALL(24); break;               \
-            case 4: CALL(32); break;               \
-            case 5: CALL(40); break;               \
-            case 6: CALL(48); break;               \
-            case 7: CALL(56); break;               \
-            default: CALL(64); break;              \
-        }
     bool persist_usable(int maxcg) {
         if (persist_state == 0) {
             persist_state = -1;
@@ -296,9 +261,10 @@ struct SessionXPhase : SessionFPhase {
             // between the ranks' kernels); never where ranks share a device (their workgroups would have to be co-resident)
             if ((comm->world == 1 || max_ranks_per_device == 1) && tile_TI > 0 && nbt <= kPersistMaxTiles && maxcg <= kCgHistCap && !(e && atoi(e) == 0)) {
                 int slots = 0;
-#define TRMF_PERSIST_PREP(KQV) slots = tile_nth == 512 ? persist_prepare<KQV, false, 512>(lds) : persist_prepare<KQV>(lds)
-                TRMF_PERSIST_SWITCH(TRMF_PERSIST_PREP)
-#undef TRMF_PERSIST_PREP
+                with_kq(hv_kq(k), [&](auto Kq) {         // (no match: no slots, and the launch-per-step path reports the rank)
+                    constexpr int KQ = decltype(Kq)::value;
+                    slots = tile_nth == 512 ? persist_prepare<KQ, false, 512>(lds) : persist_prepare<KQ>(lds);
+                });
                 if (slots >= nbt && ll_rec.alloc((size_t)2 * nbt * kLLWords) == 0 &&
                     ll_vec.alloc((size_t)2 * T * KP * (2 * sizeof(real) / sizeof(unsigned long long))) == 0) persist_state = 1;
             }
@@ -312,9 +278,7 @@ struct SessionXPhase : SessionFPhase {
             if (p2p.on && p2p.ext_bytes > 0 && tile_TI > 0 && ts_possible && nbt <= kPersistMaxTiles && maxcg <= kCgHistCap && !full) {
                 const size_t lds = persist_lds_bytes(tile_TI, midx, KP, nlag, k, nbt);
                 int slots = 0;
-#define TRMF_PERSIST_PREP_S(KQV) slots = persist_prepare<KQV, true>(lds)
-                TRMF_PERSIST_SWITCH(TRMF_PERSIST_PREP_S)
-#undef TRMF_PERSIST_PREP_S
+                with_kq(hv_kq(k), [&](auto Kq) { slots = persist_prepare<decltype(Kq)::value, true>(lds); });
                 // against the LARGEST block of the partition (the last rank may own fewer tiles): every rank must reach the same
                 // answer, or the ranks' candidate lists -- and with them the collectives of decide_x_form() -- differ
                 if (slots >= tsh_rank.tpr) persist_shard_state = 1;
@@ -370,9 +334,12 @@ struct SessionXPhase : SessionFPhase {
             hipLaunchKernelGGL(persist_peer_emulator_kernel, dim3(1), dim3(256), 0, side, ea);
             TRMF_HIP_CHECK(hipGetLastError());
         }
-#define TRMF_PERSIST_GO(KQV) if (shard ? persist_launch<KQV, true>(pa, lds) : tile_nth == 512 ? persist_launch<KQV, false, 512>(pa, lds) : persist_launch<KQV, false>(pa, lds)) return kFail
-        TRMF_PERSIST_SWITCH(TRMF_PERSIST_GO)
-#undef TRMF_PERSIST_GO
+        int rc = 0;
+        if (!with_kq(hv_kq(k), [&](auto Kq) {
+                constexpr int KQ = decltype(Kq)::value;
+                rc = shard ? persist_launch<KQ, true>(pa, lds) : tile_nth == 512 ? persist_launch<KQ, false, 512>(pa, lds) : persist_launch<KQ, false>(pa, lds);
+            })) return unsupported_rank();
+        if (rc) return kFail;
         if (emu_done) {
             hipLaunchKernelGGL(store_u64_kernel, dim3(1), dim3(1), 0, stream, emu_done, (unsigned long long)pa.epoch0);   // ends the emulator
             TRMF_HIP_CHECK(hipEventRecord(emu_end, side));
@@ -383,7 +350,6 @@ struct SessionXPhase : SessionFPhase {
         if (shard && gather_rows(W.p, tbounds, (size_t)KP * sizeof(real))) return kFail;
         return 0;
     }
-#undef TRMF_PERSIST_SWITCH
 
     // Which form of the X-solve?  Measured once, like the other shard decisions: each candidate of init_x_forms() runs two X
     // phases, the second timed; the times of every rank are exchanged and the slowest rank's time decides.  All forms of the
@@ -474,46 +440,34 @@ struct SessionXPhase : SessionFPhase {
         if (last) return 0;                                              // the closing launch has no product
         const real *operand = cg_it >= 1 ? av.d_out : av.v;
         const real *resid = cg_it >= 1 ? av.r_out : av.r_in;
-        // shared Gram, or the packed Grams of one row group, staged per workgroup
-        const size_t ap_lds = full ? (size_t)k * k * sizeof(real) : gpacked ? (size_t)apply_stages(k) * 512 * sizeof(real) : 0;
-        auto launch_apply = [&](int blocks, int row_b, int rows, int slot_b) {
+        // the packed Grams of one row group, staged per workgroup
+        const size_t ap_lds = gpacked ? (size_t)apply_stages(k) * 512 * sizeof(real) : 0;
+        auto launch_apply = [&](int blocks, int row_b, int rows, int slot_b) -> int {
             if (k > kApplyThreadPerColumn || (generic && full)) {   // very wide ranks (a workgroup per timestamp walks the columns); also the shared
                                                                     // Gram of the full-observation path above rank 64 (read from L2, not staged in LDS)
                 hipLaunchKernelGGL(apply_wide_kernel, dim3(blocks), dim3(256), (size_t)k * sizeof(real), stream, xp, st, cg_it, operand, resid, arbase.p,
                                    Gmat(), Bv.p, minus_b, out, dot_mode, P(P_DOT), row_b, rows, slot_b);
-                return;
+                return 0;
             }
-#define TRMF_LAUNCH_APPLY_PACKED(NS)                                                                                          \
-    hipLaunchKernelGGL((apply_kernel<true, NS>), dim3(blocks), dim3(256), ap_lds, stream, xp, st, cg_it, operand, resid, arbase.p, \
-                       Gmat(), Bv.p, minus_b, out, dot_mode, P(P_DOT), rpb, row_b, rows, slot_b)
-            if (gpacked) {
-                switch (apply_stages(k)) {
-                    case 5: TRMF_LAUNCH_APPLY_PACKED(5); break;
-                    case 10: TRMF_LAUNCH_APPLY_PACKED(10); break;
-                    default: TRMF_LAUNCH_APPLY_PACKED(17); break;
-                }
-            } else
-#undef TRMF_LAUNCH_APPLY_PACKED
-                hipLaunchKernelGGL(apply_kernel<false>, dim3(blocks), dim3(256), ap_lds, stream, xp, st, cg_it, operand, resid, arbase.p,
-                                   Gmat(), Bv.p, minus_b, out, dot_mode, P(P_DOT), rpb, row_b, rows, slot_b);
-        };
-        if (full && !generic && !test_env("TRMF_NO_APPLY_SHARED")) {       // one Gram for every timestamp: the product runs on the matrix pipe (never sharded)
-#define TRMF_LAUNCH_APPLY_SHARED(NTV)                                                                                           \
-    hipLaunchKernelGGL((apply_shared_mfma_kernel<NTV>), dim3(nba), dim3(256), apply_shared_lds_bytes(KP), stream, xp, st, cg_it,  \
-                       operand, resid, arbase.p, Gmat(), Bv.p, minus_b, out, dot_mode, P(P_DOT), 0, T, 0)
-            switch (NT) {
-                case 1: TRMF_LAUNCH_APPLY_SHARED(1); break;
-                case 2: TRMF_LAUNCH_APPLY_SHARED(2); break;
-                case 3: TRMF_LAUNCH_APPLY_SHARED(3); break;
-                default: TRMF_LAUNCH_APPLY_SHARED(4); break;
-            }
-#undef TRMF_LAUNCH_APPLY_SHARED
+            if (gpacked)
+                return dispatch_int<5, 10, 17>(apply_stages(k), [&](auto Ns) {
+                    hipLaunchKernelGGL((apply_kernel<true, decltype(Ns)::value>), dim3(blocks), dim3(256), ap_lds, stream, xp, st, cg_it, operand, resid, arbase.p,
+                                       Gmat(), Bv.p, minus_b, out, dot_mode, P(P_DOT), rpb, row_b, rows, slot_b);
+                }) ? 0 : unsupported_rank();
+            hipLaunchKernelGGL(apply_kernel<false>, dim3(blocks), dim3(256), ap_lds, stream, xp, st, cg_it, operand, resid, arbase.p,
+                               Gmat(), Bv.p, minus_b, out, dot_mode, P(P_DOT), rpb, row_b, rows, slot_b);
             return 0;
+        };
+        if (full && !generic) {       // one Gram for every timestamp: the product runs on the matrix pipe (never sharded)
+            return with_nt(NT, [&](auto N) {
+                hipLaunchKernelGGL((apply_shared_mfma_kernel<decltype(N)::value>), dim3(nba), dim3(256), apply_shared_lds_bytes(KP), stream, xp, st, cg_it,
+                                   operand, resid, arbase.p, Gmat(), Bv.p, minus_b, out, dot_mode, P(P_DOT), 0, T, 0);
+            }) ? 0 : unsupported_rank();
         }
         if (uts) {
             // this rank's timestamps only; then one grouped exchange: the edge rows the next kernel stages as halo and the
             // rank's slots of the partial sums
-            launch_apply(apply_slots, ush.row_b, ush.row_e - ush.row_b, comm->rank * apply_slots);
+            if (launch_apply(apply_slots, ush.row_b, ush.row_e - ush.row_b, comm->rank * apply_slots)) return kFail;
             TRMF_HIP_CHECK(hipGetLastError());
             const int c0 = P_CG0 + 3 * (cg_it & 1);
             if (cg_it >= 1) return uts_exchange(cg_it, 3, av.d_out, av.r_out, out, {{c0, 0}, {c0 + 1, 0}, {c0 + 2, 0}});
@@ -522,13 +476,12 @@ struct SessionXPhase : SessionFPhase {
             return uts_exchange(-1, 0, nullptr, nullptr, nullptr, {{P_DOT, 0}});                                              // H s
         }
         if (!cg_shard) {
-            launch_apply(nba, 0, T, 0);
-            return 0;
+            return launch_apply(nba, 0, T, 0);
         }
         // Gram product on this rank's timestamps only; its rows of `out` and its slots of the partial sums are
         // all-gathered (one grouped round), so every rank continues with identical vectors and scalars
         const int rb = (int)xbounds[comm->rank], re = (int)xbounds[comm->rank + 1];
-        launch_apply(apply_slots, rb, re - rb, comm->rank * apply_slots);
+        if (launch_apply(apply_slots, rb, re - rb, comm->rank * apply_slots)) return kFail;
         TRMF_HIP_CHECK(hipGetLastError());
         std::vector<uint64_t> poff(comm->world + 1);
         for (int r = 0; r <= comm->world; r++) poff[r] = (uint64_t)r * apply_slots * sizeof(double);

@@ -8,8 +8,8 @@
  * (exp-trmf-nips16_amd/trmf/corelib/trmf_float{32,64}.so) never links, loads or calls it.
  *
  * Parity status: PINNED against the real reference built by `make -C oracle ref`
- * (oracle/_ref/trmf_float{32,64}.so) by tests/test_oracle_vs_ref.py and by the committed golden
- * vectors under tests/golden/ (generated from oracle/_ref by tests/golden/make_golden.py).  The
+ * (oracle/_ref/trmf_float{32,64}.so) by tests/test_oracle_golden.py::test_port_matches_reference_build
+ * and by the committed golden vectors under tests/golden/ (generated from oracle/_ref by tests/golden/make_golden.py).  The
  * reference itself ships no tests or golden vectors.
  *
  * Built twice: -DORACLE_REAL=float -> libtrmf_oracle_f32.so, -DORACLE_REAL=double -> ..._f64.so.

@@ -1,7 +1,6 @@
 // The cached-Gram product of the unfused X-solve at config 5's shape (T = 50 000, k = 64, fp64): apply_kernel<false> on
-// full k x k Grams (1.64 GB per launch) against apply_kernel<true, 17> on packed upper triangles (0.83 GB), several grids,
-// and -- compiled with -DTRMF_APPLY_ABL=1|2 -- the packed kernel without its products / without its LDS copy.
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize [-DTRMF_APPLY_ABL=n] apply_packed.hip -o apply_packed
+// full k x k Grams (1.64 GB per launch) against apply_kernel<true, 17> on packed upper triangles (0.83 GB), several grids.
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize apply_packed.hip -o apply_packed
 #define TRMF_REAL double
 #include "../../exp-trmf-nips16_amd/csrc/cg_kernels.hpp"
 #include <cstdio>
@@ -38,10 +37,10 @@ int main(int argc, char **argv) {
             CK(hipEventRecord(b)); CK(hipEventSynchronize(b)); CK(hipEventElapsedTime(&ms, a, b));
         }
         const double bytes = (double)T * (pk ? packed : full) * 8;
-        printf("ABL=%d %-6s grid %5d : %7.1f us per launch, %.2f TB/s of Gram bytes\n", TRMF_APPLY_ABL, pk ? "packed" : "full", blocks, ms * 1e3 / 20,
+        printf("%-6s grid %5d : %7.1f us per launch, %.2f TB/s of Gram bytes\n", pk ? "packed" : "full", blocks, ms * 1e3 / 20,
                bytes / (ms / 20 * 1e-3) / 1e12);
     };
-    if (!TRMF_APPLY_ABL) run(false, 1024);
+    run(false, 1024);
     for (int blocks : {256, 512, 1024, 2048, 4096}) run(true, blocks);
     return 0;
 }

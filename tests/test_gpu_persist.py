@@ -36,12 +36,16 @@ def _run(p, m0, dtype, iters, missing, monkeypatch, persist, tile=None):
     dict(n=1500, T=700, k=64, nlag=6, density=0.05),         # the widest Gram slice (8-byte Gram loads in fp32)
     dict(n=400, T=300, k=8, nlag=0, density=0.1),            # no lags at all
     dict(n=600, T=260, k=24, nlag=5, density=0.08, lags=[0, 1, 2, 7, 24]),     # lag 0 is legal (trmf.py:354)
+    # the remaining rank buckets (rank rounded up to 8) of the host's dispatch: with the shapes above every one of 8 ... 64 runs fused
+    dict(n=400, T=300, k=32, nlag=3, density=0.1, must_fuse=True),
+    dict(n=400, T=300, k=48, nlag=3, density=0.1, must_fuse=True),
+    dict(n=400, T=300, k=56, nlag=3, density=0.1, must_fuse=True),
 ])
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])
 def test_persistent_kernel_bit_identical_to_launch_per_step(shape, dtype, monkeypatch):
     from trmf import synth
     c = dict(shape)
-    lags = c.pop('lags', None)
+    lags, must_fuse = c.pop('lags', None), c.pop('must_fuse', False)
     p = synth.sparse_problem(n=c['n'], T=c['T'], k=c['k'], nlag=c['nlag'], density=c['density'], dtype=np.float64, seed=5)
     if lags is not None:
         p['lag_set'] = np.array(lags, dtype=np.uint32)
@@ -49,6 +53,7 @@ def test_persistent_kernel_bit_identical_to_launch_per_step(shape, dtype, monkey
     iters = 4
     a, sa, da = _run(p, m0, dtype, iters, True, monkeypatch, persist=True)
     b, sb, db = _run(p, m0, dtype, iters, True, monkeypatch, persist=False)
+    assert not (must_fuse and 'unfused' in da), da
     if 'unfused' in da:
         pytest.skip('lag reach does not fit the fused tile: ' + da)
     assert 'persistent' in da and 'one launch per CG step' in db, (da, db)
