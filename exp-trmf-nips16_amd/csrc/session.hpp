@@ -606,7 +606,13 @@ struct TrmfSessionImpl : SessionXPhase {
                  longF.thresh, longX.rows.size(), longX.nitems, longX.thresh);
         return t;
     }
-    std::string describe() const { return describe_forms() + describe_split(); }
+    std::string describe_lag() const {
+        if (!lag_lasso()) return "; lag penalty: ridge";
+        char t[96];
+        snprintf(t, sizeof t, "; lag penalty: lasso l1=%g refit=%d", lambdaLagL1, lag_refit);
+        return t;
+    }
+    std::string describe() const { return describe_forms() + describe_split() + describe_lag(); }
     std::string describe_forms() const {
         char buf[640];
         if (comm->world <= 1) {
@@ -1018,6 +1024,36 @@ struct TrmfSessionImpl : SessionXPhase {
         if (sync()) return kFail;                 // (a recovery of a timed-out persistent kernel repeats iterations with the OLD weights)
         lambdaI = lI; lambdaAR = lAR; lambdaLag = lLag;
         xp.lambdaI = lI; xp.lambdaAR = lAR;
+        return 0;
+    }
+    // L1 weight of the lag weights and the refit on the selected support, for the Theta-solves enqueued from now on (the caller has
+    // validated l1).  (0, 0): the ridge path, exactly.
+    int set_lag_penalty(double l1, int refit) {
+        if (sync()) return kFail;
+        if ((l1 > 0 || refit) && ensure_lasso_buffers()) return kFail;
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));        // (the record table's zero fill)
+        lambdaLagL1 = l1; lag_refit = refit ? 1 : 0;
+        return 0;
+    }
+    // The Theta phase on its own, from the current W with the current penalties; blocking.  The iteration counter and the log stay.
+    int solve_lags() {
+        if (sync()) return kFail;
+        if (theta_solve(stream)) return kFail;
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new Theta
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    // Record of the last Theta-solve (the caller has synchronised the session): k x kLagRec, zeros after a ridge solve.
+    int lag_stats(int32_t *per_dim, int32_t *capped, int32_t *refit_skipped) {
+        std::vector<int> h((size_t)k * kLagRec, 0);
+        if (lag_rec_valid && lag_rec.p && nlag > 0)
+            TRMF_HIP_CHECK(hipMemcpy(h.data(), lag_rec.p, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+        int nc = 0, ns = 0;
+        for (int t = 0; t < k; t++) { nc += h[(size_t)t * kLagRec + 2] != 0; ns += h[(size_t)t * kLagRec + 3] != 0; }
+        if (per_dim) std::memcpy(per_dim, h.data(), h.size() * sizeof(int));
+        if (capped) *capped = nc;
+        if (refit_skipped) *refit_skipped = ns;
         return 0;
     }
 };

@@ -82,8 +82,8 @@ struct SessionGroup {
             tl_comm() = comms[rank];
             int rc = t(rank);
             if (rc) {
-                grp->fail();                     // nobody waits for a rank that has failed (comm.hpp: ThreadGroup::barrier)
                 w->err = trmf_last_error_text();
+                grp->fail();                     // nobody waits for a rank that has failed (comm.hpp: ThreadGroup::barrier)
             }
             { std::lock_guard<std::mutex> lk(w->mu); w->rc = rc; w->done = true; }
             w->cv.notify_all();

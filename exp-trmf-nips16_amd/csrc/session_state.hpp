@@ -259,6 +259,16 @@ struct SessionState {
     hipStream_t aux_theta = nullptr;
     hipEvent_t theta_fork = nullptr, theta_done = nullptr;
     bool theta_pending = false;
+    // ---- sparse lag weights (trmf_session_set_lag_penalty; theta_kernels.hpp: theta_lasso_kernel) ------------------------------
+    // lambdaLagL1 > 0 or lag_refit: the Theta-solve is theta_gram_kernel + theta_lasso_kernel (warm-started from the current
+    // Theta, which is part of mark / rewind); both zero: today's ridge kernels, nothing else launched.  The fp64 systems of a lag
+    // set too long for LDS live in lasso_scratch; lag_rec holds the k x kLagRec record of the last lasso solve.
+    double lambdaLagL1 = 0;
+    int lag_refit = 0;
+    DevBuf<double> lasso_scratch;
+    DevBuf<int> lag_rec;
+    bool lag_rec_valid = false;               // the last Theta-solve enqueued was a lasso solve (the ridge path keeps no record)
+    bool lag_lasso() const { return lambdaLagL1 > 0 || lag_refit != 0; }
     // lagged inner products: k T |L|^2 / 2 multiply-adds in a latency-bound kernel; 1e8 (config 3) = 28 us, 3.6e9 (paper shape) = 250 us
     bool theta_overlap_pays() const { return (double)k * (double)T * (double)nlag * (double)nlag >= (test_env("TRMF_OVERLAP_ALWAYS") ? 0.0 : 1e9); }
     bool overlap_ok() { return !verbose && !log_norms && !test_env("TRMF_NO_OVERLAP") && theta_overlap_pays() && ensure_aux() == 0; }

@@ -628,6 +628,20 @@ struct SessionXPhase : SessionFPhase {
     // ---- Theta solve (trmf.cpp:677-689 -> 455-484) ------------------------------------------------------
     size_t theta_gram_lds() const { return theta_gram_lds_bytes(midx); }
     size_t theta_solve_lds() const { return (size_t)(nlag * nlag + nlag) * sizeof(real); }
+    size_t theta_lasso_lds() const { return theta_lasso_doubles(nlag) * sizeof(double); }
+    // buffers of the lasso solve, on first use: the record table and -- where the fp64 system does not fit LDS -- the scratch
+    int ensure_lasso_buffers() {
+        if (nlag == 0) return 0;
+        FillStreamScope fill(stream);
+        if (!lag_rec.p && lag_rec.alloc((size_t)k * kLagRec)) return kFail;
+        if (theta_lasso_lds() > kLdsMax) {
+            const size_t need = (size_t)k * theta_lasso_doubles(nlag);
+            if (!lasso_scratch.p) DevicePool::current().reserve(need * sizeof(double));
+            if (!lasso_scratch.p && lasso_scratch.alloc(need, false)) return kFail;
+            return 0;
+        }
+        return allow_dyn_lds(theta_lasso_kernel<false>, theta_lasso_lds(), "lasso Theta solve");
+    }
     int theta_solve(hipStream_t stream) {
         if (nlag == 0) return 0;
         const int nchunk = std::max(1, (T - midx + kThetaChunk - 1) / kThetaChunk);
@@ -635,6 +649,18 @@ struct SessionXPhase : SessionFPhase {
         const size_t lds1 = theta_gram_lds();
         hipLaunchKernelGGL(theta_gram_kernel, dim3(k, nchunk), dim3(256), lds1, stream, W.p, T, KP, lag_set.p,
                            nlag, midx, npairs, theta_part.p);
+        if (lag_lasso()) {
+            if (lasso_scratch.p)
+                hipLaunchKernelGGL(theta_lasso_kernel<true>, dim3(k), dim3(256), 0, stream, theta_part.p, nchunk, nlag, npairs, lambdaLag,
+                                   lambdaLagL1, lag_refit, theta.p, lasso_scratch.p, lag_rec.p);
+            else
+                hipLaunchKernelGGL(theta_lasso_kernel<false>, dim3(k), dim3(256), theta_lasso_lds(), stream, theta_part.p, nchunk, nlag, npairs,
+                                   lambdaLag, lambdaLagL1, lag_refit, theta.p, (double *)nullptr, lag_rec.p);
+            TRMF_HIP_CHECK(hipGetLastError());
+            lag_rec_valid = true;
+            return 0;
+        }
+        lag_rec_valid = false;
         const size_t lds2 = theta_scratch.p ? 0 : theta_solve_lds();
         hipLaunchKernelGGL(theta_solve_kernel, dim3(k), dim3(256), lds2, stream, theta_part.p, nchunk, nlag,
                            npairs, lambdaLag, theta.p, theta_scratch.p);

@@ -143,48 +143,33 @@ __global__ __launch_bounds__(256) void theta_gram_kernel(const real *__restrict_
     }
 }
 
-// one workgroup per latent dimension; dynamic LDS = (nlag*nlag + nlag) * sizeof(real).  All 256 threads add up the
-// time-chunk partials (a single wavefront streaming nchunk * npairs doubles is latency-bound: 125 us of the former
-// 187 us at 48 lags); the |L| x |L| solve itself is one wavefront's work, the other three retire after the sum.
-// `scratch` != null: the systems live there ((nlag*nlag + nlag) reals per latent dimension, L2-resident) instead of LDS -- lag sets
-// too long for LDS (the reference has no limit on |L|: trmf.cpp:425-484); same code, workgroup barriers order the accesses.
-__global__ __launch_bounds__(256) void theta_solve_kernel(const double *__restrict__ part, int nchunk,
-                                                         int nlag, int npairs, double lambdaLag,
-                                                         real *__restrict__ theta, real *__restrict__ scratch) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    real *A = scratch ? scratch + (size_t)blockIdx.x * ((size_t)nlag * nlag + nlag) : reinterpret_cast<real *>(smem_raw);   // nlag x nlag, (i,j) at A[i*nlag+j]
-    real *y = A + nlag * nlag;
-    const int t = blockIdx.x, lane = threadIdx.x;
-    for (int p = threadIdx.x; p < npairs; p += 256) {
-        double acc = 0;
+// sum over the time chunks of pair p of latent dimension t, in the fixed chunk order (shared by the ridge and the lasso solve)
+__device__ __forceinline__ double theta_sum_pair(const double *__restrict__ part, int nchunk, int npairs, int t, int p) {
+    double acc = 0;
 #pragma unroll 8
-        for (int ch = 0; ch < nchunk; ch++) acc += part[((size_t)t * nchunk + ch) * npairs + p];   // fixed order
-        int a, b; bool rhs;
-        theta_decode_pair(p, nlag, a, b, rhs);
-        if (rhs) y[a] = (real)acc;
-        else {
-            real v = (real)acc;                                              // trmf.cpp:473
-            if (a == b) v = (real)((double)v + lambdaLag);                   // trmf.cpp:480
-            A[a * nlag + b] = v;
-            A[b * nlag + a] = v;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x >= 64) return;                      // the barriers below only count the wavefront that is left
+    for (int ch = 0; ch < nchunk; ch++) acc += part[((size_t)t * nchunk + ch) * npairs + p];   // fixed order
+    return acc;
+}
+
+// A x = y for the symmetric positive definite n x n system A ((i,j) at A[i*n+j], upper triangle read), x left in y; one wavefront
+// (lane = 0..63), LDS or -- with the workgroup barriers ordering the accesses -- global scratch.  CHECK: a pivot that is not
+// positive and finite ends the factorisation and returns false (A and y are then void); without it nothing is tested.
+template <typename E, bool CHECK> __device__ __forceinline__ bool theta_chol_solve(E *A, E *y, int nlag, int lane) {
     // upper Cholesky A = U^T U, row by row (posv 'U', rf_matrix.h:3008-3014).  One wavefront: LDS accesses
     // retire in program order, the barriers are wave-local.  Same operations on every element, in the same j order,
     // as the row-by-row loop.
     for (int j = 0; j < nlag; j++) {
-        const real ajj = sqrt(A[j * nlag + j]);
+        if (CHECK) { const E piv = A[j * nlag + j]; if (!(piv > E(0)) || !isfinite(piv)) return false; }
+        const E ajj = sqrt(A[j * nlag + j]);
         __syncthreads();
         for (int c = j + lane; c < nlag; c += 64) A[j * nlag + c] = (c == j) ? ajj : A[j * nlag + c] / ajj;
         __syncthreads();
         // trailing update, a lane per column (two for more than 64 lags): rows s = j+1 .. c of its column
         for (int c = j + 1 + lane; c < nlag; c += 64) {
-            const real ujc = A[j * nlag + c];
+            const E ujc = A[j * nlag + c];
             int s = j + 1;
             for (; s + 3 <= c; s += 4) {                 // four independent rows per pass: reads first, then writes
-                real u[4], a[4];
+                E u[4], a[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) { u[q] = A[j * nlag + s + q]; a[q] = A[(s + q) * nlag + c]; }
 #pragma unroll
@@ -210,7 +195,166 @@ __global__ __launch_bounds__(256) void theta_solve_kernel(const double *__restri
         for (int i = lane; i < q; i += 64) y[i] -= A[i * nlag + q] * y[q];
         __syncthreads();
     }
+    return true;
+}
+
+// one workgroup per latent dimension; dynamic LDS = (nlag*nlag + nlag) * sizeof(real).  All 256 threads add up the
+// time-chunk partials (a single wavefront streaming nchunk * npairs doubles is latency-bound: 125 us of the former
+// 187 us at 48 lags); the |L| x |L| solve itself is one wavefront's work, the other three retire after the sum.
+// `scratch` != null: the systems live there ((nlag*nlag + nlag) reals per latent dimension, L2-resident) instead of LDS -- lag sets
+// too long for LDS (the reference has no limit on |L|: trmf.cpp:425-484); same code, workgroup barriers order the accesses.
+__global__ __launch_bounds__(256) void theta_solve_kernel(const double *__restrict__ part, int nchunk,
+                                                         int nlag, int npairs, double lambdaLag,
+                                                         real *__restrict__ theta, real *__restrict__ scratch) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    real *A = scratch ? scratch + (size_t)blockIdx.x * ((size_t)nlag * nlag + nlag) : reinterpret_cast<real *>(smem_raw);   // nlag x nlag, (i,j) at A[i*nlag+j]
+    real *y = A + nlag * nlag;
+    const int t = blockIdx.x, lane = threadIdx.x;
+    for (int p = threadIdx.x; p < npairs; p += 256) {
+        const double acc = theta_sum_pair(part, nchunk, npairs, t, p);
+        int a, b; bool rhs;
+        theta_decode_pair(p, nlag, a, b, rhs);
+        if (rhs) y[a] = (real)acc;
+        else {
+            real v = (real)acc;                                              // trmf.cpp:473
+            if (a == b) v = (real)((double)v + lambdaLag);                   // trmf.cpp:480
+            A[a * nlag + b] = v;
+            A[b * nlag + a] = v;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;                      // the barriers below only count the wavefront that is left
+    theta_chol_solve<real, false>(A, y, nlag, lane);
     for (int a = lane; a < nlag; a += 64) theta[(size_t)t * nlag + a] = y[a];
+}
+
+// ---- sparse lag weights: L1-penalised Theta-solve (the reference's MATLAB trainer, do_lasso; no counterpart in trmf.cpp) ----------
+//   theta_t = argmin 1/2 th^T G_t th - b_t^T th + 1/2 lambdaLag |th|^2 + lambdaL1 |th|_1
+// by cyclic coordinate descent with covariance updates, warm-started from the session's current Theta, then (refit != 0) the ridge
+// solution on the support the lasso selected.  Everything in fp64 in both libraries; Theta is rounded to `real` on the final store.
+#if defined(TRMF_F32)
+constexpr double kLassoEps = 1e-7;       // a sweep that moves no coordinate by more than kLassoEps * max(1, |theta|_inf) is the last
+#else
+constexpr double kLassoEps = 1e-13;      // (1e-10 would leave Theta ~cond * 1e-10 from the minimiser: above the fp64 Cholesky's own error in the ridge limit)
+#endif
+constexpr int kLassoMaxSweeps = 1000;    // a dimension that gets here keeps its iterate and is counted (TrmfLagStats: capped)
+constexpr int kLagRec = 4;               // per-dimension record: sweeps, non-zeros, hit the cap, refit skipped
+__host__ __device__ inline size_t theta_lasso_doubles(int nlag) { return (size_t)nlag * nlag + 3 * (size_t)nlag; }   // G, b, r, theta
+
+__device__ __forceinline__ double lasso_soft(double rho, double l1) { return rho > l1 ? rho - l1 : rho < -l1 ? rho + l1 : 0.0; }
+
+// grid k, 256 threads, dynamic LDS = theta_lasso_doubles(nlag) * 8, or (GLOB) 0 and `scratch` of that many doubles per latent dimension.
+// All threads sum the chunk partials (theta_sum_pair) into the full symmetric G, into b, and form r = b - G theta; one wavefront
+// does the sweeps -- LDS accesses of one wavefront retire in program order; on global scratch the (then wave-local) workgroup
+// barrier orders them, as in theta_chol_solve.  Per coordinate j, ascending: rho = r_j + G_jj th_j, th_j' = soft(rho, l1) / (G_jj +
+// lambdaLag) (0 where that denominator is not positive and finite), r -= (th_j' - th_j) G[j, :] -- row j is column j, contiguous.
+// A fixed order of operations, no atomics: the same bits every time.
+// GLOB: the two forms are two instantiations, so that the LDS form addresses LDS as LDS (not through generic pointers).
+template <bool GLOB>
+__global__ __launch_bounds__(256) void theta_lasso_kernel(const double *__restrict__ part, int nchunk, int nlag, int npairs,
+                                                         double lambdaLag, double lambdaL1, int refit, real *__restrict__ theta,
+                                                         double *__restrict__ scratch, int *__restrict__ rec) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    constexpr bool glob = GLOB;
+    double *G = GLOB ? scratch + (size_t)blockIdx.x * theta_lasso_doubles(nlag) : reinterpret_cast<double *>(smem_raw);
+    double *b = G + (size_t)nlag * nlag, *r = b + nlag, *th = r + nlag;
+    const int t = blockIdx.x, lane = threadIdx.x;
+    for (int p = threadIdx.x; p < npairs; p += 256) {
+        const double acc = theta_sum_pair(part, nchunk, npairs, t, p);
+        int a, c; bool rhs;
+        theta_decode_pair(p, nlag, a, c, rhs);
+        if (rhs) b[a] = acc;
+        else { G[a * nlag + c] = acc; G[c * nlag + a] = acc; }
+    }
+    for (int i = threadIdx.x; i < nlag; i += 256) {
+        const double v = (double)theta[(size_t)t * nlag + i];
+        th[i] = isfinite(v) ? v : 0.0;                  // (a warm start that is not a number is no warm start)
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nlag; i += 256) {
+        double acc = b[i];
+        for (int j = 0; j < nlag; j++) acc -= G[j * nlag + i] * th[j];      // column i = row i; ascending j
+        r[i] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;                      // the barriers below only count the wavefront that is left
+    int sweeps = 0, capped = 0;
+    for (;;) {
+        double dmax = 0, tmax = 0;
+        for (int j = 0; j < nlag; j++) {
+            const double gjj = G[j * nlag + j], thj = th[j], den = gjj + lambdaLag;
+            double tn = (den > 0 && isfinite(den)) ? lasso_soft(r[j] + gjj * thj, lambdaL1) / den : 0.0;
+            if (!isfinite(tn)) tn = 0.0;
+            const double delta = tn - thj;
+            // No barrier in the LDS form: besides the in-order retirement of one wavefront's LDS accesses this needs the compiler to
+            // keep program order between the lanes' stores to r[] / th[] and the next coordinate's loads of r[j + 1], th[j + 1] -- it
+            // does, because they go through the same may-aliasing pointers.  Do not mark r / th / G __restrict__ or cache them in
+            // registers across coordinates.
+            if (delta != 0) {                           // (uniform: every lane has read the same three values)
+                if (glob) __syncthreads();              // ... before any lane overwrites r[j]
+                for (int i = lane; i < nlag; i += 64) r[i] -= delta * G[j * nlag + i];
+                if (lane == 0) th[j] = tn;
+                if (glob) __syncthreads();
+            }
+            dmax = fmax(dmax, fabs(delta)); tmax = fmax(tmax, fabs(tn));
+        }
+        sweeps++;
+        if (dmax <= kLassoEps * fmax(1.0, tmax)) break;
+        if (sweeps >= kLassoMaxSweeps) { capped = 1; break; }
+    }
+    // the support is what survives the rounding to the element type (so that the record, the refit and the stored Theta agree)
+    int *idx = reinterpret_cast<int *>(r);              // r is no longer needed: ascending indices of the support
+    int m = 0;
+    __syncthreads();
+    for (int base = 0; base < nlag; base += 64) {
+        const bool on = base + lane < nlag && (real)th[base + lane] != real(0);
+        const unsigned long long mask = __ballot(on);
+        if (on) idx[m + __popcll(mask & ((1ull << lane) - 1ull))] = base + lane;
+        m += __popcll(mask);
+    }
+    __syncthreads();
+    int skipped = 0;
+    if (refit && m > 0) {
+        // G_SS + lambdaLag I and b_S compacted in place: target (p, q) of the m x m system lies at or before its source
+        // (idx[p] >= p, idx[q] >= q, m <= nlag) and strictly before the source of every later target, so 64 targets at a time --
+        // all read, then all written -- never overwrite an entry that is still to be read
+        for (int base = 0; base < m * m; base += 64) {
+            const int o = base + lane, p = o / m, q = o - p * m;
+            double v = 0;
+            if (o < m * m) v = G[idx[p] * nlag + idx[q]] + (p == q ? lambdaLag : 0.0);
+            __syncthreads();
+            if (o < m * m) G[o] = v;
+            __syncthreads();
+        }
+        for (int base = 0; base < m; base += 64) {
+            const int p = base + lane;
+            double v = 0;
+            if (p < m) v = b[idx[p]];
+            __syncthreads();
+            if (p < m) b[p] = v;
+            __syncthreads();
+        }
+        bool ok = theta_chol_solve<double, true>(G, b, m, lane);
+        __syncthreads();
+        if (ok)
+            for (int base = 0; base < m; base += 64)
+                if (__ballot(base + lane < m && !isfinite(b[base + lane]))) ok = false;
+        if (ok) { for (int p = lane; p < m; p += 64) th[idx[p]] = b[p]; }
+        else skipped = 1;                               // the lasso's own solution stays
+        __syncthreads();
+    }
+    int nnz = 0;
+    for (int base = 0; base < nlag; base += 64) {
+        const int a = base + lane;
+        real v = real(0);
+        if (a < nlag) {
+            v = (real)th[a];
+            if (v == real(0)) v = real(0);              // exact +0 off the support
+            theta[(size_t)t * nlag + a] = v;
+        }
+        nnz += __popcll(__ballot(a < nlag && v != real(0)));
+    }
+    if (lane < kLagRec) rec[t * kLagRec + lane] = lane == 0 ? sweeps : lane == 1 ? nnz : lane == 2 ? capped : skipped;
 }
 
 }  // namespace trmf

@@ -17,7 +17,9 @@ namespace trmf {
 
 static std::string g_last_error = "";
 static std::mutex g_err_mu;
+static thread_local std::string tl_last_error;     // the calling thread's own last error (a rank thread's cause, not a peer's echo)
 void set_error(const std::string &msg) {
+    tl_last_error = msg;
     std::lock_guard<std::mutex> lk(g_err_mu);
     g_last_error = msg;
 }
@@ -32,7 +34,8 @@ static std::shared_ptr<Comm> g_comm;
 // trmf_session_destroy() leaves the session's communicator alive until the session goes away.
 // (a worker thread of an in-process session group has its own communicator and device: session_group.hpp)
 std::shared_ptr<Comm> active_comm() { return tl_comm() ? tl_comm() : g_comm ? g_comm : g_self; }
-std::string SessionGroup::trmf_last_error_text() { std::lock_guard<std::mutex> lk(g_err_mu); return g_last_error; }
+// (per thread: a peer woken by the broken barrier sets "another rank ... failed" at once, and would replace the failing rank's text)
+std::string SessionGroup::trmf_last_error_text() { return tl_last_error; }
 
 static bool bind_device() {
     int cnt = 0;
@@ -502,6 +505,24 @@ int32_t trmf_session_set_lambdas(TrmfSession *s, double lambdaI, double lambdaAR
     if (!std::isfinite(lambdaI) || !std::isfinite(lambdaAR) || !std::isfinite(lambdaLag)) { set_error("set_lambdas: weights must be finite"); return kFail; }
     DeviceGuard guard;
     return guard.ok ? HND(s)->all([&](TrmfSessionImpl *t) { return t->set_lambdas(lambdaI, lambdaAR, lambdaLag); }) : kFail;
+}
+int32_t trmf_session_set_lag_penalty(TrmfSession *s, double lambdaLagL1, int32_t refit) {
+    if (!s) { set_error("null session"); return kFail; }
+    if (!std::isfinite(lambdaLagL1) || lambdaLagL1 < 0) { set_error("set_lag_penalty: lambdaLagL1 must be finite and not negative"); return kFail; }
+    DeviceGuard guard;
+    return guard.ok ? HND(s)->all([&](TrmfSessionImpl *t) { return t->set_lag_penalty(lambdaLagL1, refit); }) : kFail;
+}
+int32_t trmf_session_solve_lags(TrmfSession *s) {
+    if (!s) { set_error("null session"); return kFail; }
+    DeviceGuard guard;
+    return guard.ok ? HND(s)->all([&](TrmfSessionImpl *t) { return t->solve_lags(); }) : kFail;
+}
+int32_t trmf_session_lag_stats(TrmfSession *s, int32_t *per_dim, int32_t *capped, int32_t *refit_skipped) {
+    if (!s) { set_error("null session"); return kFail; }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    if (HND(s)->all([&](TrmfSessionImpl *t) { return t->sync(); })) return kFail;       // every rank holds the same record: rank 0 answers
+    return HND(s)->rank0([&](TrmfSessionImpl *t) { return t->lag_stats(per_dim, capped, refit_skipped); });
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

@@ -24,8 +24,8 @@ from .model import Model
 from .validate import _grid_points
 
 _FIELDS = ('nd', 'nrmse', 'mse', 'mape', 'count')
-_DEFAULTS = dict(k=40, lambdaI=0.5, lambdaAR=50.0, lambdaLag=0.5, max_iter=10, seed=0, dtype=None)
-_GRID_KEYS = ('k', 'lambdaI', 'lambdaAR', 'lambdaLag')
+_DEFAULTS = dict(k=40, lambdaI=0.5, lambdaAR=50.0, lambdaLag=0.5, max_iter=10, seed=0, dtype=None, lambdaLagL1=0.0, lag_refit=False)
+_GRID_KEYS = ('k', 'lambdaI', 'lambdaAR', 'lambdaLag', 'lambdaLagL1')
 
 
 def _ratio(num, den):
@@ -100,8 +100,10 @@ def _session(Ytr, lag_set, k, seed, dtype, hyper):
     return Session(Ytr, model, missing=True, log_norms=False, timing=0, **hyper), model
 
 
-def impute(Y, observed, lag_set, k=40, lambdaI=0.5, lambdaAR=50.0, lambdaLag=0.5, max_iter=10, seed=0, dtype=None):
-    """Train on the observed cells of the dense T x n ``Y`` (boolean mask ``observed``) and fill in the others.
+def impute(Y, observed, lag_set, k=40, lambdaI=0.5, lambdaAR=50.0, lambdaLag=0.5, max_iter=10, seed=0, dtype=None,
+           lambdaLagL1=0.0, lag_refit=False):
+    """Train on the observed cells of the dense T x n ``Y`` (boolean mask ``observed``) and fill in the others
+    (``lambdaLagL1`` / ``lag_refit``: sparse lag weights, ``Session.set_lag_penalty``).
 
     Returns ``(filled, metrics, model)``: ``Y`` with every unobserved cell replaced by the model's prediction, the
     ``ImputeMetrics`` over the unobserved cells whose ``Y`` is finite (``None`` when there is none), and the trained ``Model``."""
@@ -109,7 +111,10 @@ def impute(Y, observed, lag_set, k=40, lambdaI=0.5, lambdaAR=50.0, lambdaLag=0.5
     Ytr = training_matrix(Y, observed, dtype)
     filled = np.array(Y, copy=True)
     metrics = None
-    sess, model = _session(Ytr, lag_set, k, seed, dtype, dict(lambdaI=lambdaI, lambdaAR=lambdaAR, lambdaLag=lambdaLag))
+    hyper = dict(lambdaI=lambdaI, lambdaAR=lambdaAR, lambdaLag=lambdaLag)
+    if lambdaLagL1 or lag_refit:
+        hyper.update(lambdaLagL1=lambdaLagL1, lag_refit=lag_refit)
+    sess, model = _session(Ytr, lag_set, k, seed, dtype, hyper)
     with sess:
         sess.run(max_iter)
         if rows.size:
@@ -128,8 +133,8 @@ def impute(Y, observed, lag_set, k=40, lambdaI=0.5, lambdaAR=50.0, lambdaLag=0.5
 
 
 def grid_impute(Y, observed, lag_set, grid_params, **kw):
-    """Every combination of ``grid_params`` (keys among k, lambdaI, lambdaAR, lambdaLag) scored like ``impute`` with the
-    remaining settings from ``kw`` (max_iter, seed, dtype and the fixed values of the grid keys).  One resident session per
+    """Every combination of ``grid_params`` (keys among k, lambdaI, lambdaAR, lambdaLag, lambdaLagL1) scored like ``impute`` with
+    the remaining settings from ``kw`` (max_iter, seed, dtype, lag_refit and the fixed values of the grid keys).  One resident session per
     ``k``: the held-out cells are uploaded once and the initial model is marked; each weight combination then rewinds to it,
     sets the weights and trains -- no factor is downloaded.  Returns ``(results, best_by_nrmse, best_by_nd)``: a list of
     ``{'kws': settings, 'metrics': ImputeMetrics}`` in grid order and the two best entries of it."""
@@ -140,6 +145,10 @@ def grid_impute(Y, observed, lag_set, grid_params, **kw):
     if unknown:
         raise ValueError('grid_impute: unknown settings {}'.format(sorted(unknown)))
     base = dict(_DEFAULTS, **kw)
+    from .session import check_lag_penalty
+    for l1 in list(grid_params.get('lambdaLagL1', ())) + [base['lambdaLagL1']]:
+        check_lag_penalty(l1, base['lag_refit'])
+    sparse_lags = bool(base['lag_refit']) or any(float(v) > 0 for v in list(grid_params.get('lambdaLagL1', ())) + [base['lambdaLagL1']])
     Y, observed, dtype, rows, cols, finite = _setup(Y, observed, base['dtype'])
     if not finite.any():
         raise ValueError('grid_impute: no unobserved cell with a finite value to score')
@@ -157,7 +166,10 @@ def grid_impute(Y, observed, lag_set, grid_params, **kw):
             sess.set_heldout(held).mark()
             for idx in members:
                 st = points[idx]
-                sess.rewind().set_lambdas(st['lambdaI'], st['lambdaAR'], st['lambdaLag']).run(st['max_iter'])
+                sess.rewind().set_lambdas(st['lambdaI'], st['lambdaAR'], st['lambdaLag'])
+                if sparse_lags:
+                    sess.set_lag_penalty(st['lambdaLagL1'], st['lag_refit'])
+                sess.run(st['max_iter'])
                 results[idx] = {'kws': st, 'metrics': sess.eval_heldout()}
     best_by_nrmse = min(results, key=lambda r: r['metrics'].nrmse)
     best_by_nd = min(results, key=lambda r: r['metrics'].nd)

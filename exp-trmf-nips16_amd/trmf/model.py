@@ -182,7 +182,15 @@ class Model(object):
             transform = NormalizedTransform(Y)
         return cls(PyMatrix(W, dtype), PyMatrix(H, dtype), PyMatrix(theta, dtype), lag_set=lags, transform=transform)
 
+    def selected_lags(self, tol=0):
+        """Per latent dimension, the lags of ``lag_set`` whose weight has ``|theta| > tol`` (a list of k uint32 arrays): with
+        sparse lag weights (``train(..., lambdaLagL1=...)``) the lags the data uses."""
+        if tol < 0:
+            raise ValueError('selected_lags: tol must not be negative')
+        used = np.abs(self.lag_val) > tol
+        return [self.lag_set[used[:, t]] for t in range(self.k)]
+
     def fit(self, Y, **kw):
-        """``model.fit(Y, ...)`` is ``train(Y, model, ...)``."""
+        """``model.fit(Y, ...)`` is ``train(Y, model, ...)``, ``lambdaLagL1`` and ``lag_refit`` included."""
         from .trmf import train
         return train(Y, self, **kw)

@@ -104,6 +104,11 @@ def bind(lib):
         lib.trmf_session_forecast_scores.argtypes = [c_void_p, POINTER(c_uint64), c_void_p]
         lib.trmf_session_forecast_scores.restype = c_int32
         lib.trmf_session_forecast_reset.argtypes = [c_void_p]; lib.trmf_session_forecast_reset.restype = c_int32
+    if hasattr(lib, 'trmf_session_set_lag_penalty'):  # (absent from libraries built before the sparse lag weights)
+        lib.trmf_session_set_lag_penalty.argtypes = [c_void_p, c_double, c_int32]; lib.trmf_session_set_lag_penalty.restype = c_int32
+        lib.trmf_session_solve_lags.argtypes = [c_void_p]; lib.trmf_session_solve_lags.restype = c_int32
+        lib.trmf_session_lag_stats.argtypes = [c_void_p, c_void_p, POINTER(c_int32), POINTER(c_int32)]
+        lib.trmf_session_lag_stats.restype = c_int32
     lib.trmf_dist_get_unique_id.argtypes = [c_void_p]; lib.trmf_dist_get_unique_id.restype = c_int32
     lib.trmf_dist_init.argtypes = [c_int32, c_int32, c_void_p]; lib.trmf_dist_init.restype = c_int32
     lib.trmf_dist_init_callback.argtypes = [c_int32, c_int32, ALLGATHERV_FN, c_void_p]
@@ -128,11 +133,28 @@ def train_profile(dtype):
     return prof.as_dict() if lib_for(dtype).trmf_last_train_profile(byref(prof)) == 0 else None
 
 
+def check_lag_penalty(lambdaLagL1, lag_refit=False):
+    """The front end's argument check of the sparse lag weights: a finite ``lambdaLagL1 >= 0`` as a float, ``lag_refit`` as a bool."""
+    try:
+        l1 = float(lambdaLagL1)
+    except (TypeError, ValueError):
+        raise TypeError('lambdaLagL1 must be a number, not {!r}'.format(lambdaLagL1))
+    if not np.isfinite(l1) or l1 < 0:
+        raise ValueError('lambdaLagL1 must be finite and not negative, not {!r}'.format(lambdaLagL1))
+    return l1, bool(lag_refit)
+
+
 class Session(object):
-    """``Session(Y, model, **hyper).run(iters)``; the model's arrays are refreshed by ``download()``."""
+    """``Session(Y, model, **hyper).run(iters)``; the model's arrays are refreshed by ``download()``.
+
+    ``lambdaLagL1 > 0`` makes the lag weights sparse (an L1 penalty next to the ridge ``lambdaLag``), ``lag_refit`` re-solves
+    them on the selected support; the defaults are the reference's ridge solve."""
 
     def __init__(self, Y, model, lambdaI=0.1, lambdaAR=0.1, lambdaLag=0.1,
-                 period_W=1, period_H=1, period_Lag=2, missing=True, verbose=0, log_norms=True, timing=1):
+                 period_W=1, period_H=1, period_Lag=2, missing=True, verbose=0, log_norms=True, timing=1,
+                 lambdaLagL1=0.0, lag_refit=False):
+        lambdaLagL1, lag_refit = check_lag_penalty(lambdaLagL1, lag_refit)
+        self.handle = None
         self.model = model
         self.lib = lib_for(model.W.dtype)
         self.pyY = Y if isinstance(Y, PyMatrix) else PyMatrix(Y, dtype=model.W.dtype)
@@ -146,6 +168,12 @@ class Session(object):
             self.lib.trmf_session_log_norms(self.handle, 0)
         if timing != 1:         # phase events (ms_* of stats()) on every `timing`-th iteration only / never (0): they cost ~25 us apiece
             self._check(self.lib.trmf_session_set_timing(self.handle, int(timing)), 'trmf_session_set_timing')
+        if lambdaLagL1 > 0 or lag_refit:
+            try:
+                self.set_lag_penalty(lambdaLagL1, lag_refit)
+            except Exception:
+                self.close()            # nobody else holds the native handle yet
+                raise
 
     def _check(self, rc, what):
         if rc < 0:
@@ -201,6 +229,25 @@ class Session(object):
         from one resident problem and one initial model)."""
         self._check(self.lib.trmf_session_set_lambdas(self.handle, lambdaI, lambdaAR, lambdaLag), 'trmf_session_set_lambdas')
         return self
+
+    def set_lag_penalty(self, lambdaLagL1, lag_refit=False):
+        """L1 weight of the lag weights (and the refit on the selected support) for the lag-weight solves run from now on;
+        ``(0, False)`` restores the ridge solve exactly.  The library refuses a negative or non-finite weight and stays usable."""
+        self._check(self.lib.trmf_session_set_lag_penalty(self.handle, float(lambdaLagL1), int(bool(lag_refit))), 'trmf_session_set_lag_penalty')
+        return self
+
+    def solve_lags(self):
+        """Recompute the lag weights from the session's current W with the current penalties (the lag-weight phase on its own)."""
+        self._check(self.lib.trmf_session_solve_lags(self.handle), 'trmf_session_solve_lags')
+        return self
+
+    def lag_stats(self):
+        """Record of the last lag-weight solve: ``{'per_dim': k x 4 int32 (sweeps, non-zeros, capped, refit skipped), 'capped': int,
+        'refit_skipped': int}``; all zero after a ridge solve."""
+        per_dim = np.zeros((self.model.k, 4), dtype=np.int32)
+        capped, skipped = c_int32(0), c_int32(0)
+        self._check(self.lib.trmf_session_lag_stats(self.handle, per_dim.ctypes.data, byref(capped), byref(skipped)), 'trmf_session_lag_stats')
+        return {'per_dim': per_dim, 'capped': int(capped.value), 'refit_skipped': int(skipped.value)}
 
     def set_heldout(self, Ytest):
         """Upload the held-out positions and truths: a sparse T' x n matrix (T' <= rows()) whose STORED entries, explicit
@@ -312,7 +359,7 @@ class Session(object):
         return buf.value.decode()
 
     def close(self):
-        if self.handle:
+        if getattr(self, 'handle', None):
             self.lib.trmf_session_destroy(self.handle)
             self.handle = None
 

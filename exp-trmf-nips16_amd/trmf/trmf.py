@@ -27,10 +27,22 @@ from .validate import grid_search, rolling_validate              # noqa: F401
 
 def train(Y, model, lambdaI=0.1, lambdaAR=0.1, lambdaLag=0.1,
           max_iter=10, period_W=1, period_H=1, period_Lag=2,
-          threads=1, missing=False, verbose=0):
-    """Run ``max_iter`` ALS iterations on the GPU, updating ``model`` in place (trmf.py:253-264)."""
+          threads=1, missing=False, verbose=0, lambdaLagL1=0.0, lag_refit=False):
+    """Run ``max_iter`` ALS iterations on the GPU, updating ``model`` in place (trmf.py:253-264).
+
+    ``lambdaLagL1 > 0`` / ``lag_refit``: sparse lag weights (``Session.set_lag_penalty``).  ``c_trmf_train`` has no argument for
+    them, so that run goes through a ``Session`` with the settings of a ``c_trmf_train`` call and downloads into ``model``."""
+    from .session import check_lag_penalty
+    lambdaLagL1, lag_refit = check_lag_penalty(lambdaLagL1, lag_refit)
     if model.transform is not None:
         Y = model.transform.preprocess(Y)
+    if lambdaLagL1 > 0 or lag_refit:
+        from .session import Session
+        with Session(Y, model, lambdaI=lambdaI, lambdaAR=lambdaAR, lambdaLag=lambdaLag, period_W=period_W, period_H=period_H,
+                     period_Lag=period_Lag, missing=missing, verbose=verbose, log_norms=bool(verbose > 0), timing=0,
+                     lambdaLagL1=lambdaLagL1, lag_refit=lag_refit) as sess:
+            sess.run(max_iter).download()
+        return model
     get_clib().train(PyMatrix(Y, dtype=model.W.dtype), model.lag_set,
                      model.pyW, model.pyH, model.pylag_val, warm_start=True,
                      lambdaI=lambdaI, lambdaAR=lambdaAR, lambdaLag=lambdaLag,

@@ -31,13 +31,13 @@ def _as_training_matrix(block, missing):
     return smat.csr_matrix(block) if missing else block
 
 
-def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose):
+def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag=None):
     """Yield the trained model of every window from one resident session.  With a transform (dense Y, full
     observation) the session holds the RAW matrix and applies each window's refitted coefficients on the device."""
     from .session import Session
     model = Model.initialize(Y[:cuts[0]], lag_set, k, seed=seed, transform=transform)
     with Session(_as_training_matrix(Y[:cuts[0]], missing), model, missing=missing, verbose=verbose,
-                 log_norms=bool(verbose), timing=0, **hyper) as sess:      # (nobody reads per-phase times here: no phase events)
+                 log_norms=bool(verbose), timing=0, **dict(hyper, **(lag or {}))) as sess:      # (nobody reads per-phase times here: no phase events)
         if model.transform is not None:
             sess.set_transform(model.transform)
         sess.run(max_iter).download()
@@ -54,14 +54,14 @@ def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing,
             yield model
 
 
-def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose):
+def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag=None):
     """The whole rolling evaluation from one resident session: every window is trained, forecast and scored on the device
     (``Session.forecast`` with the window's truth), the next window's rows are appended and, if asked for, a transform
     refitted on the grown prefix is handed over.  No factor is downloaded and no host model is rebuilt between windows."""
     from .session import Session
     model = Model.initialize(Y[:cuts[0]], lag_set, k, seed=seed, transform=transform)
     with Session(_as_training_matrix(Y[:cuts[0]], missing), model, missing=missing, verbose=verbose,
-                 log_norms=bool(verbose), timing=0, **hyper) as sess:
+                 log_norms=bool(verbose), timing=0, **dict(hyper, **(lag or {}))) as sess:
         if model.transform is not None:
             sess.set_transform(model.transform)
         for i, cut in enumerate(cuts):
@@ -74,27 +74,31 @@ def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_
         return sess.forecast_scores()
 
 
-def _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, threads, verbose):
+def _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, threads, verbose, lag=None):
     """Yield the trained model of every window, each from its own upload (needed with a per-window transform)."""
     from .trmf import train
     model = None
     for cut in cuts:
         prefix = _as_training_matrix(Y[:cut], missing)
         model = Model.initialize(prefix, lag_set, k, seed=seed, warm_start_model=model, transform=transform)
-        train(prefix, model, max_iter=max_iter, missing=missing, threads=threads, verbose=verbose, **hyper)
+        train(prefix, model, max_iter=max_iter, missing=missing, threads=threads, verbose=verbose, **dict(hyper, **(lag or {})))
         yield model
 
 
 def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5, lambdaAR=50, lambdaLag=0.5,
                      max_iter=20, missing=True, threshold=0, transform=None, threads=16, verbose=0, seed=0,
-                     resident=True, forecast_on_device=False):
-    """``forecast_on_device=True`` keeps the forecasts and their scoring on the device as well (one session, no download and no
+                     resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False):
+    """``lambdaLagL1`` / ``lag_refit``: sparse lag weights (``Session.set_lag_penalty``) on every path.
+    ``forecast_on_device=True`` keeps the forecasts and their scoring on the device as well (one session, no download and no
     host model per window); it needs the resident path and a dense ``Y``, and says so where that does not hold."""
     T, n = Y.shape
     horizon = nr_windows * window_size
     assert T > horizon, 'series too short for {} windows of {}'.format(nr_windows, window_size)
     cuts = [T - horizon + i * window_size for i in range(nr_windows)]        # training prefix of window i = Y[:cuts[i]]
     hyper = dict(lambdaI=lambdaI, lambdaAR=lambdaAR, lambdaLag=lambdaLag)
+    from .session import check_lag_penalty
+    lambdaLagL1, lag_refit = check_lag_penalty(lambdaLagL1, lag_refit)
+    lag = dict(lambdaLagL1=lambdaLagL1, lag_refit=lag_refit) if (lambdaLagL1 > 0 or lag_refit) else None     # None: the calls of before
     if forecast_on_device:
         if not isinstance(Y, np.ndarray):
             raise ValueError('forecast_on_device: needs a dense NumPy Y (a sparse Y has no resident rolling evaluation)')
@@ -105,12 +109,12 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
         if transform is not None and missing:
             raise ValueError('forecast_on_device: a transform with missing=True is refitted on the host per window; '
                              'the device applies one only to dense full-observation training (missing=False)')
-        return _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose)
+        return _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag)
     # resident: a NumPy Y, and a transform only where the device can apply it (dense full-observation training)
     if resident and isinstance(Y, np.ndarray) and (transform is None or (not missing and Y.dtype in (np.float32, np.float64))):
-        models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose)
+        models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag)
     else:
-        models = _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, threads, verbose)
+        models = _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, threads, verbose, lag)
     forecasts = np.zeros((horizon, n), dtype=Y.dtype, order='C')
     for i, model in enumerate(models):
         model.forecast(window_size, Ynew=forecasts[i * window_size:(i + 1) * window_size], threshold=threshold)

@@ -261,6 +261,24 @@ TRMF_API int32_t trmf_session_eval_heldout(TrmfSession *s, TrmfHeldoutSums *out,
  * a session created with l' from the marked model.  0, or -1 for a value that is not finite. */
 TRMF_API int32_t trmf_session_set_lambdas(TrmfSession *s, double lambdaI, double lambdaAR, double lambdaLag);
 
+/* --- sparse lag weights: which lags does the data use? -------------------------------------------------------------------
+ * With lambdaLagL1 > 0 the lag weights of latent dimension t solve
+ *     argmin  1/2 th^T G_t th - b_t^T th + 1/2 lambdaLag |th|^2 + lambdaLagL1 |th|_1
+ * (G_t, b_t: the lagged inner products of W[:, t] that the ridge solve uses, without lambdaLag on the diagonal) by cyclic
+ * coordinate descent in fp64, warm-started from the session's current lag weights; refit != 0 then replaces the weights on
+ * the selected support S by the solution of (G_SS + lambdaLag I) th_S = b_S.  Weights off the support are exact +0.
+ * Every rank; blocks until the work already enqueued has finished.  (0, 0) restores the ridge solve exactly.  0, or -1 with
+ * trmf_last_error() for a lambdaLagL1 that is negative or not finite (the session is unchanged and stays usable). */
+TRMF_API int32_t trmf_session_set_lag_penalty(TrmfSession *s, double lambdaLagL1, int32_t refit);
+/* The lag-weight phase on its own: recompute the lag weights from the session's current W with the current penalties (ridge or
+ * lasso), after every run() enqueued before; blocking.  The iteration counter, the statistics and the mark are untouched. */
+TRMF_API int32_t trmf_session_solve_lags(TrmfSession *s);
+/* Record of the last lag-weight solve.  per_dim: NULL, or k x 4 int32, row t = (sweeps used, non-zero weights, 1 if the sweep
+ * cap was hit -- the iterate is kept --, 1 if the refit met a pivot that is not positive and finite -- the lasso's solution is
+ * kept); capped / refit_skipped: NULL, or the number of dimensions with that flag.  All zero when the last solve was a ridge
+ * solve (it keeps no record) or none has run. */
+TRMF_API int32_t trmf_session_lag_stats(TrmfSession *s, int32_t *per_dim /* k x 4 */, int32_t *capped, int32_t *refit_skipped);
+
 /* --- forecasting: the next timestamps of a resident model, forecast and scored on the device ----------------------------
  * The rolling evaluation of the paper (and of rolling_validate) forecasts a window from the current factors, scores it against
  * the truth, appends the window and trains on.  These calls do the forecast and the scoring where the factors live.
