@@ -66,6 +66,15 @@ def ref(dtype=np.float32):
     return _cache[key]
 
 
+RAW_ARRAYS = ('row_ptr', 'col_idx', 'val_t', 'col_ptr', 'row_idx', 'val')
+
+
+def is_raw(A):
+    """A sparse matrix given as the six compressed arrays of the C ABI themselves (tests/rawsparse_helpers.RawSparse, duck-typed):
+    the arrays are used as they are -- duplicate entries stay apart, stored zeros stay, the order inside rows and columns stays."""
+    return all(isinstance(getattr(A, name, None), np.ndarray) for name in RAW_ARRAYS)
+
+
 class Mat(object):
     """Keeps NumPy buffers alive and exposes them as an OracleMatrix."""
 
@@ -74,7 +83,12 @@ class Mat(object):
         self.m = OracleMatrix()
         self.buf = {}
         self.m.rows, self.m.cols = A.shape
-        if smat.issparse(A):
+        if is_raw(A):
+            self.buf = dict(row_ptr=np.ascontiguousarray(A.row_ptr, dtype=np.uint64), col_idx=np.ascontiguousarray(A.col_idx, dtype=np.uint32),
+                            val_t=np.ascontiguousarray(A.val_t, dtype=dtype), col_ptr=np.ascontiguousarray(A.col_ptr, dtype=np.uint64),
+                            row_idx=np.ascontiguousarray(A.row_idx, dtype=np.uint32), val=np.ascontiguousarray(A.val, dtype=dtype))
+            self.m.type, self.m.nnz = 3, int(A.row_ptr[-1])
+        elif smat.issparse(A):
             csr, csc = smat.csr_matrix(A), smat.csc_matrix(A)
             self.buf = dict(row_ptr=csr.indptr.astype(np.uint64), col_idx=csr.indices.astype(np.uint32),
                             val_t=csr.data.astype(dtype), col_ptr=csc.indptr.astype(np.uint64),
@@ -133,8 +147,12 @@ def objective(Y, lag_set, W, H, theta, hyper):
     """Global objective J in fp64 on factors of any dtype (parity gate of SURVEY.md 8(d))."""
     import scipy.sparse as smat
     lib = port(np.float64)
-    csr = smat.csr_matrix(Y)
-    ptr = csr.indptr.astype(np.uint64); idx = csr.indices.astype(np.uint32); val = csr.data.astype(np.float64)
+    if is_raw(Y):       # the sum over the entries as stored
+        ptr = np.ascontiguousarray(Y.row_ptr, dtype=np.uint64); idx = np.ascontiguousarray(Y.col_idx, dtype=np.uint32)
+        val = np.ascontiguousarray(Y.val_t, dtype=np.float64)
+    else:
+        csr = smat.csr_matrix(Y)
+        ptr = csr.indptr.astype(np.uint64); idx = csr.indices.astype(np.uint32); val = csr.data.astype(np.float64)
     W64 = np.ascontiguousarray(W, dtype=np.float64); H64 = np.ascontiguousarray(H, dtype=np.float64)
     th = np.asfortranarray(theta, dtype=np.float64)
     lag_set = np.ascontiguousarray(lag_set, dtype=np.uint32)
