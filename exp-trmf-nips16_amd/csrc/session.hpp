@@ -204,6 +204,7 @@ struct TrmfSessionImpl : SessionXPhase {
         if (comm->world == 1) { gramx_mode = kGramxShard; fs_mode = kShardOn; }     // nothing to decide
         if (const char *e = test_env("TRMF_GRAMX")) gramx_mode = (e[0] == 'r') ? kGramxReplicate : kGramxShard;
         if (const char *e = test_env("TRMF_FSHARD")) fs_mode = (e[0] == 'r') ? kShardOff : kShardOn;
+        if (const char *e = test_env("TRMF_THETA_SOLVE")) theta_force_lds = std::string(e) == "lds";
         // the set-up's one synchronisation: uploads landed, factors padded, sum y^2 formed
         if (finish_sum_squares(&ysq_acc)) return kFail;
         set_trYTY();
@@ -607,8 +608,13 @@ struct TrmfSessionImpl : SessionXPhase {
         return t;
     }
     std::string describe_lag() const {
-        if (!lag_lasso()) return "; lag penalty: ridge";
         char t[96];
+        if (!lag_lasso()) {
+            if (nlag == 0) return "; lag penalty: ridge";
+            if (const int cls = theta_reg_class()) snprintf(t, sizeof t, "; lag penalty: ridge (solve in registers, class %d)", cls);
+            else snprintf(t, sizeof t, "; lag penalty: ridge (solve in %s)", theta_scratch.p ? "global scratch" : "LDS");
+            return t;
+        }
         snprintf(t, sizeof t, "; lag penalty: lasso l1=%g refit=%d", lambdaLagL1, lag_refit);
         return t;
     }

@@ -259,6 +259,7 @@ struct SessionState {
     hipStream_t aux_theta = nullptr;
     hipEvent_t theta_fork = nullptr, theta_done = nullptr;
     bool theta_pending = false;
+    bool theta_force_lds = false;             // TRMF_THETA_SOLVE=lds (a test knob, read at create): the LDS form of the ridge solve for every |L|
     // ---- sparse lag weights (trmf_session_set_lag_penalty; theta_kernels.hpp: theta_lasso_kernel) ------------------------------
     // lambdaLagL1 > 0 or lag_refit: the Theta-solve is theta_gram_kernel + theta_lasso_kernel (warm-started from the current
     // Theta, which is part of mark / rewind); both zero: today's ridge kernels, nothing else launched.  The fp64 systems of a lag

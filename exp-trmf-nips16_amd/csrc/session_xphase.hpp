@@ -626,7 +626,7 @@ struct SessionXPhase : SessionFPhase {
     }
 
     // ---- Theta solve (trmf.cpp:677-689 -> 455-484) ------------------------------------------------------
-    size_t theta_gram_lds() const { return theta_gram_lds_bytes(midx); }
+    size_t theta_gram_lds() const { return theta_gram_lds_bytes(midx, nlag); }
     size_t theta_solve_lds() const { return (size_t)(nlag * nlag + nlag) * sizeof(real); }
     size_t theta_lasso_lds() const { return theta_lasso_doubles(nlag) * sizeof(double); }
     // buffers of the lasso solve, on first use: the record table and -- where the fp64 system does not fit LDS -- the scratch
@@ -641,6 +641,13 @@ struct SessionXPhase : SessionFPhase {
             return 0;
         }
         return allow_dyn_lds(theta_lasso_kernel<false>, theta_lasso_lds(), "lasso Theta solve");
+    }
+    // The ridge solve's form: |L| <= kThetaRegMax -> the system in the registers of one wavefront (theta_solve_reg_kernel, by rank
+    // class 8 / 16 / 32), longer lag sets -> 0: theta_solve_kernel (LDS, global scratch beyond that).  theta_force_lds (the test knob
+    // TRMF_THETA_SOLVE=lds) keeps the LDS form for every |L|, so that a test can hold the two against each other: same bits.
+    int theta_reg_class() const {
+        if (nlag == 0 || nlag > kThetaRegMax || theta_force_lds) return 0;
+        return nlag <= 8 ? 8 : nlag <= 16 ? 16 : 32;
     }
     int theta_solve(hipStream_t stream) {
         if (nlag == 0) return 0;
@@ -661,6 +668,14 @@ struct SessionXPhase : SessionFPhase {
             return 0;
         }
         lag_rec_valid = false;
+        if (const int cls = theta_reg_class()) {
+            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(k), dim3(256), 0, stream, theta_part.p, nchunk, nlag, npairs, lambdaLag, theta.p); };
+            if (cls == 8) go(theta_solve_reg_kernel<8>);
+            else if (cls == 16) go(theta_solve_reg_kernel<16>);
+            else go(theta_solve_reg_kernel<32>);
+            TRMF_HIP_CHECK(hipGetLastError());
+            return 0;
+        }
         const size_t lds2 = theta_scratch.p ? 0 : theta_solve_lds();
         hipLaunchKernelGGL(theta_solve_kernel, dim3(k), dim3(256), lds2, stream, theta_part.p, nchunk, nlag,
                            npairs, lambdaLag, theta.p, theta_scratch.p);

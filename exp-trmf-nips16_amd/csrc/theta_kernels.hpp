@@ -23,16 +23,32 @@ __device__ __forceinline__ void theta_decode_pair(int p, int nlag, int &a, int &
     a = row; b = row + q;
 }
 
-// grid (k, nchunk), 256 threads, dynamic LDS = theta_gram_lds_bytes(midx).
+// grid (k, nchunk), 256 threads, dynamic LDS = theta_gram_lds_bytes(midx, nlag).
 // Register tiling: a thread owns a 4 x 4 block of lag pairs (a in ta, b in tb, tb >= ta; the "zero lag" series s_i
 // against a block of four lags for the right-hand side) and, when there are fewer blocks than threads, one of S time
 // slices of the chunk -- per timestamp it reads 8 series values from LDS for 16 products (0.5 reads per product instead
 // of 2).  Products are rounded to val_type, sums are double (trmf.cpp:447-453); the S slice sums of a block are added
-// in fixed order through LDS.
+// in fixed order through LDS.  The lag set is staged in LDS beside the series.
 constexpr int kThetaTile = 4;
 constexpr int kThetaRows = 4;     // consecutive timestamps per pass of the sliding-window path
-__host__ __device__ inline size_t theta_gram_lds_bytes(int midx) {
-    return ((size_t)(kThetaChunk + midx + kThetaRows) * sizeof(real) + 15) / 16 * 16 + (size_t)256 * 16 * sizeof(double);   // + window slack
+// Slice sums in LDS: entry e of thread x at red[e * kThetaRedStride + x].  Neighbouring lanes store neighbouring doubles (thread-major
+// rows of 16 doubles put every second lane of a store on the same banks); the odd stride keeps the 16 entries of a block, which the
+// closing reduction reads side by side, on different banks (the blocks of a wavefront, S doubles apart, may still share some).
+constexpr int kThetaRedStride = 257;
+__host__ __device__ inline size_t theta_gram_series_bytes(int midx) {
+    return ((size_t)(kThetaChunk + midx + kThetaRows) * sizeof(real) + 15) / 16 * 16;   // + window slack
+}
+__host__ __device__ inline size_t theta_gram_lds_bytes(int midx, int nlag) {        // series | red | blocks of a pass | lag set
+    return theta_gram_series_bytes(midx) + (size_t)16 * kThetaRedStride * sizeof(double) + (size_t)(256 + nlag) * sizeof(int);
+}
+// block q of the row-major upper triangle of NA x NA blocks (row r starts at r NA - r (r - 1) / 2) -> (row, column).  The root is
+// taken of an integer that fp32 holds exactly ((2 NA + 1)^2 <= 2^24 up to kMaxLags), so the estimate is off by one row at most.
+__device__ __forceinline__ void theta_decode_tile(int q, int NA, int &ta, int &tb) {
+    const float h = (float)(2 * NA + 1);
+    int r = min(NA - 1, max(0, (int)((h - sqrtf(h * h - 8.0f * (float)q)) * 0.5f)));
+    while (r > 0 && r * NA - r * (r - 1) / 2 > q) r--;
+    while ((r + 1) * NA - (r + 1) * r / 2 <= q) r++;
+    ta = r; tb = r + (q - (r * NA - r * (r - 1) / 2));
 }
 __global__ __launch_bounds__(256) void theta_gram_kernel(const real *__restrict__ W, int T, int KP,
                                                          const uint32_t *__restrict__ lag_set,
@@ -40,16 +56,26 @@ __global__ __launch_bounds__(256) void theta_gram_kernel(const real *__restrict_
                                                          double *__restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     real *series = reinterpret_cast<real *>(smem_raw);
-    double *red = reinterpret_cast<double *>(smem_raw + (((size_t)(kThetaChunk + midx + kThetaRows) * sizeof(real) + 15) / 16 * 16));
+    double *red = reinterpret_cast<double *>(smem_raw + theta_gram_series_bytes(midx));
+    int *blocks = reinterpret_cast<int *>(red + 16 * kThetaRedStride);     // (row | column << 16) of the blocks of a pass, for its closing reduction
+    int *lags = blocks + 256;
     const int t = blockIdx.x, ch = blockIdx.y, nchunk = gridDim.y;
     const int i0 = midx + ch * kThetaChunk;
     const int i1 = min(T, i0 + kThetaChunk);
     const int lo = i0 - midx;                           // first timestamp staged
     const int tp = colpos(t, KP / kTile);                 // column-interleaved factor layout
-    for (int i = lo + threadIdx.x; i < i1; i += 256) series[i - lo] = W[(size_t)i * KP + tp];
+    for (int i = threadIdx.x; i < nlag; i += 256) lags[i] = (int)lag_set[i];
+    for (int i = lo + threadIdx.x; i < i1; i += 4 * 256) {      // four loads of a thread in flight
+        real w[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) w[u] = i + u * 256 < i1 ? W[(size_t)(i + u * 256) * KP + tp] : real(0);
+#pragma unroll
+        for (int u = 0; u < 4; u++) if (i + u * 256 < i1) series[i + u * 256 - lo] = w[u];
+    }
     __syncthreads();
     const int NA = (nlag + kThetaTile - 1) / kThetaTile;
-    const int ntiles = NA * (NA + 1) / 2 + NA;          // upper-triangle blocks, then the rhs blocks
+    const int ntri = NA * (NA + 1) / 2;
+    const int ntiles = ntri + NA;                       // upper-triangle blocks, then the rhs blocks
     const int S = max(1, 256 / ntiles);                 // time slices per block of pairs
     double *out = part + ((size_t)t * nchunk + ch) * npairs;
     for (int base = 0; base < ntiles; base += 256 / S) {
@@ -58,14 +84,14 @@ __global__ __launch_bounds__(256) void theta_gram_kernel(const real *__restrict_
         int ta = 0, tb = 0;
         bool rhs = false;
         if (live) {
-            if (tile >= NA * (NA + 1) / 2) { rhs = true; tb = tile - NA * (NA + 1) / 2; }
-            else { int q = tile, len = NA; while (q >= len) { q -= len; ta++; len--; } tb = ta + q; }
+            if (tile >= ntri) { rhs = true; tb = tile - ntri; }
+            else theta_decode_tile(tile, NA, ta, tb);
         }
         int la[kThetaTile], lb[kThetaTile];
 #pragma unroll
         for (int u = 0; u < kThetaTile; u++) {
-            la[u] = rhs ? 0 : (int)lag_set[min(kThetaTile * ta + u, nlag - 1)];
-            lb[u] = (int)lag_set[min(kThetaTile * tb + u, nlag - 1)];
+            la[u] = rhs ? 0 : lags[min(kThetaTile * ta + u, nlag - 1)];
+            lb[u] = lags[min(kThetaTile * tb + u, nlag - 1)];
         }
         double acc[kThetaTile][kThetaTile];
 #pragma unroll
@@ -119,26 +145,29 @@ __global__ __launch_bounds__(256) void theta_gram_kernel(const real *__restrict_
                     }
             }
         }
-        // slice sums -> LDS -> the slice-0 thread of a block adds them in order and stores the block's pairs
+        // slice sums -> LDS -> sixteen threads per block, one per entry, add the S slice sums of their entry in slice order
+        // (from 0.0, ascending: the order is part of the result) and store the block's pairs
         __syncthreads();
 #pragma unroll
         for (int u = 0; u < kThetaTile; u++)
 #pragma unroll
-            for (int v = 0; v < kThetaTile; v++) red[(size_t)threadIdx.x * 16 + u * kThetaTile + v] = acc[u][v];
+            for (int v = 0; v < kThetaTile; v++) red[(u * kThetaTile + v) * kThetaRedStride + (int)threadIdx.x] = acc[u][v];
+        if (live && slice == 0) blocks[tile - base] = ta | (tb << 16);
         __syncthreads();
-        if (live && slice == 0) {
-#pragma unroll
-            for (int u = 0; u < kThetaTile; u++)
-#pragma unroll
-                for (int v = 0; v < kThetaTile; v++) {
-                    const int a = kThetaTile * ta + u, b = kThetaTile * tb + v;
-                    if (b >= nlag || (!rhs && (a >= nlag || a > b)) || (rhs && u > 0)) continue;
-                    double sum = 0;
-                    for (int sl = 0; sl < S; sl++) sum += red[(size_t)(threadIdx.x + sl) * 16 + u * kThetaTile + v];
-                    // pair index: p < nlag -> rhs entry y[b]; otherwise upper-triangle (a, b) in row-major order
-                    const int p = rhs ? b : nlag + a * nlag - a * (a - 1) / 2 + (b - a);
-                    out[p] = sum;
-                }
+        for (int o = threadIdx.x; o < (256 / S) * 16; o += 256) {
+            const int tl = o >> 4, e = o & 15, rt = base + tl;
+            if (rt >= ntiles) break;
+            const int u = e / kThetaTile, v = e % kThetaTile;
+            const bool rr = rt >= ntri;                 // a rhs block
+            const int ra = blocks[tl] & 0xffff, rb = blocks[tl] >> 16;
+            const int a = kThetaTile * ra + u, b = kThetaTile * rb + v;
+            if (b >= nlag || (!rr && (a >= nlag || a > b)) || (rr && u > 0)) continue;
+            const double *src = red + e * kThetaRedStride + tl * S;
+            double sum = 0;
+            for (int sl = 0; sl < S; sl++) sum += src[sl];
+            // pair index: p < nlag -> rhs entry y[b]; otherwise upper-triangle (a, b) in row-major order
+            const int p = rr ? b : nlag + a * nlag - a * (a - 1) / 2 + (b - a);
+            out[p] = sum;
         }
     }
 }
@@ -150,6 +179,10 @@ __device__ __forceinline__ double theta_sum_pair(const double *__restrict__ part
     for (int ch = 0; ch < nchunk; ch++) acc += part[((size_t)t * nchunk + ch) * npairs + p];   // fixed order
     return acc;
 }
+
+// a - u c of the Cholesky's trailing update and of the substitutions, as ONE fused multiply-add: what the compiler made of the
+// plain expression in theta_chol_solve (fp contraction), written out so that the LDS form and the register form cannot drift apart.
+template <typename E> __device__ __forceinline__ E theta_nmsub(E a, E u, E c) { return fma(-u, c, a); }
 
 // A x = y for the symmetric positive definite n x n system A ((i,j) at A[i*n+j], upper triangle read), x left in y; one wavefront
 // (lane = 0..63), LDS or -- with the workgroup barriers ordering the accesses -- global scratch.  CHECK: a pivot that is not
@@ -173,9 +206,9 @@ template <typename E, bool CHECK> __device__ __forceinline__ bool theta_chol_sol
 #pragma unroll
                 for (int q = 0; q < 4; q++) { u[q] = A[j * nlag + s + q]; a[q] = A[(s + q) * nlag + c]; }
 #pragma unroll
-                for (int q = 0; q < 4; q++) A[(s + q) * nlag + c] = a[q] - u[q] * ujc;
+                for (int q = 0; q < 4; q++) A[(s + q) * nlag + c] = theta_nmsub(a[q], u[q], ujc);
             }
-            for (; s <= c; s++) A[s * nlag + c] -= A[j * nlag + s] * ujc;
+            for (; s <= c; s++) A[s * nlag + c] = theta_nmsub(A[s * nlag + c], A[j * nlag + s], ujc);
         }
         __syncthreads();
     }
@@ -186,13 +219,13 @@ template <typename E, bool CHECK> __device__ __forceinline__ bool theta_chol_sol
     for (int q = 0; q < nlag; q++) {                    // U^T z = y
         if (lane == 0) y[q] = y[q] / A[q * nlag + q];
         __syncthreads();
-        for (int i = q + 1 + lane; i < nlag; i += 64) y[i] -= A[q * nlag + i] * y[q];
+        for (int i = q + 1 + lane; i < nlag; i += 64) y[i] = theta_nmsub(y[i], A[q * nlag + i], y[q]);
         __syncthreads();
     }
     for (int q = nlag - 1; q >= 0; q--) {               // U x = z
         if (lane == 0) y[q] = y[q] / A[q * nlag + q];
         __syncthreads();
-        for (int i = lane; i < q; i += 64) y[i] -= A[i * nlag + q] * y[q];
+        for (int i = lane; i < q; i += 64) y[i] = theta_nmsub(y[i], A[i * nlag + q], y[q]);
         __syncthreads();
     }
     return true;
@@ -226,6 +259,91 @@ __global__ __launch_bounds__(256) void theta_solve_kernel(const double *__restri
     if (threadIdx.x >= 64) return;                      // the barriers below only count the wavefront that is left
     theta_chol_solve<real, false>(A, y, nlag, lane);
     for (int a = lane; a < nlag; a += 64) theta[(size_t)t * nlag + a] = y[a];
+}
+
+// ---- the register form of the ridge solve: |L| <= kThetaRegMax ------------------------------------------------------------------
+// One wavefront holds the system: lane c owns column c, row s is register col[s] (statically indexed, N = the rank class >= |L|),
+// the right-hand side is one value per lane.  Pivots and row values travel by v_readlane; there is no LDS access and no barrier in
+// the factorisation or the substitutions.  Every element of the upper triangle and of y receives the operations of
+// theta_chol_solve in its order: sqrt and true division on row j, the trailing updates in ascending pivot order, the forward
+// substitution's terms in ascending q, the backward's in descending q.  What lies below the diagonal (and in lanes >= |L|) is
+// updated along with the rest and never read.
+constexpr int kThetaRegMax = 32;
+__device__ __forceinline__ float theta_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+__device__ __forceinline__ double theta_lane(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+template <typename E, int N> __device__ __forceinline__ E theta_chol_solve_reg(E (&col)[N], E yv, int nlag, int lane) {
+#pragma unroll
+    for (int j = 0; j < N; j++)
+        if (j < nlag) {                                 // (wave-uniform)
+            const E ajj = sqrt(theta_lane(col[j], j));
+            col[j] = lane == j ? ajj : col[j] / ajj;
+            const E ujc = col[j];
+#pragma unroll
+            for (int s = j + 1; s < N; s++) col[s] = theta_nmsub(col[s], theta_lane(ujc, s), ujc);
+        }
+#pragma unroll
+    for (int q = 0; q < N; q++)                         // U^T z = y: lane i keeps y[i]
+        if (q < nlag) {
+            const E zq = theta_lane(yv, q) / theta_lane(col[q], q);
+            yv = lane == q ? zq : lane > q ? theta_nmsub(yv, col[q], zq) : yv;
+        }
+    // U x = z: U(i,q) is register i of lane q, so the unknowns are kept in every lane (x[i], wave-uniform) and row q's column
+    // arrives by N readlanes
+    E x[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) x[i] = theta_lane(yv, i);
+#pragma unroll
+    for (int q = N - 1; q >= 0; q--)
+        if (q < nlag) {
+            x[q] = x[q] / theta_lane(col[q], q);
+#pragma unroll
+            for (int i = 0; i < q; i++) x[i] = theta_nmsub(x[i], theta_lane(col[i], q), x[q]);
+        }
+    E out = E(0);
+#pragma unroll
+    for (int i = 0; i < N; i++) out = lane == i ? x[i] : out;
+    return out;
+}
+
+// theta_sum_pair with the chunk partials of a pair requested 32 at a time before the first add (same adds, same order)
+__device__ __forceinline__ double theta_sum_pair_wide(const double *__restrict__ part, int nchunk, int npairs, int t, int p) {
+    double acc = 0;
+    for (int c0 = 0; c0 < nchunk; c0 += 32) {
+        double v[32];
+#pragma unroll
+        for (int u = 0; u < 32; u++) v[u] = c0 + u < nchunk ? part[((size_t)t * nchunk + c0 + u) * npairs + p] : 0.0;
+#pragma unroll
+        for (int u = 0; u < 32; u++) if (c0 + u < nchunk) acc += v[u];                          // fixed order
+    }
+    return acc;
+}
+
+// one workgroup per latent dimension, static LDS: the packed pairs.  All 256 threads add up the chunk partials; one wavefront
+// then loads its columns (rounding to `real`, then lambdaLag on the diagonal: trmf.cpp:473, 480) and solves in registers.
+template <int N>
+__global__ __launch_bounds__(256) void theta_solve_reg_kernel(const double *__restrict__ part, int nchunk, int nlag, int npairs,
+                                                             double lambdaLag, real *__restrict__ theta) {
+    __shared__ real sm[N * (N + 1) / 2 + N];
+    const int t = blockIdx.x, lane = threadIdx.x;
+    for (int p = threadIdx.x; p < npairs; p += 256) sm[p] = (real)theta_sum_pair_wide(part, nchunk, npairs, t, p);
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    real col[N];
+#pragma unroll
+    for (int s = 0; s < N; s++) {
+        real v = real(0);
+        if (s < nlag && lane < nlag) {
+            const int a = min(s, lane), b = max(s, lane);
+            v = sm[nlag + a * nlag - a * (a - 1) / 2 + (b - a)];
+            if (s == lane) v = (real)((double)v + lambdaLag);
+        }
+        col[s] = v;
+    }
+    const real yv = lane < nlag ? sm[lane] : real(0);
+    const real x = theta_chol_solve_reg<real, N>(col, yv, nlag, lane);
+    if (lane < nlag) theta[(size_t)t * nlag + lane] = x;
 }
 
 // ---- sparse lag weights: L1-penalised Theta-solve (the reference's MATLAB trainer, do_lasso; no counterpart in trmf.cpp) ----------

@@ -128,7 +128,8 @@ def outer(args):
                     sys.executable, me, '--inner', 'kernels', '--meta', kmeta] + common, check=True, timeout=1100)
     rows = _trace_rows(os.path.join(work, 'trace'))
     us = lambda key: [(e - s) / 1e3 for s, e, name in rows if key in name]
-    ridge, lasso, gram = us('theta_solve_kernel'), us('theta_lasso_kernel'), us('theta_gram_kernel')
+    # 'theta_solve_': theta_solve_kernel or theta_solve_reg_kernel<N>, one per ridge solve
+    ridge, lasso, gram = us('theta_solve_'), us('theta_lasso_kernel'), us('theta_gram_kernel')
     result = {'device': 'MI355X', 'cases': []}
     rp = lp = gp = 0
     for c in json.load(open(kmeta))['cases']:
