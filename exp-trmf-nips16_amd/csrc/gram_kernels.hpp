@@ -176,9 +176,10 @@ template <int NT> __host__ __device__ constexpr bool rhs_pad_ok(int k) { return 
 // added to the lane's column bytes in a single v_add_u32_dpp per group (rounds 1-3: a DPP move + a
 // multiply-add per group; before that a 64-bit multiply-add per row).  Factor tables are therefore limited to 4 GiB.
 // 15 vector instructions per iteration beside the 24 MFMAs at three column tiles (27 until round 4).
-// One load PER ELEMENT of the lane's slice (same descriptor, same lane offset, immediate offsets): a single
-// multi-dword load would force its destination into a register tuple, and the allocator then copies the
-// tuple's elements into the MFMA operand registers right after the load -- i.e. waits for it at once.
+// Written as one load PER ELEMENT of the lane's slice (same descriptor, same lane offset, immediate offsets); the
+// compiler merges them into the widest loads that cover the slice (fp32: one buffer_load_dword / x2 / x3 / x4 for
+// NT = 1..4, fp64: x2, x4, x4 + x2, x4 + x4) and the MFMAs read the tuple's registers directly as operands -- no copy
+// follows the load, so a slot costs one (fp64, NT >= 3: two) vmcnt ticket(s) and the waits count whole slots.
 template <int NT, typename R>
 __device__ __forceinline__ void load_factor_slice(R (&dst)[NT], __amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off) {
 #pragma unroll
@@ -192,9 +193,13 @@ __device__ __forceinline__ void load_factor_slice(R (&dst)[NT], __amdgpu_buffer_
 
 // TAIL (single-row streams with estride == 4 only: group u of an iteration is entries e0 + 4u .. e0 + 4u + 3): the last
 // iteration of the row runs after the loop and issues the arithmetic of the groups that hold entries only.  The loop
-// body stays one basic block (a branch inside it costs the exact waits); behind the loop nothing
+// body stays one basic block (fp64: two vmcnt tickets per slot at NT >= 3, and nothing to gain inside the loop); behind the loop nothing
 // is in flight that a conservative wait could delay.  Skipped groups are all-zero operands: the sums are unchanged.
-template <int NT, int D, bool DO_MMA, bool WITH_LOSS, bool RHS_PAD = false, bool TAIL = false, typename Next, typename RowDone>
+// ROWEND (estride == 4 as well; multi-row streams, whose row ends lie INSIDE the loop): groups 1..3 of an iteration sit behind a
+// wave-uniform compare each and are skipped when the row has no entry for them; the loads are issued on both sides of every
+// branch in the same order, so the counted waits survive (one per group, each in its group's block).  Costs three registers
+// and a scalar compare + branch per group; quad_row_end() names the instantiations that take it.
+template <int NT, int D, bool DO_MMA, bool WITH_LOSS, bool RHS_PAD = false, bool TAIL = false, bool ROWEND = false, typename Next, typename RowDone>
 __device__ __forceinline__ void gram_ring(GramState<NT> &st, const uint32_t *__restrict__ idx,
                                           const real *__restrict__ val, const real *__restrict__ X,
                                           uint32_t zero_row, uint32_t estride, int lane,
@@ -249,8 +254,19 @@ __device__ __forceinline__ void gram_ring(GramState<NT> &st, const uint32_t *__r
     // entries loaded one iteration ago) is then "all but the four slice loads behind them" on both paths into the loop
     // header.  With the entries requested last here (rounds 1-3) the wait merged over both paths was vmcnt(0): every
     // iteration drained the four gathers it had just issued, and a wavefront's ring only overlapped with OTHER wavefronts.
-    load_entries(d1);
-    static_for<D>([&](auto U) { load_slices(U, x, yx); });
+    // The source order alone does not hold: the instruction scheduler moved the slice loads above the entry loads in every
+    // F-solve kernel and in loss_kernel (same merged vmcnt(0); scripts/check_ring_waits.py), hence the two barriers.  With TAIL
+    // the loop may not run at all, and the compiler then sinks the entry loads out of this block into the loop's preheader,
+    // again behind the slices; so a row of one iteration takes a branch of its own here (its d1 has no entries: nothing to
+    // request) and the loop's preheader is the block that holds both requests, in the loop body's order.
+    if (TAIL && d1.row < 0) {
+        static_for<D>([&](auto U) { load_slices(U, x, yx); });
+    } else {
+        load_entries(d1);
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<D>([&](auto U) { load_slices(U, x, yx); });
+        __builtin_amdgcn_sched_barrier(0);
+    }
     // Slot u is consumed (its MFMAs and rhs FMAs issued) and then immediately re-requested for the next
     // iteration, in place: every load still has a full iteration of MFMA time (24 x 32 cycles) to land, and
     // there is no second operand set to copy into (12 + 4 register moves per iteration that the shared
@@ -282,12 +298,14 @@ __device__ __forceinline__ void gram_ring(GramState<NT> &st, const uint32_t *__r
         }
     };
     while (TAIL ? d1.row >= 0 : d0.row >= 0) {
-        // ---- single basic block ----
+        // ---- single basic block (ROWEND: one block per group) ----
         const real ycons = ysel;                         // y of the iteration being consumed (RHS_PAD)
         promote_entries();                               // entries of n+1 (loaded one iteration ago)
         load_entries(d2);                                // entries of n+2
+        const uint32_t left = ROWEND ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(d0.end - d0.e0)) : 0u;   // entries of the row from this iteration on
         static_for<D>([&](auto U) {
-            consume(U, ycons);
+            constexpr uint32_t u = (uint32_t)decltype(U)::value;
+            if (!ROWEND || u == 0 || left > 4u * u) consume(U, ycons);
             // pin the order "all of group u's arithmetic, then its reload": left alone, the scheduler moves the
             // reload above MFMAs that still read the slot, renames it and waits for the fresh load at once
             __builtin_amdgcn_sched_barrier(0);
@@ -783,6 +801,11 @@ constexpr int kQuadWaves = 3;
 // <4,64> instantiations spilled 296 / 460 bytes per lane; they are built for two wavefronts per SIMD instead.
 // (profiles/r04_fsolve_k64_fp32.txt has the comparison).
 constexpr int quad_waves(int NT) { return NT >= 4 ? 2 : kQuadWaves; }
+// Row ends at group granularity (gram_ring ROWEND) instead of whole 16-entry iterations: at config 3 (rows of ~100 entries) 642 -> ~609
+// Gram MFMAs per wavefront.  Taken by the instantiations where it costs neither scratch nor a wavefront per SIMD AND was measured
+// to pay (profiles/ring_waits.txt): <3,48> and <4,64> spill with it (388 / 676 bytes per lane), <2,24> loses a wavefront (80 -> 83
+// registers); the others have no workload to measure them on and stay as they were.
+constexpr bool quad_row_end(int NT, int KMAX) { return (NT == 3 && KMAX == 40) || (NT == 4 && KMAX == 56); }
 #if !defined(TRMF_UNIT_BODIES)     // the main translation unit sees the declaration only (kernel_units.hpp)
 template <int NT, int KMAX>
 __global__ void fsolve_quad_kernel(const uint32_t *__restrict__ ptr,
@@ -896,7 +919,7 @@ __device__ __forceinline__ void fsolve_quad_body(const uint32_t *__restrict__ pt
         float nowq[NT];
 #pragma unroll
         for (int q = 0; q < NT; q++) nowq[q] = 0;
-        gram_ring<NT, kRingDepth, true, false, PAD>(st, idx, val, X, zero_row, 4u, lane, nowq, stream.first(), stream,
+        gram_ring<NT, kRingDepth, true, false, PAD, false, quad_row_end(NT, KMAX)>(st, idx, val, X, zero_row, 4u, lane, nowq, stream.first(), stream,
                                                     finalize);
     }
 
