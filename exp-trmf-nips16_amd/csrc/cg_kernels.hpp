@@ -131,6 +131,97 @@ __device__ __forceinline__ bool cg_stopped(real rho, real cgtol) {           // 
     return sqrt((double)rho) <= (double)cgtol;
 }
 
+// ---- the scalars of a TRON step ---------------------------------------------------------------------
+// The X-solve has three forms (cg_persist_kernel; hv_tile_kernel + cg_close_kernel + accept_tile_kernel; cg_init_kernel +
+// ar_tile_kernel<AR_CG_STEP> + wnew_kernel + accept_kernel) whose vector work differs and whose scalar arithmetic must not:
+// it is defined here, once, as functions of the fixed-order sums each form has made.  Every cast and every operand order
+// below decides last bits (the library is built with the compiler's default contraction).
+//
+// Start: f, |g|, the CG tolerance and the iteration-0 stop from the gradient's sums (rf_tron.h:154-169, 424-439).
+struct TronStart { double f, gnorm; real ggr, cgtol; bool stopped; };
+__device__ __forceinline__ TronStart tron_start(const XParams &p, double ar2, double vv, double gg, double lq) {
+    TronStart t;
+    t.ggr = (real)gg;                                                        // BLAS dot in val_type; rho[0] = r^T r = g^T g (rf_tron.h:439)
+    t.gnorm = sqrt((double)t.ggr);
+    t.cgtol = (real)(p.eps_cg * t.gnorm);                                    // rf_tron.h:434
+    t.stopped = cg_stopped(t.ggr, t.cgtol);
+    // loss = sum y^2 + sum_i (w_i^T G_i w_i - 2 b_i.w_i): the reference's own formula on the full path (trmf.cpp:189-197); on
+    // the observed-entries path the same identity over the cached Grams replaces its pass over the residuals
+    // (trmf.cpp:231-245) -- f only feeds the TRON line, not the iterates
+    double f = 0.5 * (p.trYTY + lq);
+    if (p.lambdaI > 0) f += 0.5 * p.lambdaI * (double)(real)vv;              // trmf.cpp:73-75
+    if (p.nlag > 0 && p.lambdaAR > 0) f += 0.5 * p.lambdaAR * ar2;           // trmf.cpp:94
+    t.f = f;
+    return t;
+}
+// ... as the launch-per-step forms leave it in XState for their later launches
+__device__ __forceinline__ void tron_start_record(XState *st, const TronStart &t) {
+    st->f = t.f; st->fnew = t.f; st->gnorm = t.gnorm; st->cgtol = t.cgtol; st->cg_rnorm = t.gnorm;
+    st->cg_iter = t.stopped ? 0 : 1;                // iterations the CG is committed to so far (launch `it` raises it to it + 1)
+    st->accepted = 0; st->rho_hist[0] = (double)t.ggr;
+    st->stop_it = t.stopped ? 0 : kCgRunning; st->r_parity = 0;
+}
+// CG step `it` >= 1 from the three dot products of iteration it - 1: alpha, r^T r of the new residual by the recurrence
+// rho' = rho - 2 alpha <r,Hd> + alpha^2 <Hd,Hd>, the stop test at the top of iteration `it` (or `last`: the iteration cap) and
+// tmp = beta - 1 of the direction update d = d + tmp d + r.
+struct CgStep { real alpha, tmp; double rho_d; bool stopped; };
+__device__ __forceinline__ CgStep cg_step_scalars(double rho_prev_d, double dHd, double rHd, double HH, real cgtol, bool last) {
+    CgStep c;
+    const real rho_prev = (real)rho_prev_d;
+    c.alpha = rho_prev / (real)dHd;                                          // rf_tron.h:460
+    const double ad = (double)c.alpha;
+    c.rho_d = fmax(rho_prev_d - 2.0 * ad * rHd + ad * ad * HH, 0.0);         // |r - alpha Hd|^2
+    const real rho = (real)c.rho_d;
+    c.stopped = last || cg_stopped(rho, cgtol);                              // rf_tron.h:444-446
+    const real beta = rho / rho_prev;                                        // rf_tron.h:495
+    c.tmp = beta - (real)1.0;                                                // rf_tron.h:497
+    return c;
+}
+// ... recorded by one thread of launch `it`: a stop as the iteration index (see the head of this file)
+__device__ __forceinline__ void cg_step_record(XState *st, int it, const CgStep &c) {
+    st->rho_hist[it] = c.rho_d;
+    if (c.stopped) { st->stop_it = it; st->r_parity = it & 1; }
+    else st->cg_iter = it + 1;                                               // nobody reads cg_iter during the solve
+}
+// Acceptance test (rf_tron.h:186-229) from <g,s>, <s,r>, <s,s> of the closed step.  The X sub-problem is exactly quadratic, so
+// f(w) - f(w + s) = -(g.s + 1/2 s.Hs), and the CG's own recurrence r = -g - H s gives s.Hs = -s.(g + r): the reduction IS the
+// reference's prered = -1/2 (g.s - s.r), without its second pass over the observations (rf_tron.h:191 -> trmf.cpp:231-245) and
+// without an operator pass of our own.  direct (diagnostics, SessionState::cg_direct): s.Hs from one more operator pass, sHs.
+// Every thread of every workgroup evaluates this (the decision commits w).
+struct TronAccept { double gs, sr, snorm, prered, actred, fnew; bool accept; };
+__device__ __forceinline__ TronAccept tron_accept(double f, double gs_d, double sr_d, double ss_d, double sHs, bool direct) {
+    const double gs = (double)(real)gs_d, sr = (double)(real)sr_d;          // BLAS dots in val_type (rf_tron.h:186-187)
+    const double snorm = sqrt((double)(real)ss_d);
+    const double prered = -0.5 * (gs - sr);                                  // rf_tron.h:190
+    const double actred = direct ? -(gs + 0.5 * sHs) : prered;
+    const double fnew = f - actred;
+    return TronAccept{gs, sr, snorm, prered, actred, fnew, actred > 1e-4 * prered};   // eta0, rf_tron.h:222
+}
+// The TRON line of a solve, by the ONE thread that records it: into the session's XState and, if there is one, the iteration
+// record of the log (its ||.||^2 entries are off in this mode) -- written here, no copies on the stream.  rho: r^T r of the last
+// completed CG iteration.  delta: the trust-region bound the reference prints (rf_tron.h:195-215; it never constrains the step
+// here: the folded parameters of trmf.cpp:603-606 run a pure CG pass): delta0 = |g|, first iteration min(delta, |s|), then the
+// update by actred / prered.  (In the accept kernels of the launch-per-step forms f, gnorm, cgtol and cg_iter come from *st and
+// go back there with the same bits, while other workgroups read them.)
+__device__ __forceinline__ void tron_record(XState *st, XState *log_x, double *log_norms, double f, double gnorm, real cgtol, int cg_iter,
+                                            double rho, double rho_direct, const TronAccept &t) {
+    double delta = fmin(gnorm, t.snorm);
+    const double curv = t.fnew - f - t.gs;
+    const double alpha = curv <= 0 ? 4.0 : fmax(0.25, -0.5 * (t.gs / curv));
+    if (t.actred < 1e-4 * t.prered) delta = fmin(fmax(alpha, 0.25) * t.snorm, 0.5 * delta);
+    else if (t.actred < 0.25 * t.prered) delta = fmax(0.25 * delta, fmin(alpha * t.snorm, 0.5 * delta));
+    else if (t.actred < 0.75 * t.prered) delta = fmax(0.25 * delta, fmin(alpha * t.snorm, 4.0 * delta));
+    else delta = fmax(delta, fmin(alpha * t.snorm, 4.0 * delta));
+    const double cg_rnorm = sqrt((double)(real)rho);
+    auto put = [&](XState *x) {
+        x->f = f; x->fnew = t.fnew; x->gnorm = gnorm; x->cg_rnorm = cg_rnorm;
+        x->actred = t.actred; x->prered = t.prered; x->gs = t.gs; x->sr = t.sr;
+        x->cgtol = cgtol; x->cg_iter = cg_iter; x->accepted = t.accept ? 1 : 0; x->delta = delta; x->rho_direct = rho_direct;
+    };
+    put(st);
+    if (log_x) { put(log_x); log_norms[0] = log_norms[1] = log_norms[2] = -1.0; }
+}
+
 // ---- single-block reduction of a per-row array into a scalar ----------------------------------------
 #if !defined(TRMF_UNIT)      // compiled by the main translation unit only (kernel_units.hpp)
 __global__ __launch_bounds__(256) void reduce_rows_kernel(const double *__restrict__ src, int n,
@@ -298,19 +389,10 @@ __global__ __launch_bounds__(kArThreads) void ar_tile_kernel(XParams p, XState *
         double dHd = pre[0], rHd = pre[1], HH = pre[2];
         for (int i = tid + kArThreads; i < np; i += kArThreads) { dHd += Pp[i]; rHd += Pp[(size_t)p.pstride + i]; HH += Pp[2 * (size_t)p.pstride + i]; }
         block_allsum3_wide(dHd, rHd, HH, smem);
-        const double rho_prev_d = st->rho_hist[it - 1];
-        const real rho_prev = (real)rho_prev_d;
-        alpha = rho_prev / (real)dHd;                                            // rf_tron.h:460
-        nalpha = -alpha;
-        const double ad = (double)alpha;
-        const double rho_d = fmax(rho_prev_d - 2.0 * ad * rHd + ad * ad * HH, 0.0);   // |r - alpha Hd|^2
-        const real rho = (real)rho_d;
-        stopped = last || cg_stopped(rho, st->cgtol);                            // top of iteration `it`, rf_tron.h:444-446
-        tmp = rho / rho_prev - (real)1.0;                                        // rf_tron.h:495-497
+        const CgStep c = cg_step_scalars(st->rho_hist[it - 1], dHd, rHd, HH, st->cgtol, last);
+        alpha = c.alpha; nalpha = -alpha; tmp = c.tmp; stopped = c.stopped;
         if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
-            st->rho_hist[it] = rho_d;
-            if (stopped) { st->stop_it = it; st->r_parity = it & 1; }
-            else st->cg_iter = it + 1;
+            cg_step_record(st, it, c);
             if (a.note) __hip_atomic_store(a.note, (a.note_seq << 8) | ((unsigned int)it << 1) | (stopped ? 1u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
@@ -954,21 +1036,9 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? 2 : 1) void hv_tile_kernel(XParam
         }
         block_allsum3<NTH / 64>(ar2, vv, gg, smem);
         lq = block_allsum<NTH / 64>(lq, smem);
-        const real ggr = (real)gg;                                           // BLAS dot in val_type
-        const double gnorm = sqrt((double)ggr);
-        const real cgtol = (real)(p.eps_cg * gnorm);                         // rf_tron.h:434
-        stopped = cg_stopped(ggr, cgtol);                                    // rho[0] = r^T r = g^T g (rf_tron.h:439)
-        if (blockIdx.x == 0 && tid == 0) {
-            // loss = sum y^2 + sum_i (w_i^T G_i w_i - 2 b_i.w_i): the reference's own formula on the full path
-            // (trmf.cpp:189-197); on the observed-entries path the same identity over the cached Grams
-            double f = 0.5 * (p.trYTY + lq);
-            if (p.lambdaI > 0) f += 0.5 * p.lambdaI * (double)(real)vv;      // trmf.cpp:73-75
-            if (p.nlag > 0 && p.lambdaAR > 0) f += 0.5 * p.lambdaAR * ar2;   // trmf.cpp:94
-            st->f = f; st->fnew = f; st->gnorm = gnorm; st->cgtol = cgtol; st->cg_rnorm = gnorm;
-            st->cg_iter = stopped ? 0 : 1;          // iterations the CG is committed to so far (launch `it` raises it to it + 1)
-            st->accepted = 0; st->rho_hist[0] = (double)ggr;
-            st->stop_it = stopped ? 0 : kCgRunning; st->r_parity = 0;
-        }
+        const TronStart t = tron_start(p, ar2, vv, gg, lq);
+        stopped = t.stopped;
+        if (blockIdx.x == 0 && tid == 0) tron_start_record(st, t);
     }
     // ---- requests, in consumption order (vmcnt retires in order) ----
     // (a) operand rows: the staged rows [i0-midx, i0+TI+midx) are one contiguous range of the vector,
@@ -1067,21 +1137,9 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? 2 : 1) void hv_tile_kernel(XParam
             }
         }
         block_allsum3<NTH / 64>(dHd, rHd, HH, smem);
-        const double rho_prev_d = st->rho_hist[it - 1];
-        const real rho_prev = (real)rho_prev_d;
-        alpha = rho_prev / (real)dHd;                                        // rf_tron.h:460
-        nalpha = -alpha;
-        const double ad = (double)alpha;
-        const double rho_d = fmax(rho_prev_d - 2.0 * ad * rHd + ad * ad * HH, 0.0);   // |r - alpha Hd|^2
-        const real rho = (real)rho_d;
-        stopped = last || cg_stopped(rho, st->cgtol);                        // top of iteration `it`, rf_tron.h:444-446
-        const real beta = rho / rho_prev;                                    // rf_tron.h:495
-        tmp = beta - (real)1.0;                                              // rf_tron.h:497
-        if (blockIdx.x == 0 && tid == 0) {
-            st->rho_hist[it] = rho_d;
-            if (stopped) { st->stop_it = it; st->r_parity = it & 1; }
-            else st->cg_iter = it + 1;                                       // nobody reads cg_iter during the solve
-        }
+        const CgStep c = cg_step_scalars(st->rho_hist[it - 1], dHd, rHd, HH, st->cgtol, last);
+        alpha = c.alpha; nalpha = -alpha; tmp = c.tmp; stopped = c.stopped;
+        if (blockIdx.x == 0 && tid == 0) cg_step_record(st, it, c);
     }
 
     const uint32_t own_n = (uint32_t)((i1 - i0) * KP);
@@ -1326,25 +1384,7 @@ __global__ __launch_bounds__(256) void cg_init_kernel(XParams p, XState *__restr
     const double vv = sum_partials(Pbase + P_VV * (size_t)p.pstride, np_base, smem);
     const double gg = sum_partials(Pbase + P_DOT * (size_t)p.pstride, np_dot, smem);
     const double lq = sum_partials(Pbase + P_LQ * (size_t)p.pstride, np_dot, smem);
-    const real ggr = (real)gg;                                               // BLAS dot in val_type
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        // loss = sum y^2 + sum_i (w_i^T G_i w_i - 2 b_i.w_i): the reference's own formula on the full path
-        // (trmf.cpp:189-197); on the observed-entries path the same identity over the cached Grams replaces its
-        // pass over the residuals (trmf.cpp:231-245) -- f only feeds the TRON line, not the iterates
-        double f = 0.5 * (p.trYTY + lq);
-        if (p.lambdaI > 0) f += 0.5 * p.lambdaI * (double)(real)vv;          // trmf.cpp:73-75
-        if (p.nlag > 0 && p.lambdaAR > 0) f += 0.5 * p.lambdaAR * ar2;       // trmf.cpp:94
-        const double gnorm = sqrt((double)ggr);
-        st->f = f; st->fnew = f; st->gnorm = gnorm;
-        st->cgtol = (real)(p.eps_cg * gnorm);                                // rf_tron.h:434
-        st->cg_rnorm = gnorm;
-        const bool stopped = cg_stopped(ggr, (real)(p.eps_cg * gnorm));
-        st->cg_iter = stopped ? 0 : 1;              // iterations the CG is committed to so far (launch `it` raises it to it + 1)
-        st->accepted = 0;
-        st->rho_hist[0] = (double)ggr;                                       // rho[0] = r^T r = g^T g (rf_tron.h:439)
-        st->stop_it = stopped ? 0 : kCgRunning;
-        st->r_parity = 0;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) tron_start_record(st, tron_start(p, ar2, vv, gg, lq));
     // elements [e_begin, e_end): everything, or a rank's timestamps plus the halo rows whose gradient it has been sent
     for (size_t e = e_begin + (size_t)blockIdx.x * 256 + threadIdx.x; e < e_end; e += (size_t)gridDim.x * 256) {
         const real gv = g[e];
@@ -1382,12 +1422,10 @@ __global__ __launch_bounds__(256) void wnew_kernel(XParams p, const XState *__re
 }
 #endif
 
-// ---- acceptance test and commit (rf_tron.h:191-229) -------------------------------------------------
-// The X sub-problem is exactly quadratic, so f(w+s) - f(w) = g.s + 1/2 s.Hs.  The reference evaluates
-// fun(w+s) with another full pass over the observations (rf_tron.h:191 -> trmf.cpp:231-245); here one
-// extra Hessian-vector product H s (cached Grams, no gather) gives the same reduction without the
-// cancellation of subtracting two large objective values.  Every block derives the same decision;
-// block 0 records the TRON line values.
+// ---- acceptance test and commit of the unfused path (rf_tron.h:186-229) ----------------------------------
+// tron_accept() on the sums wnew_kernel left (under `direct` also <s,Hs> of one more operator application).  Every block derives
+// the same decision and commits its share of w; block 0 records the TRON line.  Prr_final: r^T r of the final residual as
+// partial sums where the caller has them; null: the CG's own rho_hist.
 #if !defined(TRMF_UNIT)      // compiled by the main translation unit only (kernel_units.hpp)
 __global__ __launch_bounds__(256) void accept_kernel(XParams p, XState *__restrict__ st,
                                                      const double *__restrict__ Pbase, int np,
@@ -1397,47 +1435,17 @@ __global__ __launch_bounds__(256) void accept_kernel(XParams p, XState *__restri
                                                      XState *__restrict__ log_x, double *__restrict__ log_norms,
                                                      size_t e_begin, size_t e_end, int direct) {
     __shared__ double smem[256];
-    const double gs = (double)(real)sum_partials(Pbase + P_GS * (size_t)p.pstride, np, smem);
-    const double sr = (double)(real)sum_partials(Pbase + P_SR * (size_t)p.pstride, np, smem);
+    const double gs_d = sum_partials(Pbase + P_GS * (size_t)p.pstride, np, smem);
+    const double sr_d = sum_partials(Pbase + P_SR * (size_t)p.pstride, np, smem);
     const double sHs = direct ? sum_partials(Pbase + P_DOT * (size_t)p.pstride, np_dot, smem) : 0.0;
-    const double snorm = sqrt((double)(real)sum_partials(Pbase + P_SS * (size_t)p.pstride, np, smem));
-    const double rho = Prr_final ? (double)(real)sum_partials(Prr_final, np, smem)
-                                 : (double)(real)st->rho_hist[st->cg_iter];              // fused CG path
-    const double f = st->f;
-    const double prered = -0.5 * (gs - sr);                                  // rf_tron.h:190
-    // direct (diagnostics): s^T H s from one more operator pass; else through the CG's recurrence r = -g - H s, i.e. s^T H s =
-    // -s^T (g + r) and f - f(w+s) = prered (cg_persist.hpp has the argument)
-    const double actred = direct ? -(gs + 0.5 * sHs) : prered;
-    const double fnew = f - actred;
-    const bool accept = actred > 1e-4 * prered;                              // eta0, rf_tron.h:222
-    if (accept) {
+    const double ss_d = sum_partials(Pbase + P_SS * (size_t)p.pstride, np, smem);
+    const double rho = Prr_final ? sum_partials(Prr_final, np, smem) : st->rho_hist[st->cg_iter];
+    const TronAccept t = tron_accept(st->f, gs_d, sr_d, ss_d, sHs, direct != 0);
+    if (t.accept) {
         for (size_t e = e_begin + (size_t)blockIdx.x * 256 + threadIdx.x; e < e_end; e += (size_t)gridDim.x * 256)
             w[e] = w_new[e];
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {          // fields no block reads in this kernel
-        st->fnew = fnew; st->gs = gs; st->sr = sr;
-        st->prered = prered; st->actred = actred;
-        st->accepted = accept ? 1 : 0;
-        st->cg_rnorm = sqrt(rho);
-        // trust-region bound the reference prints (rf_tron.h:195-215; it never constrains the step here: the folded
-        // parameters of trmf.cpp:603-606 run a pure CG pass): delta0 = |g|, first iteration min(delta, |s|), then the
-        // update by the ratio of actual to predicted reduction
-        double delta = fmin(st->gnorm, snorm);
-        const double curv = fnew - f - gs;
-        const double alpha = curv <= 0 ? 4.0 : fmax(0.25, -0.5 * (gs / curv));
-        if (actred < 1e-4 * prered) delta = fmin(fmax(alpha, 0.25) * snorm, 0.5 * delta);
-        else if (actred < 0.25 * prered) delta = fmax(0.25 * delta, fmin(alpha * snorm, 0.5 * delta));
-        else if (actred < 0.75 * prered) delta = fmax(0.25 * delta, fmin(alpha * snorm, 4.0 * delta));
-        else delta = fmax(delta, fmin(alpha * snorm, 4.0 * delta));
-        st->delta = delta;
-        st->rho_direct = -1.0;
-        if (log_x) {                                    // iteration record written here: no copies on the stream
-            log_x->f = f; log_x->fnew = fnew; log_x->gnorm = st->gnorm; log_x->cg_rnorm = sqrt(rho);
-            log_x->actred = actred; log_x->prered = prered; log_x->gs = gs; log_x->sr = sr;
-            log_x->cgtol = st->cgtol; log_x->cg_iter = st->cg_iter; log_x->accepted = accept ? 1 : 0; log_x->delta = delta; log_x->rho_direct = -1.0;
-            log_norms[0] = log_norms[1] = log_norms[2] = -1.0;      // ||.||^2 lines are off in this mode
-        }
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) tron_record(st, log_x, log_norms, st->f, st->gnorm, st->cgtol, st->cg_iter, rho, -1.0, t);
 }
 #endif
 
@@ -1513,7 +1521,7 @@ __global__ __launch_bounds__(NTH) void cg_close_kernel(XParams p, const XState *
 
 // ---- acceptance test and commit of the fused path: sums of the per-tile records -----------------------------------
 // <g,s>, <s,r>, <s,s> (cg_close_kernel) and <s,Hs> (plain launch) sit in the same records; with several ranks a rank
-// commits its own timestamps [row_b, row_e) (the rows of W are all-gathered next).
+// commits its own timestamps [row_b, row_e) (the rows of W are all-gathered next).  The test itself: tron_accept().
 #if !defined(TRMF_UNIT)      // compiled by the main translation unit only (kernel_units.hpp)
 template <int NTH = 256>
 __global__ __launch_bounds__(NTH) void accept_tile_kernel(XParams p, XState *__restrict__ st, const double *__restrict__ msgP,
@@ -1529,39 +1537,13 @@ __global__ __launch_bounds__(NTH) void accept_tile_kernel(XParams p, XState *__r
     }
     block_allsum3<NTH / 64>(gs_d, sr_d, ss_d, smem);
     sHs = block_allsum<NTH / 64>(sHs, smem);
-    const double gs = (double)(real)gs_d, sr = (double)(real)sr_d;          // BLAS dots in val_type (rf_tron.h:186-187)
-    const double snorm = sqrt((double)(real)ss_d);
-    const double rho = (double)(real)st->rho_hist[st->cg_iter];
-    const double f = st->f;
-    const double prered = -0.5 * (gs - sr);                                  // rf_tron.h:190
-    const double actred = direct ? -(gs + 0.5 * sHs) : prered;               // f - f(w+s): directly / through the recurrence (accept_kernel)
-    const double fnew = f - actred;
-    const bool accept = actred > 1e-4 * prered;                              // eta0, rf_tron.h:222
-    if (accept) {
+    const TronAccept t = tron_accept(st->f, gs_d, sr_d, ss_d, sHs, direct != 0);
+    if (t.accept) {
         const size_t e0 = (size_t)sh.row_b * p.KP, e1 = (size_t)sh.row_e * p.KP;
         for (size_t e = e0 + (size_t)blockIdx.x * NTH + threadIdx.x; e < e1; e += (size_t)gridDim.x * NTH) w[e] = w_new[e];
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {          // fields no block reads in this kernel
-        st->fnew = fnew; st->gs = gs; st->sr = sr;
-        st->prered = prered; st->actred = actred;
-        st->accepted = accept ? 1 : 0;
-        st->cg_rnorm = sqrt(rho);
-        st->rho_direct = -1.0;
-        double delta = fmin(st->gnorm, snorm);          // trust-region bound of the TRON line: see accept_kernel
-        const double curv = fnew - f - gs;
-        const double alpha = curv <= 0 ? 4.0 : fmax(0.25, -0.5 * (gs / curv));
-        if (actred < 1e-4 * prered) delta = fmin(fmax(alpha, 0.25) * snorm, 0.5 * delta);
-        else if (actred < 0.25 * prered) delta = fmax(0.25 * delta, fmin(alpha * snorm, 0.5 * delta));
-        else if (actred < 0.75 * prered) delta = fmax(0.25 * delta, fmin(alpha * snorm, 4.0 * delta));
-        else delta = fmax(delta, fmin(alpha * snorm, 4.0 * delta));
-        st->delta = delta;
-        if (log_x) {                                    // iteration record written here: no copies on the stream
-            log_x->f = f; log_x->fnew = fnew; log_x->gnorm = st->gnorm; log_x->cg_rnorm = sqrt(rho);
-            log_x->actred = actred; log_x->prered = prered; log_x->gs = gs; log_x->sr = sr;
-            log_x->cgtol = st->cgtol; log_x->cg_iter = st->cg_iter; log_x->accepted = accept ? 1 : 0; log_x->delta = delta; log_x->rho_direct = -1.0;
-            log_norms[0] = log_norms[1] = log_norms[2] = -1.0;      // ||.||^2 lines are off in this mode
-        }
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        tron_record(st, log_x, log_norms, st->f, st->gnorm, st->cgtol, st->cg_iter, st->rho_hist[st->cg_iter], -1.0, t);
 }
 #endif
 

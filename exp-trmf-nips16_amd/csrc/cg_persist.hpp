@@ -606,18 +606,13 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? 2 : 1) void cg_persist_kernel(XPa
     if (!collect(xi, 4, sum, true, vs)) return;            // + the neighbours' rows of g
     stamp(0, 4);
     xi++;
-    // f, |g|, tolerances (rf_tron.h:154-169, 424-439)
-    const real ggr = (real)sum[2];
-    const real cgtol = (real)(p.eps_cg * sqrt((double)ggr));
-    {
-        double f = 0.5 * (p.trYTY + sum[3]);
-        if (p.lambdaI > 0) f += 0.5 * p.lambdaI * (double)(real)sum[1];
-        if (p.nlag > 0 && p.lambdaAR > 0) f += 0.5 * p.lambdaAR * sum[0];
-        if (tid == 0) { keep[0] = f; keep[1] = sqrt((double)ggr); keep[2] = (double)ggr; }   // f, |g|, r^T r of the last completed iteration
-    }
-    double rho_prev_d = (double)ggr, rho_d = rho_prev_d;
+    // f, |g|, tolerances: tron_start() (cg_kernels.hpp)
+    const TronStart ts = tron_start(p, sum[0], sum[1], sum[2], sum[3]);
+    const real cgtol = ts.cgtol;
+    if (tid == 0) { keep[0] = ts.f; keep[1] = ts.gnorm; keep[2] = (double)ts.ggr; }   // f, |g|, r^T r of the last completed iteration
+    double rho_prev_d = (double)ts.ggr, rho_d = rho_prev_d;
     if (lead) st->rho_hist[0] = rho_prev_d;                     // r^T r of iteration 0 = g^T g (the launch-per-step path stores it likewise)
-    bool stopped = cg_stopped(ggr, cgtol);
+    bool stopped = ts.stopped;
     int stop_it = stopped ? 0 : kCgRunning, cg_iter = stopped ? 0 : 1;
 
     // =========================== CG ===========================
@@ -630,22 +625,17 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? 2 : 1) void cg_persist_kernel(XPa
     __syncthreads();
     for (;;) {
         if (it > 0) {
-            // the three dot products of iteration it-1 -> alpha, r^T r, the stop test, beta (rf_tron.h:444-446, 460, 495-497)
+            // the three dot products of iteration it-1 -> alpha, r^T r, the stop test, beta: cg_step_scalars() (cg_kernels.hpp)
             if (!collect(xi, 3, sum, true, hst)) return;    // + the halo rows of H d(it-1)
             stamp(it + 1, 0);
             stamp_all(it, 0);
             xi++;
-            const real rho_prev = (real)rho_prev_d;
-            alpha = rho_prev / (real)sum[0];
-            const double ad = (double)alpha;
-            rho_d = fmax(rho_prev_d - 2.0 * ad * sum[1] + ad * ad * sum[2], 0.0);
-            const real rho = (real)rho_d;
-            stopped = it == a.maxcg || cg_stopped(rho, cgtol);
+            const CgStep c = cg_step_scalars(rho_prev_d, sum[0], sum[1], sum[2], cgtol, it == a.maxcg);
+            alpha = c.alpha; rho_d = c.rho_d; stopped = c.stopped;
             if (lead) st->rho_hist[it] = rho_d;
             if (stopped) { stop_it = it; if (tid == 0) keep[2] = rho_d; break; }
             cg_iter = it + 1;
-            const real beta = rho / rho_prev;
-            const real tmp = beta - (real)1.0, nalpha = -alpha;
+            const real tmp = c.tmp, nalpha = -alpha;
             rho_prev_d = rho_d;
             // element-wise, no sums: any assignment of elements to threads gives the same vectors.  One 16-byte vector of neighbouring
             // elements per thread and array, two trips' worth requested before the first use (all of nV, own0, own_n are multiples of
@@ -722,8 +712,7 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? 2 : 1) void cg_persist_kernel(XPa
     }
     block_allsum3<NW>(gs, sr, ss, smem);
     // a.direct (diagnostics; TRMF_TEST + TRMF_CG_DIRECT): one more operator pass evaluates s^T H s and the residual -g - H s directly.
-    // Otherwise (round 6) this is the solve's LAST exchange: the CG's own recurrence r = -g - H s gives s^T H s = -s^T (g + r) -- what the
-    // reference's prered is made of (rf_tron.h:189-190) -- so f(w + s) - f(w) = g.s + 1/2 s.Hs = 1/2 (g.s - s.r): actred = prered, one
+    // Otherwise this is the solve's LAST exchange: tron_accept() (cg_kernels.hpp) takes the reduction from the CG's own recurrence, one
     // pass (~12 us at config 3) and the halo rows of s saved.  How far the recurrence is from the direct residual at the stopping
     // step is on record (tests/test_gpu_fullsize.py, < 1e-2 of rho; the exit is at 10 % of |g|).
     const bool direct = a.direct != 0;
@@ -755,36 +744,14 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? 2 : 1) void cg_persist_kernel(XPa
         if (tid == 0) publish(xi, rdir, 0, sHs, 0, true);
         if (!collect(xi, 3, ps, false, nullptr)) return;
     } else __syncthreads();                                                      // keep[] (thread 0) before everybody reads it
-    const double gsr = (double)(real)keep[3], srr = (double)(real)keep[4];       // BLAS dots in val_type (rf_tron.h:186-187)
-    const double snorm = sqrt((double)(real)keep[5]);
-    const double prered = -0.5 * (gsr - srr);                                    // rf_tron.h:190
-    const double actred = direct ? -(gsr + 0.5 * ps[2]) : prered;                // f - f(w+s): directly / through the recurrence
     const double f = keep[0], gnorm = keep[1], rho_stop = keep[2];               // (written before many barriers ago)
-    const double fnew = f - actred;
-    const bool accept = actred > 1e-4 * prered;                                  // eta0, rf_tron.h:222
-    if (accept)
+    const TronAccept t = tron_accept(f, keep[3], keep[4], keep[5], ps[2], direct);             // cg_kernels.hpp
+    if (t.accept)
         for (int e = tid; e < own_n; e += NTH) { real *wp = a.W + (size_t)i0 * KP + e; *wp = *wp + sown[e]; }   // w_new = w + s (rf_tron.h:183-184)
     stamp(kProfIters - 1, 0);
     if (lead) {
-        const double rho = (double)(real)rho_stop;
-        st->f = f; st->fnew = fnew; st->gnorm = gnorm; st->cgtol = cgtol; st->gs = gsr; st->sr = srr;
-        st->prered = prered; st->actred = actred; st->accepted = accept ? 1 : 0; st->cg_iter = cg_iter;
-        st->stop_it = stop_it; st->r_parity = stop_it & 1; st->cg_rnorm = sqrt(rho); st->rho_direct = ps[0];
-        double delta = fmin(gnorm, snorm);                                       // trust-region bound of the TRON line: see accept_kernel
-        const double curv = fnew - f - gsr;
-        const double al = curv <= 0 ? 4.0 : fmax(0.25, -0.5 * (gsr / curv));
-        if (actred < 1e-4 * prered) delta = fmin(fmax(al, 0.25) * snorm, 0.5 * delta);
-        else if (actred < 0.25 * prered) delta = fmax(0.25 * delta, fmin(al * snorm, 0.5 * delta));
-        else if (actred < 0.75 * prered) delta = fmax(0.25 * delta, fmin(al * snorm, 4.0 * delta));
-        else delta = fmax(delta, fmin(al * snorm, 4.0 * delta));
-        st->delta = delta;
-        if (a.log_x) {
-            XState *lx = a.log_x;
-            lx->f = f; lx->fnew = fnew; lx->gnorm = gnorm; lx->cg_rnorm = sqrt(rho);
-            lx->actred = actred; lx->prered = prered; lx->gs = gsr; lx->sr = srr;
-            lx->cgtol = cgtol; lx->cg_iter = cg_iter; lx->accepted = accept ? 1 : 0; lx->delta = delta; lx->rho_direct = ps[0];
-            a.log_n[0] = a.log_n[1] = a.log_n[2] = -1.0;
-        }
+        tron_record(st, a.log_x, a.log_n, f, gnorm, cgtol, cg_iter, rho_stop, ps[0], t);
+        st->stop_it = stop_it; st->r_parity = stop_it & 1;
     }
 }
 

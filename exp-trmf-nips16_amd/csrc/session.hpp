@@ -285,9 +285,8 @@ struct TrmfSessionImpl : SessionXPhase {
                 int wide_TI = 0;
                 // (the wide geometry pays through the persistent kernel; where that cannot run -- switched off, a CG cap beyond its
                 // history, LDS -- the launch-per-step path is faster on narrow tiles: 975 against 959 iter/s at config 3)
-                const int maxcg = (int)std::min<long long>(max_cg_iter, (long long)T * k);
                 const char *pe = getenv("TRMF_PERSIST");
-                const bool persist_wanted = !(pe && atoi(pe) == 0) && maxcg <= kCgHistCap;
+                const bool persist_wanted = !(pe && atoi(pe) == 0) && max_cg() <= kCgHistCap;
                 if (tk && tk[0] == 'w') wide_TI = std::min(rows_wide, std::max(need, TI + 1));
                 else if (persist_wanted && (T + TI - 1) / TI > cus && need <= rows_wide &&
                          persist_lds_bytes(need, midx, KP, nlag, k, (T + need - 1) / need) <= kLdsMax) wide_TI = need;
@@ -657,9 +656,8 @@ struct TrmfSessionImpl : SessionXPhase {
     int run(int iters) {
         if (comm->world == 1 && snap_iter < 0 && period_W > 0 && iters > 0 && tile_TI > 0 && !persist_failed) {
             // the persistent kernel is about to be used: the state to come back to if it times out (persist_recover)
-            const int maxcg = (int)std::min<long long>(max_cg_iter, (long long)T * k);
             FillStreamScope fill(stream);                 // (persist_usable() allocates the exchange tables on first use)
-            if (maxcg <= kCgHistCap && persist_usable(maxcg) && take_snapshot()) return kFail;
+            if (max_cg() <= kCgHistCap && persist_usable(max_cg()) && take_snapshot()) return kFail;
         }
         for (int it = 0; it < iters; it++) {
             const int iter1 = ++iter;                       // 1-based like the reference

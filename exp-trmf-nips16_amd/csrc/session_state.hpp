@@ -54,11 +54,10 @@ struct SessionState {
     int period_W = 1, period_H = 1, period_Lag = 2, verbose = 0;
     bool log_norms = true;       // ||.||^2 records of the iteration log (the reference: only under verbose)
     int max_cg_iter = 20;        // 10 * 2, trmf.h:90-93 folded by trmf.cpp:603-606
-    // The acceptance test's f(w) - f(w + s).  The reference evaluates fun(w + s) by a pass over the observations (rf_tron.h:191);
-    // rounds 1-5 took one more operator pass (s^T H s; exact for this quadratic).  Since round 6 the CG's own recurrence supplies it
-    // (r = -g - H s, so s^T H s = -s^T (g + r) -- the quantities the reference's prered is built from, rf_tron.h:189-190): one pass per
-    // solve less in every form of the CG.  TRMF_TEST + TRMF_CG_DIRECT=1 brings the pass back as a diagnostic (TrmfIterStats.
-    // cg_rnorm_direct, the direct actred); the iterates are the same either way unless a step is rejected, which has not been seen.
+    int max_cg() const { return (int)std::min<long long>(max_cg_iter, (long long)T * k); }   // the CG cap of an X-solve, trmf.cpp:523-526
+    // The acceptance test takes f(w) - f(w + s) from the CG's own recurrence (tron_accept(), cg_kernels.hpp).  TRMF_TEST +
+    // TRMF_CG_DIRECT=1 adds one operator pass per solve as a diagnostic (s^T H s directly: TrmfIterStats.cg_rnorm_direct, the direct
+    // actred); the iterates are the same either way unless a step is rejected, which has not been seen.
     bool cg_direct = test_env("TRMF_CG_DIRECT") != nullptr && atoi(test_env("TRMF_CG_DIRECT")) != 0;
     double eps_cg = 0.1;
     int iter = 0;                // ALS iterations done so far

@@ -167,31 +167,49 @@ struct SessionXPhase : SessionFPhase {
 
     // ---- X-solve (trmf.cpp:665-674 -> rf_tron.h:134-254) -----------------------------------------------
     // Fused path (the AR halo fits LDS): hv_tile_kernel in its four roles, one launch per CG iteration.
-    template <int MODE, bool SHARD> int launch_hv_tile_as(const HvVecs &a, int it, int last, const double *rec_in, double *rec_out) {
-        const size_t lds = hv_tile_lds_bytes(tile_TI, midx, KP, nlag, k);
-        const TileShard &sh = SHARD ? tsh_rank : tsh;
-        const PeerTable *pt = (SHARD && p2p_use) ? peer_table.p : nullptr;
-        const int mi = rec_out == xm[0] ? 0 : rec_out == xm[1] ? 1 : 2;
-        // (wide tiles -- 512 threads, one rank only: session.hpp, choose_tile() -- have their own instantiations, unit_hv_wide.hip)
-        return with_kq(hv_kq(k), [&](auto Kq) {
-            constexpr int KQ = decltype(Kq)::value;
-            if (!SHARD && tile_nth == 512)
-                hipLaunchKernelGGL((hv_tile_kernel<MODE, KQ, false, 512>), dim3(sh.ntiles), dim3(512), lds, stream, xp, xstate.p, a, sh, it, last,
-                                   lag_set.p, theta.p, Gmat(), rec_in, rec_out, pt, mi, tile_TI);
-            else
-                hipLaunchKernelGGL((hv_tile_kernel<MODE, KQ, SHARD>), dim3(sh.ntiles), dim3(256), lds, stream, xp, xstate.p, a, sh, it, last,
-                                   lag_set.p, theta.p, Gmat(), rec_in, rec_out, pt, mi, tile_TI);
-        }) ? 0 : unsupported_rank();
+    // The tile kernels' <SHARD, NTH> from (shard, tile_nth), in the style of with_kq: f(std::bool_constant<SHARD>{},
+    // std::integral_constant<int, NTH>{}).  Wide tiles (512 threads) exist on one rank only (session.hpp, the tile geometry) and
+    // have their own instantiations (unit_hv_wide.hip).
+    template <class F> void with_tile_form(bool shard, F &&f) const {
+        if (shard) f(std::true_type{}, std::integral_constant<int, 256>{});
+        else if (tile_nth == 512) f(std::false_type{}, std::integral_constant<int, 512>{});
+        else f(std::false_type{}, std::integral_constant<int, 256>{});
     }
     template <int MODE> int launch_hv_tile(bool shard, const HvVecs &a, int it, int last, const double *rec_in, double *rec_out) {
-        return shard ? launch_hv_tile_as<MODE, true>(a, it, last, rec_in, rec_out) : launch_hv_tile_as<MODE, false>(a, it, last, rec_in, rec_out);
+        const size_t lds = hv_tile_lds_bytes(tile_TI, midx, KP, nlag, k);
+        const TileShard &sh = shard ? tsh_rank : tsh;
+        const PeerTable *pt = (shard && p2p_use) ? peer_table.p : nullptr;
+        const int mi = rec_out == xm[0] ? 0 : rec_out == xm[1] ? 1 : 2;
+        bool ok = false;
+        with_tile_form(shard, [&](auto Shard, auto Nth) {
+            constexpr bool SHARD = decltype(Shard)::value;
+            constexpr int NTH = decltype(Nth)::value;
+            ok = with_kq(hv_kq(k), [&](auto Kq) {
+                hipLaunchKernelGGL((hv_tile_kernel<MODE, decltype(Kq)::value, SHARD, NTH>), dim3(sh.ntiles), dim3(NTH), lds, stream, xp, xstate.p, a, sh,
+                                   it, last, lag_set.p, theta.p, Gmat(), rec_in, rec_out, pt, mi, tile_TI);
+            });
+        });
+        return ok ? 0 : unsupported_rank();
+    }
+    // Host-followed CG (time-sharded through the communicator: an exchange costs a collective, so none is issued for an iteration
+    // that will not run).  The loop enqueues as many iterations as the previous solve needed (cg_pred), then, after launch `upto`,
+    // reads XState::stop_it back -- identical on every rank -- and goes on two at a time.  Returns 1: the CG has stopped (leave the
+    // loop), 0: go on, kFail.
+    int first_stop_check(bool follow, int maxcg) const { return follow ? std::min(maxcg, std::max(1, cg_pred)) : maxcg; }
+    int follow_stop(int it, int maxcg, int &upto) {
+        if (it == maxcg) cg_pred = maxcg;
+        if (it != upto || it == maxcg) return 0;
+        int stop = kCgRunning;
+        TRMF_HIP_CHECK(hipMemcpyAsync(&stop, &xstate.p->stop_it, sizeof(int), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (stop != kCgRunning) { cg_pred = stop; return 1; }
+        upto = std::min(maxcg, upto + 2);
+        return 0;
     }
     // The fused X-solve: gradient launch, CG launches (one per iteration, the closing one also forms w_new and the sums
     // of the acceptance test), plain launch H s, accept.  shard: every launch runs this rank's tiles only and is
-    // followed by the exchange of its message; the host then follows the CG's progress (the stop is detected on the
-    // device) so that no exchange is issued for an iteration that will not run: it enqueues as many iterations as the
-    // previous solve needed, reads XState::stop_it back, and goes on two at a time.  All ranks derive identical scalars
-    // from identical records, so they take identical decisions (the collectives match).
+    // followed by the exchange of its message; the host then follows the CG's progress (follow_stop).  All ranks derive
+    // identical scalars from identical records, so they take identical decisions (the collectives match).
     int xsolve_fused(bool shard, int maxcg, XState *log_x, double *log_n) {
         real *dbuf[2] = {d0.p, d1.p}, *rbuf[2] = {r.p, r1.p}, *hbuf[2] = {Hd.p, Hd1.p};
         double *mg = xm[2], *mc[2] = {xm[0], xm[1]};
@@ -206,7 +224,7 @@ struct SessionXPhase : SessionFPhase {
         // host-followed progress only where an exchange costs a collective; peer to peer (and on one rank) the launches of
         // iterations that will not run are no-ops on the device and everything is enqueued at once
         const bool follow = shard && !p2p_use;
-        int upto = follow ? std::min(maxcg, std::max(1, cg_pred)) : maxcg;
+        int upto = first_stop_check(follow, maxcg);
         for (int it = 1; it <= maxcg; it++) {                              // launch `maxcg` only closes the last iteration
             a.v = dbuf[(it - 1) & 1]; a.r_in = rbuf[(it - 1) & 1]; a.hd_in = hbuf[(it - 1) & 1];
             a.d_out = dbuf[it & 1]; a.r_out = rbuf[it & 1]; a.out = hbuf[it & 1];
@@ -214,26 +232,16 @@ struct SessionXPhase : SessionFPhase {
             if (!shard) continue;
             if (exchange(it & 1, it, 3, dbuf[it & 1], rbuf[it & 1], hbuf[it & 1])) return kFail;
             if (!follow) continue;
-            if (it == upto && it < maxcg) {                                // has the CG stopped?  (identical on every rank)
-                int stop = kCgRunning;
-                TRMF_HIP_CHECK(hipMemcpyAsync(&stop, &xstate.p->stop_it, sizeof(int), hipMemcpyDeviceToHost, stream));
-                TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-                if (stop != kCgRunning) { cg_pred = stop; break; }
-                upto = std::min(maxcg, upto + 2);
-            } else if (it == maxcg) cg_pred = maxcg;
+            if (const int fs = follow_stop(it, maxcg, upto)) { if (fs == kFail) return kFail; break; }
         }
         // close the last completed iteration: s, w_new = w + s, the sums of the acceptance test (+ the edge rows of s)
         const TileShard &sh = shard ? tsh_rank : tsh;
         const PeerTable *pt = (shard && p2p_use) ? peer_table.p : nullptr;
-        if (shard)
-            hipLaunchKernelGGL(cg_close_kernel<true>, dim3(sh.ntiles), dim3(256), 0, stream, xp, xstate.p, sh, tile_TI, mc[0], mc[1], dbuf[0],
-                               dbuf[1], rbuf[0], rbuf[1], hbuf[0], hbuf[1], s.p, g.p, W.p, w_new.p, mg, pt);
-        else if (tile_nth == 512)
-            hipLaunchKernelGGL((cg_close_kernel<false, 512>), dim3(sh.ntiles), dim3(512), 0, stream, xp, xstate.p, sh, tile_TI, mc[0], mc[1], dbuf[0],
-                               dbuf[1], rbuf[0], rbuf[1], hbuf[0], hbuf[1], s.p, g.p, W.p, w_new.p, mg, pt);
-        else
-            hipLaunchKernelGGL(cg_close_kernel<false>, dim3(sh.ntiles), dim3(256), 0, stream, xp, xstate.p, sh, tile_TI, mc[0], mc[1], dbuf[0],
-                               dbuf[1], rbuf[0], rbuf[1], hbuf[0], hbuf[1], s.p, g.p, W.p, w_new.p, mg, pt);
+        with_tile_form(shard, [&](auto Shard, auto Nth) {
+            constexpr int NTH = decltype(Nth)::value;
+            hipLaunchKernelGGL((cg_close_kernel<decltype(Shard)::value, NTH>), dim3(sh.ntiles), dim3(NTH), 0, stream, xp, xstate.p, sh, tile_TI, mc[0],
+                               mc[1], dbuf[0], dbuf[1], rbuf[0], rbuf[1], hbuf[0], hbuf[1], s.p, g.p, W.p, w_new.p, mg, pt);
+        });
         // the records of the closing launch (+ under cg_direct the halo rows of s, operand of the pass below)
         if (shard && exchange(2, -1, cg_direct ? 1 : 0, cg_direct ? s.p : nullptr, nullptr, nullptr)) return kFail;
         if (cg_direct) {                                                           // diagnostics: s^T H s by one more operator pass (session_state.hpp)
@@ -243,11 +251,11 @@ struct SessionXPhase : SessionFPhase {
             if (shard && exchange(2, -1, 0, nullptr, nullptr, nullptr)) return kFail;
         }
         const int nb = (int)std::min<size_t>(kMaxPartials, ((size_t)(sh.row_e - sh.row_b) * KP + 255) / 256);
-        if (!shard && tile_nth == 512)                 // (the records are summed in the tiles' own order: thread stride = workgroup size)
-            hipLaunchKernelGGL(accept_tile_kernel<512>, dim3(std::max(nb, 1)), dim3(512), 0, stream, xp, xstate.p, mg, sh, 0, w_new.p, W.p, log_x, log_n, cg_direct ? 1 : 0);
-        else
-            hipLaunchKernelGGL(accept_tile_kernel<256>, dim3(std::max(nb, 1)), dim3(256), 0, stream, xp, xstate.p, mg, sh,
-                               shard ? 1 : 0, w_new.p, W.p, log_x, log_n, cg_direct ? 1 : 0);
+        with_tile_form(shard, [&](auto, auto Nth) {     // (the records are summed in the tiles' own order: thread stride = workgroup size)
+            constexpr int NTH = decltype(Nth)::value;
+            hipLaunchKernelGGL(accept_tile_kernel<NTH>, dim3(std::max(nb, 1)), dim3(NTH), 0, stream, xp, xstate.p, mg, sh, shard ? 1 : 0, w_new.p, W.p,
+                               log_x, log_n, cg_direct ? 1 : 0);
+        });
         TRMF_HIP_CHECK(hipGetLastError());
         if (shard && gather_rows(W.p, tbounds, (size_t)KP * sizeof(real))) return kFail;   // the F-solve gathers rows of all of W
         return 0;
@@ -274,8 +282,7 @@ struct SessionXPhase : SessionFPhase {
     bool persist_usable_shard() {
         if (persist_shard_state == 0) {
             persist_shard_state = -1;
-            const int maxcg = (int)std::min<long long>(max_cg_iter, (long long)T * k);
-            if (p2p.on && p2p.ext_bytes > 0 && tile_TI > 0 && ts_possible && nbt <= kPersistMaxTiles && maxcg <= kCgHistCap && !full) {
+            if (p2p.on && p2p.ext_bytes > 0 && tile_TI > 0 && ts_possible && nbt <= kPersistMaxTiles && max_cg() <= kCgHistCap && !full) {
                 const size_t lds = persist_lds_bytes(tile_TI, midx, KP, nlag, k, nbt);
                 int slots = 0;
                 with_kq(hv_kq(k), [&](auto Kq) { slots = persist_prepare<decltype(Kq)::value, true>(lds); });
@@ -499,7 +506,7 @@ struct SessionXPhase : SessionFPhase {
     const real *Gmat() const { return full ? GSx.p : G.p; }      // shared H^T H or the per-timestamp cache
     int xsolve(XState *log_x = nullptr, double *log_n = nullptr) {   // log_*: record written by the accept kernel
         XState *st = xstate.p;
-        const int maxcg = (int)std::min<long long>(max_cg_iter, (long long)T * k);   // trmf.cpp:523-526
+        const int maxcg = max_cg();
         const bool fused = tile_TI > 0 && maxcg <= kCgHistCap;
         bool timed = false;
         int form = x_form;
@@ -575,7 +582,7 @@ struct SessionXPhase : SessionFPhase {
         av.v = dbuf[0]; av.r_in = rbuf[0];
         if (hv(av, 0, 0, 0, hbuf[0], 1)) return kFail;                   // H d0 and its three dot products
         const bool follow_u = uts && !p2p_use;                            // peer to peer: everything is enqueued at once, as on one GPU
-        int upto = follow_u ? std::min(maxcg, std::max(1, cg_pred)) : maxcg;
+        int upto = first_stop_check(follow_u, maxcg);
         // one rank: stay kCgLook steps ahead of the device and stop enqueuing once the CG has stopped (session_state.hpp, cg_note)
         const bool follow_note = comm->world == 1 && maxcg > kCgLook + 1 && maxcg < 128 && !test_env("TRMF_NO_CG_FOLLOW") && ensure_cg_note() == 0;
         const unsigned int seq = follow_note ? (++cg_seq & 0xffffffu) : 0u;
@@ -601,14 +608,8 @@ struct SessionXPhase : SessionFPhase {
                 }
                 if (stopped) break;
             }
-            if (!follow_u) continue;
-            if (it == upto && it < maxcg) {                              // time-sharded: follow the stop (identical on every rank)
-                int stop = kCgRunning;
-                TRMF_HIP_CHECK(hipMemcpyAsync(&stop, &xstate.p->stop_it, sizeof(int), hipMemcpyDeviceToHost, stream));
-                TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-                if (stop != kCgRunning) { cg_pred = stop; break; }
-                upto = std::min(maxcg, upto + 2);
-            } else if (it == maxcg) cg_pred = maxcg;
+            if (!follow_u) continue;                                  // time-sharded through the communicator
+            if (const int fs = follow_stop(it, maxcg, upto)) { if (fs == kFail) return kFail; break; }
         }
         hipLaunchKernelGGL(wnew_kernel, dim3(nbw), dim3(256), 0, stream, xp, st, W.p, s.p, g.p, rbuf[0], rbuf[1], w_new.p, Pb, own_b, own_e,
                            uts ? comm->rank * wn_slots : 0);

@@ -7,8 +7,8 @@ set -euo pipefail
 R=$(cd "$(dirname "$0")/.." && pwd); OLD=$(realpath "$1"); cd "$R"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 O=${AB_OUT:-build/ab}; mkdir -p $O
-TRMF_CORELIB_DIR=$OLD timeout -k 10 300 python scripts/digest_run.py > $O/digest_old.txt 2>&1
-timeout -k 10 300 python scripts/digest_run.py > $O/digest_new.txt 2>&1
+TRMF_CORELIB_DIR=$OLD timeout -k 10 420 python scripts/digest_run.py > $O/digest_old.txt 2>&1
+timeout -k 10 420 python scripts/digest_run.py > $O/digest_new.txt 2>&1
 if diff $O/digest_old.txt $O/digest_new.txt > /dev/null; then echo "DIGESTS IDENTICAL"
 else echo "DIGESTS DIFFER"; diff $O/digest_old.txt $O/digest_new.txt | head || true; exit 1; fi
 # iter/s over all windows, the windows' median / min / max, phase times, CG pass
@@ -17,4 +17,6 @@ for lib in old new old new; do
   if [ $lib = old ]; then export TRMF_CORELIB_DIR=$OLD; else unset TRMF_CORELIB_DIR; fi
   echo "== $lib c3"; rep
   echo "== $lib c2"; rep --config c2 --steps 40 --warmup 10
+  echo "== $lib imp"; rep --config imp          # one launch per CG step (accept_tile_kernel, hv_tile_kernel)
+  echo "== $lib imp60"; rep --config imp60      # the unfused path (ar_tile_kernel<AR_CG_STEP>, cg_init_kernel, accept_kernel)
 done
