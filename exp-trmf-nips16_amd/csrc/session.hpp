@@ -137,6 +137,7 @@ struct TrmfSessionImpl : SessionXPhase {
         KP = padded_rank(k); NT = KP / kTile; KMAX = ((k + 7) / 8) * 8;
         generic = k > kMaxRank;
         nlag = (int)lag_size; midx = nlag ? (int)lags[nlag - 1] : 0;
+        has_lag0 = nlag > 0 && lags[0] == 0;
         comm = active_comm();
         if (StreamCache::acquire(&stream)) return kFail;
         FillStreamScope fill(stream);
@@ -1020,6 +1021,80 @@ struct TrmfSessionImpl : SessionXPhase {
         TRMF_HIP_CHECK(hipStreamSynchronize(stream));
         for (int q = 0; q < 2; q++) { fc_table[q].release(); fc_prev[q].release(); }      // the next scored call starts from zeroed ones
         fc_cur = 0; fc_rows = 0;
+        return 0;
+    }
+    // ---- online updates (trmf_session_assimilate; online_kernels.hpp) ---------------------------------------------------------
+    // Rows [first_row, T) of W re-solved in ascending order with H and Theta fixed (the caller has validated first_row, the lag set
+    // and the rank).  Stage A rebuilds the Gram cache rows and right-hand sides of the range with the X phase's own builders -- every
+    // X phase rebuilds the rows it reads before it reads them (xsolve: gram_x / xprepare_full), so nothing relies on their old
+    // contents -- stage B factors all rows in parallel, stage C is the serial chain.  Everything lands in scratch; W changes by ONE
+    // device copy after the flag has been read.  No collective: every rank holds the whole Y and W and computes the same bits.
+    // A pivot that is not positive and finite is not a failure of this rank's task (res->bad_row names the row, nothing is
+    // committed): the entry point reports it on the calling thread, so the barrier of a TRMF_DEVICES group stays whole.
+    struct AssimResult {
+        uint64_t rows = 0, entries = 0;
+        double sq_err_before = 0, sq_err_after = 0;
+        int bad_row = -1;
+    };
+    int assimilate(int first_row, AssimResult *res, real *Wout) {
+        *res = AssimResult{};
+        if (sync()) return kFail;
+        const int nr = T - first_row;
+        if (nr <= 0) return 0;
+        FillStreamScope fill(stream);
+        int chunk = kAssimChunk;
+        if (const char *e = test_env("TRMF_ASSIM_CHUNK")) chunk = std::max(1, atoi(e));      // tests: several passes on a small shape
+        chunk = std::min(chunk, nr);
+        DevBuf<real> Wn, flat, U;
+        DevBuf<int> flag;
+        DevBuf<double> errs;
+        SyncStreamOnExit drain(stream);
+        if (Wn.alloc((size_t)nr * KP) || (Wout && flat.alloc((size_t)nr * k, false)) || U.alloc((size_t)chunk * k * k, false) ||
+            flag.alloc(1, false) || errs.alloc((size_t)2 * nr, false)) return kFail;
+        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
+        // stage A
+        if (full) {
+            if (y_times_factor(false, H.p, Bv.p, dense ? 0u : (uint32_t)first_row, (uint32_t)T)) return kFail;        // rows of Y H
+            if (small_gram(H.p, n, real(0), GSx.p, stream)) return kFail;                                             // H^T H
+        } else if (launch_gram_x_rows((uint32_t)first_row, (uint32_t)T)) return kFail;
+        TRMF_HIP_CHECK(hipGetLastError());
+        // stages B and C, a chunk of rows at a time
+        const real lamAR = (real)lambdaAR, lam = (real)lambdaI + lamAR;
+        int reach = 0;
+        if (midx > 0 && assim_chain_lds_bytes(k, nlag, midx) <= kLdsMax && !test_env("TRMF_FORECAST_GLOBAL")) reach = midx;
+        const size_t lds = assim_chain_lds_bytes(k, nlag, reach);
+        if (allow_dyn_lds(assim_chain_kernel, lds, "online update")) return kFail;
+        for (int r0 = first_row; r0 < T; r0 += chunk) {
+            const int rows = std::min(chunk, T - r0);
+            AssimFactorArgs fa{Gmat(), full ? (size_t)0 : xp.gstride, gpacked ? 1 : 0, U.p, flag.p, lam, r0, rows, k};
+            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3((rows + 3) / 4), dim3(256), 0, stream, fa); }))
+                return unsupported_rank();
+            AssimChainArgs ca{W.p, Wn.p, Wout ? flat.p : nullptr, Bv.p, U.p, lag_set.p, theta.p, lamAR, first_row, r0, rows, k, KP, NT, nlag, reach};
+            hipLaunchKernelGGL(assim_chain_kernel, dim3(1), dim3(256), lds, stream, ca);
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        {   // the squared errors of the range with W as it is and as it will be
+            AssimErrArgs ea{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr, H.p,
+                            W.p, Wn.p, 0, first_row, errs.p, first_row, nr, n, KP, full ? 1 : 0};
+            hipLaunchKernelGGL(assim_err_kernel, dim3(nr), dim3(256), 0, stream, ea);
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        int bad = kAssimNoBadRow;
+        std::vector<double> herr((size_t)2 * nr);
+        std::vector<real> hflat(Wout ? (size_t)nr * k : 0);
+        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, herr.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (Wout) TRMF_HIP_CHECK(hipMemcpyAsync(hflat.data(), flat.p, hflat.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (bad != kAssimNoBadRow) { res->bad_row = bad; return 0; }
+        // ---- commit ----
+        TRMF_HIP_CHECK(hipMemcpyAsync(W.p + (size_t)first_row * KP, Wn.p, (size_t)nr * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new W
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        res->rows = (uint64_t)nr;
+        res->entries = full ? (uint64_t)nr * (uint64_t)n : host_row_ptr[T] - host_row_ptr[first_row];
+        for (int r = 0; r < nr; r++) { res->sq_err_before += herr[2 * r]; res->sq_err_after += herr[2 * r + 1]; }
+        if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
         return 0;
     }
     // New regularisation weights for the iterations enqueued from now on: the session's own copies (F-solve, Theta-solve, the

@@ -68,6 +68,7 @@ struct SessionState {
     hipStream_t stream = nullptr;
     DevBuf<uint32_t> Yc_ptr, Yc_idx, Yr_ptr, Yr_idx, lag_set, lag_steps;   // lag_steps: ar_lag_steps() of the lag set
     int nsteps = 0;
+    bool has_lag0 = false;       // the lag set contains lag 0 (trmf_session_assimilate refuses it: a row would be its own prior)
     DevBuf<real> Yc_val, Yr_val, W, H, theta, G, Bv, g, s, r, r1, d0, d1, Hd, Hd1, w_new;
     DevBuf<double> lossrow, partials, theta_part;
     // full-observation path (missing == 0)

@@ -525,6 +525,39 @@ int32_t trmf_session_lag_stats(TrmfSession *s, int32_t *per_dim, int32_t *capped
     return HND(s)->rank0([&](TrmfSessionImpl *t) { return t->lag_stats(per_dim, capped, refit_skipped); });
 }
 
+// Online update: the arguments are checked on the calling thread before any rank's worker runs (see trmf_session_set_heldout); a
+// bad pivot is found on the device by every rank alike and reported here, not by a failing worker task.
+int32_t trmf_session_assimilate(TrmfSession *s, int32_t first_row, TrmfAssimilateSums *out, void *Wnew) {
+    if (!s) { set_error("null session"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (f->k > kMaxRank) {
+        set_error("assimilate: online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
+        return kFail;
+    }
+    if (f->has_lag0) { set_error("assimilate: the lag set contains lag 0 (a row would be its own prior)"); return kFail; }
+    if (first_row < f->midx || first_row > f->T) {
+        set_error("assimilate: first_row " + std::to_string(first_row) + " outside [" + std::to_string(f->midx) + " (the largest lag), " +
+                  std::to_string(f->T) + " (rows)]");
+        return kFail;
+    }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    const bool grouped = HND(s)->group != nullptr;
+    std::vector<TrmfSessionImpl::AssimResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
+    if (HND(s)->all([&](TrmfSessionImpl *t) {
+            const int slot = grouped ? t->comm->rank : 0;
+            return t->assimilate(first_row, &res[slot], slot == 0 ? (real *)Wnew : nullptr);
+        })) return kFail;
+    for (const auto &r : res)
+        if (r.bad_row >= 0) {
+            set_error("assimilate: row " + std::to_string(r.bad_row) + ": a pivot of G + (lambdaI + lambdaAR) I is not positive and finite "
+                      "(lambdaI + lambdaAR == 0 and a rank-deficient row?); nothing was changed");
+            return kFail;
+        }
+    if (out) { out->rows = res[0].rows; out->entries = res[0].entries; out->sq_err_before = res[0].sq_err_before; out->sq_err_after = res[0].sq_err_after; }
+    return 0;
+}
+
 // ---- multi-GPU ----------------------------------------------------------------------------------
 int32_t trmf_dist_get_unique_id(void *out_id) {
     RcclApi &api = rccl_api();

@@ -2,10 +2,11 @@
 
 Importable exactly like the reference package (python/trmf/__init__.py:1-6):
 ``from trmf import Model, Metrics, train, rolling_validate, grid_search``; imputation (the paper's second task) adds
-``impute``, ``grid_impute`` and ``ImputeMetrics``.
+``impute``, ``grid_impute`` and ``ImputeMetrics``; online updates add ``filter_rows`` (and ``Model.assimilate``, ``Session.update``).
 """
 from .trmf import Model, Metrics
 from .trmf import train, fit, rolling_validate, grid_search
 from .impute import ImputeMetrics, impute, grid_impute
+from .online import filter_rows
 
-__all__ = ['Model', 'Metrics', 'train', 'fit', 'rolling_validate', 'grid_search', 'ImputeMetrics', 'impute', 'grid_impute']
+__all__ = ['Model', 'Metrics', 'train', 'fit', 'rolling_validate', 'grid_search', 'ImputeMetrics', 'impute', 'grid_impute', 'filter_rows']

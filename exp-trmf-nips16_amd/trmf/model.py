@@ -141,6 +141,22 @@ class Model(object):
             Ynew[:] = self.transform.postprocess(Ynew)
         return Ynew, Wnew
 
+    # ---- online update ----------------------------------------------------------------------------
+    def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True):
+        """A new ``Model`` grown by the ``Ynew.shape[0]`` timestamps of ``Ynew`` (raw values; a transform of this model is
+        applied first): H, the lag weights and the rows this model has stay as they are, every new row of W is solved from its
+        own observations and the AR prior of the rows before it (``trmf.online.filter_rows``; the host form of
+        ``Session.update``).  This model is left untouched."""
+        from .online import filter_rows
+        if self.transform is not None:
+            if smat.issparse(Ynew):
+                raise ValueError('assimilate: a series transform needs dense rows')
+            Ynew = self.transform.preprocess(np.asarray(Ynew)).astype(self.W.dtype)
+        grown = np.zeros((self.m + Ynew.shape[0], self.k), dtype=self.W.dtype, order='C')
+        grown[:self.m] = self.W
+        grown = filter_rows(grown, self.H, self.lag_set, self.lag_val, Ynew, self.m, lambdaI, lambdaAR, missing)
+        return Model.from_arrays(grown, self.H.copy(), self.lag_val.copy(), self.lag_set.copy(), transform=self.transform)
+
     # ---- construction ------------------------------------------------------------------------------
     @staticmethod
     def syn_gen(m, n, k, lag_set, seed=None, noise=0.01, dtype=np.float32):

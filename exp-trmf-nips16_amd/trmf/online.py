@@ -1,0 +1,73 @@
+"""Online updates on the host: the forward filter that ``trmf_session_assimilate`` runs on the device, as plain NumPy.
+
+New timestamps are absorbed without ALS iterations over the history: H and the lag weights stay fixed, and each new row of W,
+in ascending order, is the minimiser of its own observations plus the AR prior from the rows before it::
+
+    Omega_i = the stored entries of row i (missing)  |  every series, an absent entry reading as 0 (not missing)
+    A_i     = sum_{j in Omega_i} h_j h_j^T + (lambdaI + lambdaAR) I
+    p_i     = sum_l lag_val[l] * W[i - lag_set[l]]          (rows < i as already updated; Model.latent_forecast's expression)
+    W[i]    = A_i^-1 (sum_{j in Omega_i} y_ij h_j + lambdaAR p_i)
+
+A filter, not a smoother: rows before ``first_row`` never see the new data.  ``filter_rows`` is the specification the device
+tests compare against and the host path of ``Model.assimilate``.
+"""
+import numpy as np
+import scipy.linalg
+import scipy.sparse as smat
+
+
+def filter_rows(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, missing):
+    """A copy of ``W`` (T x k) whose rows ``first_row .. T-1`` are re-solved in ascending order; ``Yrows`` holds the
+    ``T - first_row`` rows of the training matrix that belong to them (a ``scipy.sparse`` matrix or an array; with
+    ``missing`` the stored entries of a sparse matrix, the non-zeros of an array, are the observations).  All arithmetic is
+    in the dtype of ``W``; each weight is cast to it before the two are added.  ``ValueError`` for a lag set with lag 0, a
+    ``first_row`` below the largest lag or above T, a row count that does not match, or a row whose system is not positive
+    definite (possible only with ``lambdaI + lambdaAR == 0``); the message names the row."""
+    W = np.asarray(W)
+    dt = W.dtype
+    T, k = W.shape
+    back = np.asarray(lag_set).astype(np.int64)
+    if back.size and back.min() == 0:
+        raise ValueError('filter_rows: the lag set contains lag 0 (a row would be its own prior)')
+    reach = int(back.max()) if back.size else 0
+    first_row = int(first_row)
+    if first_row < reach or first_row > T:
+        raise ValueError('filter_rows: first_row {} outside [{} (the largest lag), {} (rows)]'.format(first_row, reach, T))
+    if Yrows.shape[0] != T - first_row or (T > first_row and Yrows.shape[1] != H.shape[0]):
+        raise ValueError('filter_rows: Yrows is {}, rows {}..{} of {} series were expected'.format(Yrows.shape, first_row, T, H.shape[0]))
+    H = np.asarray(H, dtype=dt)
+    theta = np.asarray(lag_val, dtype=dt)
+    lamAR = dt.type(lambdaAR)
+    lam = dt.type(lambdaI) + lamAR
+    sparse = smat.issparse(Yrows)
+    Yr = Yrows.tocsr() if sparse else np.asarray(Yrows)
+    out = W.copy()
+    eye = np.eye(k, dtype=dt)
+    for i in range(first_row, T):
+        r = i - first_row
+        if sparse:
+            lo, hi = Yr.indptr[r], Yr.indptr[r + 1]
+            cols, y = Yr.indices[lo:hi], Yr.data[lo:hi].astype(dt)
+            if not missing:                                  # every series counts: absent entries read as 0
+                full = np.zeros(H.shape[0], dtype=dt)
+                np.add.at(full, cols, y)
+                cols, y = slice(None), full
+        elif missing:
+            cols = np.nonzero(Yr[r])[0]
+            y = Yr[r, cols].astype(dt)
+        else:
+            cols, y = slice(None), Yr[r].astype(dt)
+        Hi = H[cols]
+        A = Hi.T.dot(Hi) + lam * eye
+        prior = np.sum(out[i - back] * theta, axis=0) if back.size else np.zeros(k, dtype=dt)
+        b = Hi.T.dot(y) + lamAR * prior
+        try:
+            if not np.all(np.isfinite(A)):
+                raise np.linalg.LinAlgError('not finite')
+            L = np.linalg.cholesky(A)
+            if not (np.all(np.isfinite(L)) and np.all(np.diagonal(L) > 0)):
+                raise np.linalg.LinAlgError('pivot')
+        except np.linalg.LinAlgError:
+            raise ValueError('filter_rows: row {}: G + (lambdaI + lambdaAR) I is not positive definite'.format(i))
+        out[i] = scipy.linalg.cho_solve((L, True), b, check_finite=False)
+    return out

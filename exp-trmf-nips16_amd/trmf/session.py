@@ -45,6 +45,14 @@ class TrmfSeriesSums(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TrmfAssimilateSums(ctypes.Structure):
+    """Sums of an online update (include/trmf_abi.h): rows re-solved, their observed entries, the squared error before / after."""
+    _fields_ = [('rows', c_uint64), ('entries', c_uint64), ('sq_err_before', c_double), ('sq_err_after', c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class TrmfTrainProfile(ctypes.Structure):
     """Split of the last c_trmf_train call of this process (include/trmf_abi.h)."""
     _fields_ = [('total_s', c_double), ('setup_s', c_double), ('upload_s', c_double), ('compute_s', c_double),
@@ -109,6 +117,9 @@ def bind(lib):
         lib.trmf_session_solve_lags.argtypes = [c_void_p]; lib.trmf_session_solve_lags.restype = c_int32
         lib.trmf_session_lag_stats.argtypes = [c_void_p, c_void_p, POINTER(c_int32), POINTER(c_int32)]
         lib.trmf_session_lag_stats.restype = c_int32
+    if hasattr(lib, 'trmf_session_assimilate'):       # (absent from libraries built before the online updates)
+        lib.trmf_session_assimilate.argtypes = [c_void_p, c_int32, POINTER(TrmfAssimilateSums), c_void_p]
+        lib.trmf_session_assimilate.restype = c_int32
     lib.trmf_dist_get_unique_id.argtypes = [c_void_p]; lib.trmf_dist_get_unique_id.restype = c_int32
     lib.trmf_dist_init.argtypes = [c_int32, c_int32, c_void_p]; lib.trmf_dist_init.restype = c_int32
     lib.trmf_dist_init_callback.argtypes = [c_int32, c_int32, ALLGATHERV_FN, c_void_p]
@@ -204,6 +215,37 @@ class Session(object):
         block = Ynew if isinstance(Ynew, PyMatrix) else PyMatrix(Ynew, dtype=self.model.W.dtype)
         self._check(self.lib.trmf_session_append_rows(self.handle, byref(block)), 'trmf_session_append_rows')
         return self
+
+    def assimilate(self, first_row, return_latent=False):
+        """Online update on the device: rows ``first_row .. rows()-1`` of W are re-solved in ascending order from their own
+        observations and the AR prior of the rows before them, with H and the lag weights fixed (``trmf.online.filter_rows``
+        is the same computation in NumPy).  Returns ``{'rows', 'entries', 'sq_err_before', 'sq_err_after'}`` -- right after
+        ``append_rows`` the third is the one-step-ahead forecast error of the block -- or ``(sums, Wnew)`` with
+        ``return_latent``.  A refused call (lag 0 in the lag set, rank above 64, ``first_row`` below the largest lag, a row
+        whose system is not positive definite) raises and leaves the session as it was."""
+        first_row = int(first_row)
+        sums = TrmfAssimilateSums()
+        Wnew = None
+        if return_latent:
+            Wnew = np.empty((max(self.rows() - first_row, 0), self.model.k), dtype=self.model.W.dtype)
+        self._check(self.lib.trmf_session_assimilate(self.handle, first_row, byref(sums), Wnew.ctypes.data if Wnew is not None and Wnew.size else None),
+                    'trmf_session_assimilate')
+        return (sums.as_dict(), Wnew) if return_latent else sums.as_dict()
+
+    def update(self, Ynew, iters=0):
+        """Absorb the new timestamps ``Ynew`` (as for ``append_rows``): append them, assimilate the new block, run ``iters``
+        ALS iterations if asked for.  ``self.model`` is replaced by a host model of ``rows()`` timestamps (H, lag weights, lag
+        set and transform carried over; its arrays are filled by the next ``download()``).  Returns the sums of ``assimilate``."""
+        before = self.rows()
+        self.append_rows(Ynew)
+        old = self.model
+        grown = np.zeros((self.rows(), old.k), dtype=old.W.dtype, order='C')
+        grown[:min(before, old.m)] = old.W[:before]
+        self.model = type(old).from_arrays(grown, old.H.copy(), old.lag_val.copy(), old.lag_set.copy(), transform=old.transform)
+        sums = self.assimilate(before)
+        if iters:
+            self.run(int(iters))
+        return sums
 
     def set_transform(self, transform):
         """Train on ``transform.preprocess`` of the raw dense Y held by the session (``None``: the raw values); the

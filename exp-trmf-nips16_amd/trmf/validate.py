@@ -15,6 +15,10 @@ stay where they are).  A per-window ``NormalizedTransform`` (the paper scripts' 
 every entry of the prefix: the session then keeps the RAW dense matrix and applies each window's refitted
 coefficients on the device (``Session.set_transform`` -> ``trmf_session_set_series_transform``), so only 2n numbers
 per window are uploaded.  ``resident=False`` forces a fresh upload per window through ``train``.
+
+``update='assimilate'`` is the online form of the same evaluation: window 0 is trained with ``max_iter`` iterations, every
+later window only appends its rows and absorbs them with the forward filter (``Session.update``), H and the lag weights
+staying as window 0 left them.
 """
 import itertools
 import pickle
@@ -31,7 +35,7 @@ def _as_training_matrix(block, missing):
     return smat.csr_matrix(block) if missing else block
 
 
-def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag=None):
+def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag=None, assimilate=False):
     """Yield the trained model of every window from one resident session.  With a transform (dense Y, full
     observation) the session holds the RAW matrix and applies each window's refitted coefficients on the device."""
     from .session import Session
@@ -43,6 +47,10 @@ def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing,
         sess.run(max_iter).download()
         yield model
         for prev_cut, cut in zip(cuts[:-1], cuts[1:]):
+            if assimilate:      # online: the new rows are filtered in, nothing is retrained
+                sess.update(_as_training_matrix(Y[prev_cut:cut], missing))
+                yield sess.download()
+                continue
             # host-side model of the new size: same warm start the device applies, same RNG consumption as the
             # reference, and (if asked for) a transform refitted on the grown prefix
             model = Model.initialize(Y[:cut], lag_set, k, seed=seed, warm_start_model=model, transform=transform)
@@ -54,7 +62,8 @@ def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing,
             yield model
 
 
-def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag=None):
+def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag=None,
+                             assimilate=False):
     """The whole rolling evaluation from one resident session: every window is trained, forecast and scored on the device
     (``Session.forecast`` with the window's truth), the next window's rows are appended and, if asked for, a transform
     refitted on the grown prefix is handed over.  No factor is downloaded and no host model is rebuilt between windows."""
@@ -69,7 +78,10 @@ def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_
                 sess.append_rows(_as_training_matrix(Y[cuts[i - 1]:cut], missing))
                 if transform is not None:
                     sess.set_transform(NormalizedTransform(Y[:cut]))
-            sess.run(max_iter)
+            if assimilate and i > 0:
+                sess.assimilate(cuts[i - 1])        # online: the appended rows are filtered in, nothing is retrained
+            else:
+                sess.run(max_iter)
             sess.forecast(window_size, threshold=threshold, truth=np.ascontiguousarray(Y[cut:cut + window_size]), return_forecast=False)
         return sess.forecast_scores()
 
@@ -87,8 +99,11 @@ def _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, tr
 
 def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5, lambdaAR=50, lambdaLag=0.5,
                      max_iter=20, missing=True, threshold=0, transform=None, threads=16, verbose=0, seed=0,
-                     resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False):
-    """``lambdaLagL1`` / ``lag_refit``: sparse lag weights (``Session.set_lag_penalty``) on every path.
+                     resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False, update='retrain'):
+    """``update='assimilate'``: window 0 is trained with ``max_iter`` iterations, every later window appends its rows and
+    absorbs them by the forward filter (``Session.update``) instead of retraining; it needs the resident path and refuses a
+    per-window transform (a refitted transform rescales the whole history, which an online update does not revisit).
+    ``lambdaLagL1`` / ``lag_refit``: sparse lag weights (``Session.set_lag_penalty``) on every path.
     ``forecast_on_device=True`` keeps the forecasts and their scoring on the device as well (one session, no download and no
     host model per window); it needs the resident path and a dense ``Y``, and says so where that does not hold."""
     T, n = Y.shape
@@ -99,6 +114,14 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
     from .session import check_lag_penalty
     lambdaLagL1, lag_refit = check_lag_penalty(lambdaLagL1, lag_refit)
     lag = dict(lambdaLagL1=lambdaLagL1, lag_refit=lag_refit) if (lambdaLagL1 > 0 or lag_refit) else None     # None: the calls of before
+    if update not in ('retrain', 'assimilate'):
+        raise ValueError("update must be 'retrain' or 'assimilate', not {!r}".format(update))
+    online = update == 'assimilate'
+    if online:
+        if transform is not None:
+            raise ValueError("update='assimilate': a per-window transform rescales the whole history, which an online update does not revisit")
+        if not resident or not isinstance(Y, np.ndarray):
+            raise ValueError("update='assimilate': needs the resident path (resident=True and a dense NumPy Y)")
     if forecast_on_device:
         if not isinstance(Y, np.ndarray):
             raise ValueError('forecast_on_device: needs a dense NumPy Y (a sparse Y has no resident rolling evaluation)')
@@ -109,10 +132,10 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
         if transform is not None and missing:
             raise ValueError('forecast_on_device: a transform with missing=True is refitted on the host per window; '
                              'the device applies one only to dense full-observation training (missing=False)')
-        return _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag)
+        return _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag, online)
     # resident: a NumPy Y, and a transform only where the device can apply it (dense full-observation training)
     if resident and isinstance(Y, np.ndarray) and (transform is None or (not missing and Y.dtype in (np.float32, np.float64))):
-        models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag)
+        models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag, online)
     else:
         models = _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, threads, verbose, lag)
     forecasts = np.zeros((horizon, n), dtype=Y.dtype, order='C')

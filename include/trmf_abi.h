@@ -313,6 +313,38 @@ TRMF_API int32_t trmf_session_forecast_scores(TrmfSession *s, uint64_t *rows_sco
 /* Zero the sums, the row count and the kept truth row.  append_rows, rewind, set_lambdas and set_series_transform leave them. */
 TRMF_API int32_t trmf_session_forecast_reset(TrmfSession *s);
 
+/* --- online updates: assimilate new timestamps without retraining -------------------------------------------------------
+ * What a deployed forecaster does most often: new observations arrive, the model absorbs them and forecasts again.  A forward
+ * filter over the rows i = first_row .. rows - 1 of W, in ascending order, with H, the lag weights and every earlier row fixed
+ * (later rows are ignored: they are re-solved in turn):
+ *   Omega_i  the stored entries of row i of the training matrix (missing != 0); every series, an absent entry reading as 0
+ *            (missing == 0, dense or sparse storage)
+ *   A_i  = sum_{j in Omega_i} h_j h_j^T + (lambdaI + lambdaAR) I
+ *   p_i[t] = sum_l lag_val(l, t) W[i - lag_l][t]      rows < i as already updated; each product rounded to the element type,
+ *                                                     summed in ascending lag order (Model.latent_forecast)
+ *   W[i] = A_i^-1 (sum_{j in Omega_i} y_ij h_j + lambdaAR p_i)      Cholesky in the element type, both substitutions
+ * y is the value the session trains on (the transformed one under trmf_session_set_series_transform); the lambdas are the
+ * session's current ones (trmf_session_set_lambdas), each cast to the element type before they are added.  A filter, not a
+ * smoother: rows before first_row never see the new data.  Typical use: append_rows(Ynew); assimilate(rows - Tn); forecast(..).
+ *
+ * Blocking, ordered after every run() enqueued before; every rank computes the same rows on its own copy (no exchange) and ends
+ * up with the same bits; repeated calls from the same state give the same bits.  The iteration counter, the statistics, the mark,
+ * the forecast scores and the measured multi-rank decisions are untouched.
+ *   out    NULL, or: rows re-solved; entries = sum |Omega_i|; sq_err_before / sq_err_after = sum over Omega of (y - w_i . h_j)^2
+ *          over the range with W as it was / as it is now, in fp64 and a fixed order.  Right after append_rows, sq_err_before is
+ *          the one-step-ahead forecast error of the block in the training scale.
+ *   Wnew   NULL, or (rows - first_row) x k reals, row-major: the new rows
+ * 0 (first_row == rows: nothing to do), or -1 with trmf_last_error() and W, the outputs and the session as they were:
+ * first_row below the largest lag or above rows; a lag set that contains lag 0; rank k > 64 (online updates cover the
+ * register-tiled ranks 1..64); an A_i with a pivot that is not positive and finite (possible only with lambdaI + lambdaAR == 0
+ * and a rank-deficient row; the message names the first such row); a device failure. */
+typedef struct {
+    uint64_t rows, entries;
+    double sq_err_before, sq_err_after;
+} TrmfAssimilateSums;
+TRMF_API int32_t trmf_session_assimilate(TrmfSession *s, int32_t first_row, TrmfAssimilateSums *out /* or NULL */,
+                                         void *Wnew /* or NULL: (rows - first_row) x k, row-major */);
+
 /* --- multi-GPU (one process per GPU; RCCL all-gathers over xGMI) ---------------------------- */
 #define TRMF_UNIQUE_ID_BYTES 128
 /* Rank 0: create an RCCL unique id; the caller broadcasts the bytes to all ranks
