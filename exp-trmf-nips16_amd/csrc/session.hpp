@@ -1023,6 +1023,199 @@ struct TrmfSessionImpl : SessionXPhase {
         fc_cur = 0; fc_rows = 0;
         return 0;
     }
+    // ---- forecast uncertainty (trmf_session_fit_noise / _noise / _set_noise / _forecast_dist / _interval_scores) -----------------
+    // Stages 1-2 of uncertainty_kernels.hpp on the current factors (the caller has checked rows > the largest lag).  The work items
+    // of the residual pass are rebuilt from the host copy of the item pointers on every call (append_rows moves them): a few thousand
+    // records.  Everything lands in scratch; the resident variances change by two device copies once the sums have been read.  No
+    // collective: every rank holds the whole Y and the factors and computes the same bits.  A training matrix without a stored entry
+    // is not a failure of this rank's task (res->no_entries; nothing is committed): the entry point reports it on the calling
+    // thread, so the barrier of a TRMF_DEVICES group stays whole.
+    struct NoiseResult {
+        double pooled = 0, s2_min = 0, s2_max = 0, q_min = 0, q_max = 0;
+        uint64_t series_pooled = 0;
+        int no_entries = 0;
+    };
+    int fit_noise(NoiseResult *res) {
+        *res = NoiseResult{};
+        if (sync()) return kFail;
+        FillStreamScope fill(stream);
+        uint32_t chunk = kNzChunk;
+        if (const char *e = test_env("TRMF_NOISE_CHUNK")) chunk = (uint32_t)std::max(1, atoi(e));      // tests: several items per series on a small shape
+        std::vector<NoiseItem> items;
+        std::vector<uint32_t> first((size_t)n + 1);
+        for (int j = 0; j < n; j++) {
+            first[j] = (uint32_t)items.size();
+            if (full)       // every timestamp: the dense orientation's values, or zeros that the stored entries then correct
+                for (uint32_t b = 0; b < (uint32_t)T; b += chunk)
+                    items.push_back(NoiseItem{(uint32_t)j, b, std::min<uint32_t>(b + chunk, (uint32_t)T), (uint32_t)(dense ? kNzDense : kNzZero)});
+            if (!dense)
+                for (uint64_t b = host_col_ptr[j]; b < host_col_ptr[j + 1]; b += chunk)
+                    items.push_back(NoiseItem{(uint32_t)j, (uint32_t)b, (uint32_t)std::min<uint64_t>(b + chunk, host_col_ptr[j + 1]), (uint32_t)(full ? kNzCorrect : kNzStored)});
+            if (items.size() >= (1ull << 31)) { set_error("fit_noise: too many work items"); return kFail; }
+        }
+        first[n] = (uint32_t)items.size();
+        const uint32_t nitems = (uint32_t)items.size();
+        const int nchunks = (T - midx + kNzInnovChunk - 1) / kNzInnovChunk;
+        DevBuf<NoiseItem> d_items;
+        DevBuf<uint32_t> d_first;
+        DevBuf<double> part, sq, cnt, s2, pooled, ipart, qn;
+        SyncStreamOnExit drain(stream);
+        if (d_items.upload(items.data(), nitems) || d_first.upload(first.data(), first.size()) || part.alloc((size_t)2 * nitems, false) ||
+            sq.alloc(n, false) || cnt.alloc(n, false) || s2.alloc(n, false) || pooled.alloc(2, false) ||
+            ipart.alloc((size_t)nchunks * k, false) || qn.alloc(k, false)) return kFail;
+        if (nitems) {
+            NoiseResidArgs ra{d_items.p, nitems, dense ? nullptr : Yc_idx.p, dense ? nullptr : Yc_val.p, dense ? Yd_nt.p : nullptr, W.p, H.p, part.p, T, KP, NT};
+            const dim3 grid((nitems + 3) / 4);
+            if (!with_nt0(generic ? 0 : NT, [&](auto N) { hipLaunchKernelGGL(noise_resid_kernel<decltype(N)::value>, grid, dim3(256), 0, stream, ra); }))
+                return unsupported_rank();
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(noise_series_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, part.p, d_first.p, n, sq.p, cnt.p);
+        hipLaunchKernelGGL(noise_pool_kernel, dim3(1), dim3(256), 0, stream, sq.p, cnt.p, n, s2.p, pooled.p);
+        TRMF_HIP_CHECK(hipGetLastError());
+        {
+            size_t lds = innov_lds_bytes(nlag);
+            NoiseInnovArgs ia{W.p, lag_set.p, theta.p, ipart.p, T, midx, k, KP, NT, nlag, 1};
+            if (lds > kLdsMax) { ia.lds = 0; lds = 0; }                 // a lag set too long for LDS: Theta and the lags from global memory
+            else if (allow_dyn_lds(noise_innov_kernel, lds, "noise fit")) return kFail;
+            hipLaunchKernelGGL(noise_innov_kernel, dim3(nchunks, (k + 63) / 64), dim3(64), lds, stream, ia);
+            hipLaunchKernelGGL(noise_q_kernel, dim3((k + 63) / 64), dim3(64), 0, stream, ipart.p, nchunks, k, (double)(T - midx), qn.p);
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        std::vector<double> hs2(n), hcnt(n), hq(k);
+        double hp[2] = {0, 0};
+        TRMF_HIP_CHECK(hipMemcpyAsync(hs2.data(), s2.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(hcnt.data(), cnt.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(hq.data(), qn.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(hp, pooled.p, sizeof hp, hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (!(hp[1] > 0)) { res->no_entries = 1; return 0; }
+        // ---- commit ----
+        if (nz_sigma2.alloc(n, false) || nz_q.alloc(k, false)) return kFail;
+        TRMF_HIP_CHECK(hipMemcpyAsync(nz_sigma2.p, s2.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(nz_q.p, qn.p, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        nz_set = true;
+        res->pooled = hp[0] / hp[1];
+        res->s2_min = res->s2_max = hs2[0];
+        for (int j = 0; j < n; j++) {
+            res->s2_min = std::min(res->s2_min, hs2[j]); res->s2_max = std::max(res->s2_max, hs2[j]);
+            res->series_pooled += hcnt[j] > 0 ? 0 : 1;
+        }
+        res->q_min = res->q_max = hq[0];
+        for (int t = 0; t < k; t++) { res->q_min = std::min(res->q_min, hq[t]); res->q_max = std::max(res->q_max, hq[t]); }
+        return 0;
+    }
+    // the caller's variances (validated: finite, not negative) in place of fitted ones; every rank keeps its own copy
+    int set_noise(const double *sigma2, const double *q) {
+        if (sync()) return kFail;
+        FillStreamScope fill(stream);
+        DevBuf<double> a, b;
+        SyncStreamOnExit drain(stream);
+        if (a.upload(sigma2, n) || b.upload(q, k)) return kFail;
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        nz_sigma2.swap(a); nz_q.swap(b);
+        nz_set = true;
+        return 0;
+    }
+    int noise(double *sigma2, double *q) {
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (sigma2) TRMF_HIP_CHECK(hipMemcpy(sigma2, nz_sigma2.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        if (q) TRMF_HIP_CHECK(hipMemcpy(q, nz_q.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    // forecast() plus the predictive standard deviation and the interval sums (the caller has validated the arguments, checked that
+    // a noise is resident and synchronised the session).  The roll-out is forecast()'s; the outputs and the interval table change
+    // only when every step has succeeded -- an impulse response that overflows included.
+    int forecast_dist(int steps, bool clip, double threshold, double zq, const PyMatrix *truth, real *Ynew, real *Ysd, real *Wnew) {
+        FillStreamScope fill(stream);
+        const size_t NY = (size_t)steps * n, NW = (size_t)steps * k, NT7 = (size_t)n * kIvSums;
+        const bool score = truth != nullptr;
+        DevBuf<real> roll, flat, tru, yd, ysd;
+        DevBuf<double> v, psig;
+        DevBuf<int> flag;
+        std::vector<real> blk;
+        SyncStreamOnExit drain(stream);
+        if (roll.alloc((size_t)steps * KP) || v.alloc((size_t)steps * KP) || flag.alloc(1) || (Wnew && flat.alloc(NW, false)) ||
+            (Ynew && yd.alloc(NY, false)) || (Ysd && ysd.alloc(NY, false))) return kFail;
+        if (score) {
+            const real *src = (const real *)truth->val;
+            if (truth->type != TRMF_DENSE_ROWMAJOR) { (void)dense_rows_to_rowmajor(truth, blk); src = blk.data(); }
+            if (tru.upload(src, NY)) return kFail;
+            if (iv_table[0].n != NT7 || iv_table[1].n != NT7) {      // first scored call since a reset
+                if (iv_table[0].alloc(NT7) || iv_table[1].alloc(NT7)) return kFail;
+                iv_cur = 0; iv_rows = 0;
+            }
+        }
+        if (launch_rollout(W.p, T, steps, roll.p, Wnew ? flat.p : nullptr)) return kFail;
+        {
+            PsiArgs pa{lag_set.p, theta.p, nz_q.p, v.p, nullptr, flag.p, steps, k, KP, NT, nlag, 0};
+            const size_t lds = psi_lds_bytes(nlag, midx);
+            if (midx > 0 && lds <= kLdsMax && !test_env("TRMF_FORECAST_GLOBAL")) {
+                if (allow_dyn_lds(forecast_psi_kernel, lds, "impulse response")) return kFail;
+                pa.reach = midx;
+            } else {
+                if (psig.alloc(NW, false)) return kFail;
+                pa.psi_glob = psig.p;
+            }
+            hipLaunchKernelGGL(forecast_psi_kernel, dim3((k + 63) / 64), dim3(64), pa.reach ? lds : 0, stream, pa);
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        if (score || Ynew || Ysd) {
+            const int in = iv_cur, out = 1 - iv_cur;
+            DistArgs a{H.p, roll.p, v.p, nz_sigma2.p, score ? tru.p : nullptr, Ynew ? yd.p : nullptr, Ysd ? ysd.p : nullptr,
+                       has_transform ? tr_a.p : nullptr, has_transform ? tr_b.p : nullptr, score ? iv_table[in].p : nullptr, score ? iv_table[out].p : nullptr,
+                       (real)threshold, zq, clip ? 1 : 0, n, steps, KP, NT, dist_rows_per_pass(KP, generic)};
+            const dim3 grid((n + 255) / 256);
+            if (!with_nt0(generic ? 0 : NT, [&](auto N) { hipLaunchKernelGGL(forecast_dist_kernel<decltype(N)::value>, grid, dim3(256), 0, stream, a); }))
+                return unsupported_rank();
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        // the outputs come back through host staging (pinned memory of the library when they fit) and are copied out together
+        const size_t bY = Ynew ? NY * sizeof(real) : 0, bS = Ysd ? NY * sizeof(real) : 0, bW = Wnew ? NW * sizeof(real) : 0;
+        std::unique_lock<std::mutex> lease;
+        std::vector<unsigned char> fallback;
+        unsigned char *base = nullptr;
+        if (bY + bS + bW) {
+            base = HostStager::current().staging(bY + bS + bW, lease);
+            if (!base) {
+                try { fallback.resize(bY + bS + bW); } catch (const std::bad_alloc &) { set_error("host staging of the forecast: out of memory"); return kFail; }
+                base = fallback.data();
+            }
+            if (bY) TRMF_HIP_CHECK(hipMemcpyAsync(base, yd.p, bY, hipMemcpyDeviceToHost, stream));
+            if (bS) TRMF_HIP_CHECK(hipMemcpyAsync(base + bY, ysd.p, bS, hipMemcpyDeviceToHost, stream));
+            if (bW) TRMF_HIP_CHECK(hipMemcpyAsync(base + bY + bS, flat.p, bW, hipMemcpyDeviceToHost, stream));
+        }
+        int bad = 0;
+        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (bad) { set_error("forecast_dist: lag weights explosive over this horizon (a latent forecast variance is not finite); nothing was changed"); return kFail; }
+        // ---- commit ----
+        if (bY) HostStager::parallel_copy(Ynew, base, bY);
+        if (bS) HostStager::parallel_copy(Ysd, base + bY, bS);
+        if (bW) std::memcpy(Wnew, base + bY + bS, bW);
+        if (score) { iv_cur = 1 - iv_cur; iv_rows += (uint64_t)steps; }
+        return 0;
+    }
+    int interval_scores(uint64_t *rows_scored, double *per_series) {
+        const size_t NT7 = (size_t)n * kIvSums;
+        if (per_series) {
+            std::vector<double> h(NT7, 0.0);
+            if (iv_table[iv_cur].n == NT7) {
+                TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+                TRMF_HIP_CHECK(hipMemcpy(h.data(), iv_table[iv_cur].p, NT7 * sizeof(double), hipMemcpyDeviceToHost));
+            }
+            std::memcpy(per_series, h.data(), NT7 * sizeof(double));
+        }
+        if (rows_scored) *rows_scored = iv_rows;
+        return 0;
+    }
+    int interval_reset() {
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        for (int q = 0; q < 2; q++) iv_table[q].release();      // the next scored call starts from zeroed ones
+        iv_cur = 0; iv_rows = 0;
+        return 0;
+    }
     // ---- online updates (trmf_session_assimilate; online_kernels.hpp) ---------------------------------------------------------
     // Rows [first_row, T) of W re-solved in ascending order with H and Theta fixed (the caller has validated first_row, the lag set
     // and the rank).  Stage A rebuilds the Gram cache rows and right-hand sides of the range with the X phase's own builders -- every

@@ -218,6 +218,15 @@ struct SessionState {
     DevBuf<real> fc_prev[2];
     int fc_cur = 0;
     uint64_t fc_rows = 0;                     // forecast rows scored since the last reset
+    // ---- forecast uncertainty (trmf_session_fit_noise / _set_noise / _forecast_dist / _interval_scores; uncertainty_kernels.hpp) --
+    // The fitted (or set) observation noise per series and innovation variance per latent dimension, resident on every rank;
+    // run, assimilate, append_rows and rewind neither refit nor invalidate them (the caller decides when to refit).  The interval
+    // table: seven fp64 sums per series in two generations, switched after a call's last synchronisation like the point table.
+    DevBuf<double> nz_sigma2, nz_q;
+    bool nz_set = false;
+    DevBuf<double> iv_table[2];
+    int iv_cur = 0;
+    uint64_t iv_rows = 0;
     // fp32: four systems per wavefront (fsolve_quad_kernel); fp64: one system per wavefront, factorised in the MFMA
     // accumulator layout (fsolve_mfma_kernel)
     // X-side Gram build across ranks: sharded rows + all-gather of G (64 MB at config 3) pays only when a

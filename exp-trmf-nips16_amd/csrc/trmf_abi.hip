@@ -465,23 +465,26 @@ int32_t trmf_session_eval_heldout(TrmfSession *s, TrmfHeldoutSums *out, void *pr
     return rc;
 }
 // Forecast: like the held-out calls, every argument is checked on the calling thread before any rank's worker runs.
-int32_t trmf_session_forecast(TrmfSession *s, int32_t steps, int32_t clip, double threshold, const PyMatrix *truth, void *Ynew, void *Wnew) {
-    if (!s) { set_error("null session"); return kFail; }
-    const TrmfSessionImpl *f = HND(s)->first();
-    if (steps < 1) { set_error("forecast: steps must be at least 1"); return kFail; }
+static int check_forecast_args(const TrmfSessionImpl *f, const std::string &what, int32_t steps, int32_t clip, double threshold, const PyMatrix *truth) {
+    if (steps < 1) { set_error(what + ": steps must be at least 1"); return kFail; }
     if ((uint64_t)f->T + (uint64_t)steps + 1 >= (1ull << 24) || (uint64_t)steps * (uint64_t)f->n >= (1ull << 32)) {
-        set_error("forecast: the window would exceed 32-bit device indices"); return kFail;
+        set_error(what + ": the window would exceed 32-bit device indices"); return kFail;
     }
-    if (clip && !std::isfinite(threshold)) { set_error("forecast: the threshold must be finite"); return kFail; }
+    if (clip && !std::isfinite(threshold)) { set_error(what + ": the threshold must be finite"); return kFail; }
     if (truth) {
-        if (truth->type != TRMF_DENSE_ROWMAJOR && truth->type != TRMF_DENSE_COLMAJOR) { set_error("forecast: the truth must be a dense PyMatrix"); return kFail; }
+        if (truth->type != TRMF_DENSE_ROWMAJOR && truth->type != TRMF_DENSE_COLMAJOR) { set_error(what + ": the truth must be a dense PyMatrix"); return kFail; }
         if (truth->rows != (uint64_t)steps || truth->cols != (uint64_t)f->n) {
-            set_error("forecast: the truth is " + std::to_string(truth->rows) + " x " + std::to_string(truth->cols) + ", the forecast " + std::to_string(steps) +
+            set_error(what + ": the truth is " + std::to_string(truth->rows) + " x " + std::to_string(truth->cols) + ", the forecast " + std::to_string(steps) +
                       " x " + std::to_string(f->n));
             return kFail;
         }
-        if (!truth->val) { set_error("forecast: the truth lacks its values"); return kFail; }
+        if (!truth->val) { set_error(what + ": the truth lacks its values"); return kFail; }
     }
+    return 0;
+}
+int32_t trmf_session_forecast(TrmfSession *s, int32_t steps, int32_t clip, double threshold, const PyMatrix *truth, void *Ynew, void *Wnew) {
+    if (!s) { set_error("null session"); return kFail; }
+    if (check_forecast_args(HND(s)->first(), "forecast", steps, clip, threshold, truth)) return kFail;
     DeviceGuard guard;
     if (!guard.ok) return kFail;
     if (HND(s)->all([&](TrmfSessionImpl *t) { return t->sync(); })) return kFail;       // every rank holds the same factors: rank 0 answers
@@ -556,6 +559,71 @@ int32_t trmf_session_assimilate(TrmfSession *s, int32_t first_row, TrmfAssimilat
         }
     if (out) { out->rows = res[0].rows; out->entries = res[0].entries; out->sq_err_before = res[0].sq_err_before; out->sq_err_after = res[0].sq_err_after; }
     return 0;
+}
+
+// Forecast uncertainty: the arguments are checked on the calling thread before any rank's worker runs (see trmf_session_set_heldout);
+// a training matrix without a stored entry is found by every rank alike and reported here, not by a failing worker task.
+int32_t trmf_session_fit_noise(TrmfSession *s, TrmfNoiseStats *out) {
+    if (!s) { set_error("null session"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (f->T <= f->midx) {
+        set_error("fit_noise: " + std::to_string(f->T) + " rows do not reach past the largest lag " + std::to_string(f->midx));
+        return kFail;
+    }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    const bool grouped = HND(s)->group != nullptr;
+    std::vector<TrmfSessionImpl::NoiseResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
+    if (HND(s)->all([&](TrmfSessionImpl *t) { return t->fit_noise(&res[grouped ? t->comm->rank : 0]); })) return kFail;
+    for (const auto &r : res)
+        if (r.no_entries) { set_error("fit_noise: the training matrix has no stored entry; nothing was changed"); return kFail; }
+    if (out) {
+        out->pooled_sigma2 = res[0].pooled; out->sigma2_min = res[0].s2_min; out->sigma2_max = res[0].s2_max;
+        out->series_pooled = res[0].series_pooled; out->q_min = res[0].q_min; out->q_max = res[0].q_max;
+    }
+    return 0;
+}
+int32_t trmf_session_noise(TrmfSession *s, double *sigma2, double *q) {
+    if (!s) { set_error("null session"); return kFail; }
+    if (!HND(s)->first()->nz_set) { set_error("noise: none has been fitted or set (trmf_session_fit_noise / _set_noise)"); return kFail; }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    return HND(s)->rank0([&](TrmfSessionImpl *t) { return t->noise(sigma2, q); });
+}
+int32_t trmf_session_set_noise(TrmfSession *s, const double *sigma2, const double *q) {
+    if (!s || !sigma2 || !q) { set_error("set_noise: null session or table"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    for (int j = 0; j < f->n; j++)
+        if (!(std::isfinite(sigma2[j]) && sigma2[j] >= 0)) { set_error("set_noise: sigma2[" + std::to_string(j) + "] is negative or not finite"); return kFail; }
+    for (int t = 0; t < f->k; t++)
+        if (!(std::isfinite(q[t]) && q[t] >= 0)) { set_error("set_noise: q[" + std::to_string(t) + "] is negative or not finite"); return kFail; }
+    DeviceGuard guard;
+    return guard.ok ? HND(s)->all([&](TrmfSessionImpl *t) { return t->set_noise(sigma2, q); }) : kFail;
+}
+int32_t trmf_session_forecast_dist(TrmfSession *s, int32_t steps, int32_t clip, double threshold, double zq, const PyMatrix *truth,
+                                   void *Ynew, void *Ysd, void *Wnew) {
+    if (!s) { set_error("null session"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (!f->nz_set) { set_error("forecast_dist: no noise has been fitted or set (trmf_session_fit_noise / _set_noise)"); return kFail; }
+    if (!(std::isfinite(zq) && zq > 0)) { set_error("forecast_dist: zq must be positive and finite"); return kFail; }
+    if (check_forecast_args(f, "forecast_dist", steps, clip, threshold, truth)) return kFail;
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    if (HND(s)->all([&](TrmfSessionImpl *t) { return t->sync(); })) return kFail;       // every rank holds the same factors: rank 0 answers
+    return HND(s)->rank0([&](TrmfSessionImpl *t) { return t->forecast_dist(steps, clip != 0, threshold, zq, truth, (real *)Ynew, (real *)Ysd, (real *)Wnew); });
+}
+int32_t trmf_session_interval_scores(TrmfSession *s, uint64_t *rows_scored, TrmfIntervalSums *per_series) {
+    if (!s) { set_error("null session"); return kFail; }
+    static_assert(sizeof(TrmfIntervalSums) == kIvSums * sizeof(double), "the resident table is an array of TrmfIntervalSums");
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    return HND(s)->rank0([&](TrmfSessionImpl *t) { return t->interval_scores(rows_scored, reinterpret_cast<double *>(per_series)); });
+}
+int32_t trmf_session_interval_reset(TrmfSession *s) {
+    if (!s) { set_error("null session"); return kFail; }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    return HND(s)->rank0([&](TrmfSessionImpl *t) { return t->interval_reset(); });
 }
 
 // ---- multi-GPU ----------------------------------------------------------------------------------

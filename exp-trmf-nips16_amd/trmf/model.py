@@ -141,6 +141,31 @@ class Model(object):
             Ynew[:] = self.transform.postprocess(Ynew)
         return Ynew, Wnew
 
+    # ---- forecast uncertainty ----------------------------------------------------------------------
+    def fit_noise(self, Y, missing=True):
+        """Fit the observation noise per series and the innovation variance per latent dimension of this model on its
+        training matrix ``Y`` (raw values; a transform of this model is applied first) and keep them as ``self.noise =
+        (sigma2, q)`` (``trmf.uncertainty.fit_noise``; the host form of ``Session.fit_noise``).  Returns ``self``."""
+        from .uncertainty import fit_noise
+        if self.transform is not None:
+            if smat.issparse(Y):
+                raise ValueError('fit_noise: a series transform needs a dense Y')
+            Y = self.transform.preprocess(np.asarray(Y)).astype(self.W.dtype)
+            if missing:
+                Y = smat.csr_matrix(Y)
+        sigma2, q, _ = fit_noise(self.W, self.H, self.lag_set, self.lag_val, Y, missing)
+        self.noise = (sigma2, q)
+        return self
+
+    def forecast_std(self, window):
+        """Predictive standard deviation (window x n) of ``forecast(window)``, in the units ``forecast`` reports; needs
+        ``fit_noise`` first.  A plug-in estimate: see ``trmf.uncertainty``."""
+        from .uncertainty import forecast_std
+        noise = getattr(self, 'noise', None)
+        if noise is None:
+            raise ValueError('forecast_std: no noise fitted (Model.fit_noise)')
+        return forecast_std(self.H, self.lag_set, self.lag_val, noise[0], noise[1], window, transform=self.transform)
+
     # ---- online update ----------------------------------------------------------------------------
     def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True):
         """A new ``Model`` grown by the ``Ynew.shape[0]`` timestamps of ``Ynew`` (raw values; a transform of this model is

@@ -53,6 +53,25 @@ class TrmfAssimilateSums(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TrmfNoiseStats(ctypes.Structure):
+    """Summary of a noise fit (include/trmf_abi.h)."""
+    _fields_ = [('pooled_sigma2', c_double), ('sigma2_min', c_double), ('sigma2_max', c_double), ('series_pooled', c_uint64),
+                ('q_min', c_double), ('q_max', c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TrmfIntervalSums(ctypes.Structure):
+    """One series' interval sums over the scored forecasts (include/trmf_abi.h); ``IntervalMetrics.from_series_sums`` turns the
+    table into scores."""
+    _fields_ = [('cells', c_double), ('covered', c_double), ('sd_sum', c_double), ('abs_truth', c_double), ('z2_sum', c_double),
+                ('nll_sum', c_double), ('crps_sum', c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class TrmfTrainProfile(ctypes.Structure):
     """Split of the last c_trmf_train call of this process (include/trmf_abi.h)."""
     _fields_ = [('total_s', c_double), ('setup_s', c_double), ('upload_s', c_double), ('compute_s', c_double),
@@ -120,6 +139,15 @@ def bind(lib):
     if hasattr(lib, 'trmf_session_assimilate'):       # (absent from libraries built before the online updates)
         lib.trmf_session_assimilate.argtypes = [c_void_p, c_int32, POINTER(TrmfAssimilateSums), c_void_p]
         lib.trmf_session_assimilate.restype = c_int32
+    if hasattr(lib, 'trmf_session_fit_noise'):        # (absent from libraries built before the forecast uncertainty)
+        lib.trmf_session_fit_noise.argtypes = [c_void_p, POINTER(TrmfNoiseStats)]; lib.trmf_session_fit_noise.restype = c_int32
+        lib.trmf_session_noise.argtypes = [c_void_p, c_void_p, c_void_p]; lib.trmf_session_noise.restype = c_int32
+        lib.trmf_session_set_noise.argtypes = [c_void_p, c_void_p, c_void_p]; lib.trmf_session_set_noise.restype = c_int32
+        lib.trmf_session_forecast_dist.argtypes = [c_void_p, c_int32, c_int32, c_double, c_double, P, c_void_p, c_void_p, c_void_p]
+        lib.trmf_session_forecast_dist.restype = c_int32
+        lib.trmf_session_interval_scores.argtypes = [c_void_p, POINTER(c_uint64), c_void_p]
+        lib.trmf_session_interval_scores.restype = c_int32
+        lib.trmf_session_interval_reset.argtypes = [c_void_p]; lib.trmf_session_interval_reset.restype = c_int32
     lib.trmf_dist_get_unique_id.argtypes = [c_void_p]; lib.trmf_dist_get_unique_id.restype = c_int32
     lib.trmf_dist_init.argtypes = [c_int32, c_int32, c_void_p]; lib.trmf_dist_init.restype = c_int32
     lib.trmf_dist_init_callback.argtypes = [c_int32, c_int32, ALLGATHERV_FN, c_void_p]
@@ -328,6 +356,20 @@ class Session(object):
             return ImputeMetrics.from_sums(sums), pred
         return ImputeMetrics.from_sums(self.eval_heldout_sums())
 
+    def _truth_matrix(self, truth, what):
+        """The truth of a forecast as a PyMatrix of the session's dtype (``None`` stays ``None``)."""
+        dt = np.dtype(self.model.W.dtype)
+        if truth is None or isinstance(truth, PyMatrix):
+            return truth
+        if smat.issparse(truth):
+            return PyMatrix(truth, dtype=dt)               # refused by the library: the truth of a forecast is dense
+        truth = np.asarray(truth)
+        if truth.dtype != dt:
+            raise TypeError('{}: the truth is {}, the session forecasts in {}'.format(what, truth.dtype, dt))
+        if truth.ndim != 2:
+            raise ValueError('{}: the truth must be a steps x n array'.format(what))
+        return PyMatrix(truth, dtype=dt)
+
     def forecast(self, steps, threshold=None, truth=None, return_forecast=True, return_latent=False):
         """The next ``steps`` timestamps from the current factors, on the device: W rolled forward by the AR model (the bits of
         ``Model.latent_forecast``), times H, clipped from below at ``threshold`` if one is given, mapped back through the session's
@@ -337,19 +379,7 @@ class Session(object):
         dt = np.dtype(self.model.W.dtype)
         n, k = self.model.n, self.model.k
         steps = int(steps)
-        pyT = None
-        if truth is not None:
-            if isinstance(truth, PyMatrix):
-                pyT = truth
-            elif smat.issparse(truth):
-                pyT = PyMatrix(truth, dtype=dt)            # refused by the library: the truth of a forecast is dense
-            else:
-                truth = np.asarray(truth)
-                if truth.dtype != dt:
-                    raise TypeError('forecast: the truth is {}, the session forecasts in {}'.format(truth.dtype, dt))
-                if truth.ndim != 2:
-                    raise ValueError('forecast: the truth must be a steps x n array')
-                pyT = PyMatrix(truth, dtype=dt)
+        pyT = self._truth_matrix(truth, 'forecast')
         Ynew = np.empty((max(steps, 0), n), dtype=dt) if return_forecast else None
         Wnew = np.empty((max(steps, 0), k), dtype=dt) if return_latent else None
         self._check(self.lib.trmf_session_forecast(
@@ -374,6 +404,78 @@ class Session(object):
 
     def reset_forecast_scores(self):
         self._check(self.lib.trmf_session_forecast_reset(self.handle), 'trmf_session_forecast_reset')
+        return self
+
+    # ---- forecast uncertainty (trmf.uncertainty is the same computation in NumPy) ------------------------------------------
+    def fit_noise(self):
+        """Fit the observation noise per series and the innovation variance per latent dimension on the session's current factors
+        and training matrix, on the device, into resident tables (``trmf.uncertainty.fit_noise``).  Later ``run`` /
+        ``assimilate`` / ``append_rows`` / ``rewind`` calls neither refit nor invalidate them: call again when the model has
+        moved.  Returns ``{'pooled_sigma2', 'sigma2_min', 'sigma2_max', 'series_pooled', 'q_min', 'q_max'}``."""
+        stats = TrmfNoiseStats()
+        self._check(self.lib.trmf_session_fit_noise(self.handle, byref(stats)), 'trmf_session_fit_noise')
+        return stats.as_dict()
+
+    def noise(self):
+        """``(sigma2, q)``: the resident variances, n and k float64 values."""
+        sigma2, q = np.zeros(self.model.n, dtype=np.float64), np.zeros(self.model.k, dtype=np.float64)
+        self._check(self.lib.trmf_session_noise(self.handle, sigma2.ctypes.data, q.ctypes.data), 'trmf_session_noise')
+        return sigma2, q
+
+    def set_noise(self, sigma2, q):
+        """Replace the resident variances (finite, not negative), e.g. by out-of-sample ones."""
+        sigma2 = np.ascontiguousarray(sigma2, dtype=np.float64).ravel()
+        q = np.ascontiguousarray(q, dtype=np.float64).ravel()
+        if sigma2.shape != (self.model.n,) or q.shape != (self.model.k,):
+            raise ValueError('set_noise: sigma2 must have n = {} values and q k = {}'.format(self.model.n, self.model.k))
+        self._check(self.lib.trmf_session_set_noise(self.handle, sigma2.ctypes.data, q.ctypes.data), 'trmf_session_set_noise')
+        return self
+
+    def forecast_dist(self, steps, level=0.9, threshold=None, truth=None, return_latent=False):
+        """``(Ynew, Ysd)`` -- or ``(Ynew, Ysd, Wnew)`` -- of the next ``steps`` timestamps: ``Ynew`` (and ``Wnew``) exactly as
+        ``forecast`` returns them, ``Ysd`` the predictive standard deviation in the same units.  Needs ``fit_noise`` or
+        ``set_noise`` first.  With ``truth`` the cells are scored into the resident interval table (``interval_scores``), the
+        central ``level`` interval deciding ``coverage``.  A plug-in estimate: see ``trmf.uncertainty``."""
+        from .uncertainty import z_of_level
+        dt = np.dtype(self.model.W.dtype)
+        n, k = self.model.n, self.model.k
+        steps = int(steps)
+        zq = z_of_level(level)
+        pyT = self._truth_matrix(truth, 'forecast_dist')
+        Ynew = np.empty((max(steps, 0), n), dtype=dt)
+        Ysd = np.empty((max(steps, 0), n), dtype=dt)
+        Wnew = np.empty((max(steps, 0), k), dtype=dt) if return_latent else None
+        self._check(self.lib.trmf_session_forecast_dist(
+            self.handle, steps, int(threshold is not None), float(threshold) if threshold is not None else 0.0, zq,
+            byref(pyT) if pyT is not None else None, Ynew.ctypes.data, Ysd.ctypes.data,
+            Wnew.ctypes.data if Wnew is not None else None), 'trmf_session_forecast_dist')
+        return (Ynew, Ysd, Wnew) if return_latent else (Ynew, Ysd)
+
+    def forecast_interval(self, steps, level=0.9, threshold=None, truth=None):
+        """``(Ynew, lo, hi)``: the forecast and its central ``level`` interval ``Ynew -+ zq Ysd`` (``lo`` clipped from below at
+        ``threshold`` when one is given)."""
+        from .uncertainty import z_of_level
+        Ynew, Ysd = self.forecast_dist(steps, level=level, threshold=threshold, truth=truth)
+        half = Ysd * Ynew.dtype.type(z_of_level(level))
+        lo, hi = Ynew - half, Ynew + half
+        if threshold is not None:
+            np.maximum(lo, Ynew.dtype.type(threshold), out=lo)
+        return Ynew, lo, hi
+
+    def interval_series_sums(self):
+        """(rows scored by ``forecast_dist`` since the last reset, n x 7 float64 table in ``TrmfIntervalSums`` order)."""
+        rows = c_uint64(0)
+        table = np.zeros((self.model.n, len(TrmfIntervalSums._fields_)), dtype=np.float64)
+        self._check(self.lib.trmf_session_interval_scores(self.handle, byref(rows), table.ctypes.data), 'trmf_session_interval_scores')
+        return int(rows.value), table
+
+    def interval_scores(self, level=0.9):
+        """``IntervalMetrics`` of every cell scored since the last reset; ``level`` must be the one the calls were scored with."""
+        from .uncertainty import IntervalMetrics
+        return IntervalMetrics.from_series_sums(self.interval_series_sums()[1], level)
+
+    def reset_interval_scores(self):
+        self._check(self.lib.trmf_session_interval_reset(self.handle), 'trmf_session_interval_reset')
         return self
 
     def download(self):

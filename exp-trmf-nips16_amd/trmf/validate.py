@@ -63,10 +63,12 @@ def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing,
 
 
 def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag=None,
-                             assimilate=False):
+                             assimilate=False, interval_level=None):
     """The whole rolling evaluation from one resident session: every window is trained, forecast and scored on the device
     (``Session.forecast`` with the window's truth), the next window's rows are appended and, if asked for, a transform
-    refitted on the grown prefix is handed over.  No factor is downloaded and no host model is rebuilt between windows."""
+    refitted on the grown prefix is handed over.  No factor is downloaded and no host model is rebuilt between windows.  With an
+    ``interval_level`` every window also refits the noise (``Session.fit_noise``) and scores its predictive distribution
+    (``Session.forecast_dist``) next to the point forecast; the result is then ``(Metrics, IntervalMetrics)``."""
     from .session import Session
     model = Model.initialize(Y[:cuts[0]], lag_set, k, seed=seed, transform=transform)
     with Session(_as_training_matrix(Y[:cuts[0]], missing), model, missing=missing, verbose=verbose,
@@ -82,7 +84,13 @@ def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_
                 sess.assimilate(cuts[i - 1])        # online: the appended rows are filtered in, nothing is retrained
             else:
                 sess.run(max_iter)
-            sess.forecast(window_size, threshold=threshold, truth=np.ascontiguousarray(Y[cut:cut + window_size]), return_forecast=False)
+            truth = np.ascontiguousarray(Y[cut:cut + window_size])
+            sess.forecast(window_size, threshold=threshold, truth=truth, return_forecast=False)
+            if interval_level is not None:
+                sess.fit_noise()
+                sess.forecast_dist(window_size, level=interval_level, threshold=threshold, truth=truth)
+        if interval_level is not None:
+            return sess.forecast_scores(), sess.interval_scores(interval_level)
         return sess.forecast_scores()
 
 
@@ -99,8 +107,11 @@ def _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, tr
 
 def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5, lambdaAR=50, lambdaLag=0.5,
                      max_iter=20, missing=True, threshold=0, transform=None, threads=16, verbose=0, seed=0,
-                     resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False, update='retrain'):
-    """``update='assimilate'``: window 0 is trained with ``max_iter`` iterations, every later window appends its rows and
+                     resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False, update='retrain', interval_level=None):
+    """``interval_level`` (e.g. 0.9; needs ``forecast_on_device=True``): every window also fits the noise of its trained model and
+    scores the predictive distribution of its forecast on the device; the result is ``(Metrics, IntervalMetrics)``, the ``Metrics``
+    being exactly those of the call without it.
+    ``update='assimilate'``: window 0 is trained with ``max_iter`` iterations, every later window appends its rows and
     absorbs them by the forward filter (``Session.update``) instead of retraining; it needs the resident path and refuses a
     per-window transform (a refitted transform rescales the whole history, which an online update does not revisit).
     ``lambdaLagL1`` / ``lag_refit``: sparse lag weights (``Session.set_lag_penalty``) on every path.
@@ -122,6 +133,11 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
             raise ValueError("update='assimilate': a per-window transform rescales the whole history, which an online update does not revisit")
         if not resident or not isinstance(Y, np.ndarray):
             raise ValueError("update='assimilate': needs the resident path (resident=True and a dense NumPy Y)")
+    if interval_level is not None:
+        from .uncertainty import z_of_level
+        z_of_level(interval_level)
+        if not forecast_on_device:
+            raise ValueError('interval_level: the intervals are fitted and scored on the device (forecast_on_device=True)')
     if forecast_on_device:
         if not isinstance(Y, np.ndarray):
             raise ValueError('forecast_on_device: needs a dense NumPy Y (a sparse Y has no resident rolling evaluation)')
@@ -132,7 +148,8 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
         if transform is not None and missing:
             raise ValueError('forecast_on_device: a transform with missing=True is refitted on the host per window; '
                              'the device applies one only to dense full-observation training (missing=False)')
-        return _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag, online)
+        return _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag, online,
+                                        interval_level)
     # resident: a NumPy Y, and a transform only where the device can apply it (dense full-observation training)
     if resident and isinstance(Y, np.ndarray) and (transform is None or (not missing and Y.dtype in (np.float32, np.float64))):
         models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag, online)

@@ -345,6 +345,60 @@ typedef struct {
 TRMF_API int32_t trmf_session_assimilate(TrmfSession *s, int32_t first_row, TrmfAssimilateSums *out /* or NULL */,
                                          void *Wnew /* or NULL: (rows - first_row) x k, row-major */);
 
+/* --- forecast uncertainty: noise fit, predictive standard deviation and interval scores ---------------------------------
+ * TRMF read as a linear-Gaussian state-space model (the paper's own reading): y_ij = w_i . h_j + eps_ij with eps_ij ~ N(0, sigma_j^2),
+ * every latent dimension t an AR process with innovation variance q_t.  With m the largest lag and T = trmf_session_rows():
+ *   sigma_j^2 = (1/|Omega_j|) sum_{i in Omega_j} (y_ij - w_i . h_j)^2   over the stored entries of series j (missing != 0), or over
+ *               every timestamp with an absent entry reading as 0 (missing == 0, |Omega_j| = T); y is the value the session trains
+ *               on; products, dot product, difference, square and sum in fp64 from the stored element-type values.  A series
+ *               without a stored entry takes the pooled value sum_j sq_j / sum_j cnt_j (both summed in series order)
+ *   q_t       = (1/(T - m)) sum_{i >= m} (w_i[t] - p_i[t])^2,  p_i the one-step latent forecast formed as the roll-out forms it
+ *               (products rounded to the element type, ascending lag order); difference, square and sum in fp64
+ *   psi_t[0] = 1, psi_t[s] = sum_{l: lag_l <= s} lag_val(l, t) psi_t[s - lag_l]  (fp64);   v_t[s] = q_t sum_{u <= s} psi_t[u]^2
+ *   V[s][j]  = sigma_j^2 + sum_t H[j][t]^2 v_t[s]     the predictive variance of the forecast of series j, s + 1 steps ahead
+ *   sd[s][j] = sqrt(V[s][j]) (/ |a_j| under an active series transform y -> a_j y + b_j), rounded once to the element type
+ * A PLUG-IN interval: it ignores the estimation error of H, of the lag weights and of the last rows of W, and the residuals are
+ * in-sample ones, so it is too narrow where the model overfits.  trmf_session_set_noise is the hook for a caller who has
+ * out-of-sample variances (for example TrmfSeriesSums.sq_err of earlier windows).  Every sum is formed in a fixed order without
+ * atomics: repeated calls, and every rank, give the same bits.
+ *
+ * None of these calls touches the point-score table and its kept truth row, the trajectory and the iteration counter, the
+ * statistics, the mark or the measured multi-rank decisions. */
+typedef struct {
+    double pooled_sigma2;                  /* sum_j sq_j / sum_j cnt_j                                     */
+    double sigma2_min, sigma2_max;         /* over the series, those that took the pooled value included  */
+    uint64_t series_pooled;                /* series without a stored entry                                */
+    double q_min, q_max;
+} TrmfNoiseStats;
+/* Fit sigma_j^2 (n doubles) and q_t (k doubles) on the current factors into resident tables.  Blocking, ordered after every
+ * run() enqueued before; every rank computes on its own copy (no exchange).  Later run / assimilate / append_rows / rewind calls
+ * neither refit nor invalidate the tables: the caller decides when to refit.  out may be NULL.  0, or -1 with
+ * trmf_last_error() (rows <= the largest lag, a training matrix without a stored entry, a device failure) with the tables as
+ * they were. */
+TRMF_API int32_t trmf_session_fit_noise(TrmfSession *s, TrmfNoiseStats *out /* or NULL */);
+/* Read (either pointer may be NULL) / replace the resident tables.  -1 when none has been fitted or set (noise), or for a
+ * value that is negative or not finite (set_noise; the tables stay as they were). */
+TRMF_API int32_t trmf_session_noise(TrmfSession *s, double *sigma2 /* n */, double *q /* k */);
+TRMF_API int32_t trmf_session_set_noise(TrmfSession *s, const double *sigma2 /* n */, const double *q /* k */);
+/* Seven fp64 sums per series over the scored cells (e = truth - mean, z = e / sd, both from the two element-type values the call
+ * stores): cells; covered = the number with |e| <= zq sd; sd_sum; abs_truth = sum |truth|; z2_sum; nll_sum = sum of
+ * log(2 pi sd^2)/2 + z^2/2; crps_sum = sum of sd (z (2 Phi(z) - 1) + 2 phi(z) - 1/sqrt(pi)), Phi through the fp64 erf.  A series'
+ * cells are added in timestamp order by one thread. */
+typedef struct {
+    double cells, covered, sd_sum, abs_truth, z2_sum, nll_sum, crps_sum;
+} TrmfIntervalSums;
+/* trmf_session_forecast plus the predictive standard deviation: the same arguments, zq > 0 (the normal quantile of the interval
+ * scored into `covered`) and Ysd (NULL, or steps x n reals, row-major, in the units of Ynew).  Ynew and Wnew are bit for bit what
+ * trmf_session_forecast returns.  With a truth the interval table grows (not the point-score table).  0, or -1 with
+ * trmf_last_error() -- before any device work: no noise fitted or set, zq not positive and finite, and every reason
+ * trmf_session_forecast refuses; after it: lag weights explosive over this horizon (a v_t[s] that is not finite), a device
+ * failure -- with Ynew, Ysd, Wnew and the table as they were.  With TRMF_DEVICES rank 0 forecasts. */
+TRMF_API int32_t trmf_session_forecast_dist(TrmfSession *s, int32_t steps, int32_t clip, double threshold, double zq,
+                                            const PyMatrix *truth, void *Ynew, void *Ysd, void *Wnew);
+/* rows_scored: NULL, or the forecast rows scored by forecast_dist since the last reset; per_series: NULL, or n records. */
+TRMF_API int32_t trmf_session_interval_scores(TrmfSession *s, uint64_t *rows_scored, TrmfIntervalSums *per_series);
+TRMF_API int32_t trmf_session_interval_reset(TrmfSession *s);
+
 /* --- multi-GPU (one process per GPU; RCCL all-gathers over xGMI) ---------------------------- */
 #define TRMF_UNIQUE_ID_BYTES 128
 /* Rank 0: create an RCCL unique id; the caller broadcasts the bytes to all ranks
