@@ -249,7 +249,10 @@ class Session(object):
         observations and the AR prior of the rows before them, with H and the lag weights fixed (``trmf.online.filter_rows``
         is the same computation in NumPy).  Returns ``{'rows', 'entries', 'sq_err_before', 'sq_err_after'}`` -- right after
         ``append_rows`` the third is the one-step-ahead forecast error of the block -- or ``(sums, Wnew)`` with
-        ``return_latent``.  A refused call (lag 0 in the lag set, rank above 64, ``first_row`` below the largest lag, a row
+        ``return_latent``.  The session's arrays are taken as they are: a cell stored several times is several observations
+        with ``missing`` (each in the row's system, in ``entries`` and in the squared errors); without, its values add up in
+        the right-hand side and the squared error of the cell is ``p^2 + sum_e y_e (y_e - 2 p)``, as in the training objective
+        (``||Y||^2`` is the sum of squares of the stored values), not ``(sum_e y_e - p)^2``.  A refused call (lag 0 in the lag set, rank above 64, ``first_row`` below the largest lag, a row
         whose system is not positive definite) raises and leaves the session as it was."""
         first_row = int(first_row)
         sums = TrmfAssimilateSums()
@@ -411,7 +414,9 @@ class Session(object):
         """Fit the observation noise per series and the innovation variance per latent dimension on the session's current factors
         and training matrix, on the device, into resident tables (``trmf.uncertainty.fit_noise``).  Later ``run`` /
         ``assimilate`` / ``append_rows`` / ``rewind`` calls neither refit nor invalidate them: call again when the model has
-        moved.  Returns ``{'pooled_sigma2', 'sigma2_min', 'sigma2_max', 'series_pooled', 'q_min', 'q_max'}``."""
+        moved.  A cell that sparse storage holds several times counts as the training objective counts it (one residual per
+        stored entry with ``missing``; ``p^2 + sum_e y_e (y_e - 2 p)`` without).
+        Returns ``{'pooled_sigma2', 'sigma2_min', 'sigma2_max', 'series_pooled', 'q_min', 'q_max'}``."""
         stats = TrmfNoiseStats()
         self._check(self.lib.trmf_session_fit_noise(self.handle, byref(stats)), 'trmf_session_fit_noise')
         return stats.as_dict()

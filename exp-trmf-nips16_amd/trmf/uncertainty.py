@@ -44,6 +44,10 @@ def fit_noise(W, H, lag_set, lag_val, Y, missing=True):
 
     ``sigma2[j] = (1 / |Omega_j|) sum_{i in Omega_j} (y_ij - w_i . h_j)^2`` over the stored entries of series j (``missing``;
     ``Y`` must be sparse), or over every timestamp with an absent entry of a sparse ``Y`` reading as 0 (``missing=False``).
+    A cell that a sparse ``Y`` stores several times is read as the training objective reads it: with ``missing`` every stored
+    entry is a residual of its own (and counts in ``|Omega_j|``); without, ``||Y||^2`` is the sum of squares of the stored
+    values and ``Y . W H^T`` adds them, so the cell contributes ``p^2 + sum_e y_e (y_e - 2 p)`` and counts once -- not
+    ``(sum_e y_e - p)^2``, which a caller gets by summing duplicates first.
     Products, dot product, difference, square and sum are fp64, formed from the stored values of W, H and Y.  A series without
     a stored entry takes the pooled value ``sum_j sq_j / sum_j cnt_j`` (both summed in series order).
 
@@ -71,9 +75,20 @@ def fit_noise(W, H, lag_set, lag_val, Y, missing=True):
         sq = np.bincount(coo.col, weights=res * res, minlength=n).astype(np.float64)
         cnt = np.bincount(coo.col, minlength=n).astype(np.float64)
     else:
-        dense = np.asarray(Y.toarray() if smat.issparse(Y) else Y, dtype=np.float64)
+        if smat.issparse(Y):
+            # the stored entries as they are (scipy's own astype would add repeated cells first, in Y's element type)
+            coo = Y.tocoo()
+            y = coo.data.astype(np.float64)
+            dense = smat.coo_matrix((y, (coo.row, coo.col)), shape=Y.shape).toarray()
+        else:
+            dense = np.asarray(Y, dtype=np.float64)
         res = dense - W64.dot(H64.T)
-        sq = (res * res).sum(axis=0)
+        cell = res * res
+        if smat.issparse(Y):
+            # a cell stored several times: (sum_e y_e - p)^2 less the cross terms (sum_e y_e)^2 - sum_e y_e^2 (exactly 0 for a
+            # cell stored once, so a canonical matrix keeps its bits)
+            cell = cell - (dense * dense - smat.coo_matrix((y * y, (coo.row, coo.col)), shape=Y.shape).toarray())
+        sq = cell.sum(axis=0)
         cnt = np.full(n, float(T))
     total_cnt = _sequential_sum(cnt)
     if total_cnt == 0:

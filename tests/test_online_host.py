@@ -112,6 +112,115 @@ def test_yardstick_of_the_device_tests_stays_small(k, lamI, lamAR):
         assert dev <= 1e-5
 
 
+def _inputs_as_first_written(k, density=0.3, lags=OH.LAGS):
+    """The recipe of online_helpers.inputs before it took a shape, kept here word for word."""
+    rng = np.random.RandomState(1000 + k)
+    W = rng.rand(96, k).astype(np.float32)
+    H = rng.rand(50, k).astype(np.float32)
+    theta = rng.randn(len(lags), k)
+    theta = np.asfortranarray((theta / (np.abs(theta).sum(axis=0) + 0.1)).astype(np.float32))
+    mask = rng.rand(96, 50) < density
+    mask[77] = False
+    mask[83] = False
+    mask[83, 17] = True
+    vals = rng.rand(96, 50).astype(np.float32)
+    vals[vals == 0] = 0.5
+    return W, H, theta, smat.csr_matrix(np.where(mask, vals, np.float32(0)).astype(np.float32))
+
+
+@pytest.mark.parametrize('k,density', [(1, 0.3), (16, 0.3), (40, 0.7), (64, 1.0)])
+def test_generalised_inputs_return_the_old_arrays_for_the_old_arguments(k, density):
+    W, H, theta, Y = _inputs_as_first_written(k, density)
+    for d in (OH.inputs(k, density), OH.inputs(k, density, OH.LAGS, OH.T, OH.N, OH.FIRST)):
+        assert np.array_equal(d['W'], W) and np.array_equal(d['H'], H) and np.array_equal(d['theta'], theta)
+        assert d['theta'].flags.f_contiguous and d['lag_set'].tolist() == list(OH.LAGS) and d['k'] == k
+        assert np.array_equal(d['Y'].indptr, Y.indptr) and np.array_equal(d['Y'].indices, Y.indices) and np.array_equal(d['Y'].data, Y.data)
+    other = OH.inputs(16, 0.3, (1, 7, 30), 64, 50, 40)                      # another shape: the designed rows move with first
+    assert other['W'].shape == (64, 16) and other['Y'].shape == (64, 50) and other['theta'].shape == (3, 16)
+    assert other['Y'][45].nnz == 0 and other['Y'][51].nnz == 1
+
+
+@pytest.mark.parametrize('missing', [True, False])
+@pytest.mark.parametrize('k', [7, 40])
+def test_row_systems_reproduce_filter_rows_in_fp64(k, missing):
+    """The fp64 systems the conditioning tests measure the device by (online_helpers.row_systems, prior_of), solved by NumPy,
+    are the rows of filter_rows in fp64 to 1e-10 on the standard input -- and the per-entry model of the raw-sparse tests is too."""
+    d = OH.inputs(k)
+    lamI, lamAR = OH.LAMBDAS[1]
+    W = OH.twin(d, np.float64, lamI, lamAR, missing)
+    S = OH.row_systems(d, np.float64, lamI, lamAR, missing)
+    assert len(S) == OH.TN
+    for r, (A, b) in enumerate(S):
+        i = OH.FIRST + r
+        x = np.linalg.solve(A, b + lamAR * OH.prior_of(W, i, d['lag_set'], d['theta'].astype(np.float64)))
+        assert relmax(x, W[i]) <= 1e-10, i
+    eta = OH.row_backward_errors(d, S, W, np.float64, lamAR)
+    assert eta.max() <= 8 * 2.0 ** -53
+    c = d['Y'].tocoo()
+    assert relmax(OH.entry_filter(c.row, c.col, c.data, d['W'], d['H'], d['lag_set'], d['theta'], OH.FIRST, lamI, lamAR, missing)[OH.FIRST:],
+                  W[OH.FIRST:]) <= 1e-10
+    for Wx in (d['W'], W):
+        a, b = OH.sq_err(d, Wx, OH.FIRST, missing), OH.sq_err_entries(c.row, c.col, c.data, Wx, d['H'], OH.FIRST, OH.T, missing)
+        assert a[1] == b[1] and abs(a[0] - b[0]) <= 1e-12 * a[0]              # one reading on a canonical matrix
+
+
+@pytest.mark.parametrize('scale,lamI,lamAR', OH.HARD_CASES)
+@pytest.mark.parametrize('k', OH.HARD_RANKS)
+def test_hard_filter_problem_stays_out_of_the_breakdown_regime(k, scale, lamI, lamAR):
+    """filter_rows refuses no case of the hard problem in fp32 (nor in fp64), and the twin's own teacher-forced backward error
+    stays below 8 u on both paths: the device gate 4 x max(twin, u) is never a gate against a broken yardstick."""
+    from conditioning_helpers import U
+    d = OH.hard_filter_problem(k, scale)
+    for missing, Y in ((True, d['Y']), (False, d['Yd'])):
+        cond = max(float(np.linalg.cond(A)) for A, _ in OH.row_systems(d, np.float64, lamI, lamAR, missing))
+        for dtype in (np.float32, np.float64):
+            W = OH.twin(d, dtype, lamI, lamAR, missing, d['first'], Y=Y)            # raises where a row breaks down
+            eta = OH.row_backward_errors(d, OH.row_systems(d, dtype, lamI, lamAR, missing), W, dtype, lamAR)
+            u = U[np.dtype(dtype).name]
+            print('hard filter problem k=%d scale=%g lambdaI=%g lambdaAR=%g missing=%d %s: cond up to %.1e, twin eta %.2f u (row %d)' % (
+                k, scale, lamI, lamAR, missing, np.dtype(dtype).name, cond, eta.max() / u, d['first'] + int(eta.argmax())))
+            assert np.all(np.isfinite(W)) and eta.max() < 8 * u
+
+
+def test_filter_rows_sums_the_prior_in_lag_set_order_and_counts_a_repeated_lag_twice():
+    """An unsorted lag set is refused when a session is created (the lag set of the C interface is ascending), so this order is
+    the host's alone; a repeated lag passes both and counts twice."""
+    from trmf import filter_rows
+    d = OH.inputs(7)
+    W64, H64, Y = d['W'].astype(np.float64), d['H'].astype(np.float64), d['Y'][OH.FIRST:].astype(np.float64)
+    th = d['theta'].astype(np.float64)
+    a = filter_rows(W64, H64, np.array([1, 2, 5]), th, Y, OH.FIRST, 0.5, 0.5, True)
+    b = filter_rows(W64, H64, np.array([5, 1, 2]), th[[2, 0, 1]], Y, OH.FIRST, 0.5, 0.5, True)
+    assert relmax(b[OH.FIRST:], a[OH.FIRST:]) <= 1e-13
+    rep = filter_rows(W64, H64, np.array([1, 2, 2, 5]), th[[0, 1, 1, 2]], Y, OH.FIRST, 0.5, 0.5, True)
+    once = filter_rows(W64, H64, np.array([1, 2, 5]), th * np.array([[1.0], [2.0], [1.0]]), Y, OH.FIRST, 0.5, 0.5, True)
+    assert relmax(rep[OH.FIRST:], once[OH.FIRST:]) <= 1e-13
+
+
+def test_fit_noise_reads_a_repeated_cell_as_the_training_objective_does():
+    """missing = 0 on a sparse Y with a cell stored twice: ||Y||^2 of the objective is the sum of squares of the stored values, so
+    the cell's residual is p^2 + sum_e y_e (y_e - 2 p) -- not (sum_e y_e - p)^2.  A canonical matrix keeps its bits."""
+    from trmf import fit_noise
+    d = OH.inputs(7)
+    c = d['Y'].tocoo()
+    args = (d['W'], d['H'], d['lag_set'], d['theta'])
+    canon = fit_noise(*args, d['Y'], missing=False)
+    dense = fit_noise(*args, np.asarray(d['Y'].todense()), missing=False)
+    assert np.array_equal(canon[0], dense[0]) and np.array_equal(canon[1], dense[1])
+    dup = smat.coo_matrix((np.concatenate([c.data, c.data[:40] + np.float32(0.25)]),
+                           (np.concatenate([c.row, c.row[:40]]), np.concatenate([c.col, c.col[:40]]))), shape=d['Y'].shape)
+    got = fit_noise(*args, dup, missing=False)
+    want = np.zeros(OH.N)
+    for j in range(OH.N):                                                   # series j alone: its entries against the one row h_j
+        e = dup.col == j
+        want[j] = OH.sq_err_entries(dup.row[e], np.zeros(e.sum(), int), dup.data[e], d['W'], d['H'][j:j + 1], 0, OH.T, False)[0]
+    assert np.allclose(got[2]['sq'], want, rtol=1e-12, atol=0) and np.all(got[2]['cnt'] == OH.T)
+    merged = fit_noise(*args, dup.tocsr(), missing=False)                  # a caller who sums duplicates first states another problem
+    assert not np.allclose(merged[2]['sq'], want, rtol=1e-3)
+    per_entry = fit_noise(*args, dup, missing=True)                         # missing = 1: one residual per stored entry
+    assert per_entry[2]['cnt'].sum() == dup.nnz
+
+
 def test_rolling_validate_says_where_an_online_update_does_not_apply():
     import trmf
     Y = np.abs(np.random.RandomState(0).randn(120, 6)) + 0.5
