@@ -15,13 +15,14 @@
 //   unit_heldout.hip   heldout_eval_kernel (5): the model at a resident set of held-out positions (trmf_session_eval_heldout)
 //   unit_forecast.hip  forecast_rollout_kernel, forecast_score_kernel (5): the next timestamps forecast and scored (trmf_session_forecast)
 //   unit_online.hip    assim_factor_kernel (4), assim_chain_kernel, assim_err_kernel: the forward filter of trmf_session_assimilate
+//   unit_robust.hip    assim_robust_part_kernel (4), assim_robust_solve_kernel (4), assim_robust_prior_kernel: trmf_session_assimilate_robust
 //   unit_uncertainty.hip  noise_resid_kernel (5), forecast_dist_kernel (5), the noise / psi kernels: trmf_session_fit_noise, _forecast_dist
 //
 // A unit defines TRMF_UNIT before including this file; the non-template kernels of the shared headers are compiled by the main
 // unit only (#if !defined(TRMF_UNIT) around them).
 #pragma once
 
-// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty; the kernels of these families
+// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online; the kernels of these families
 // have their BODIES only where TRMF_UNIT_BODIES is defined -- the main unit sees declarations, so that it neither compiles them
 // nor runs them through the optimiser as `extern template` would (available_externally bodies: 3 of its 3.5 minutes))
 #if defined(TRMF_UNIT) || defined(TRMF_SINGLE_UNIT)
@@ -49,6 +50,9 @@
 #endif
 #if !defined(TRMF_UNIT) || TRMF_UNIT == 8
 #include "uncertainty_kernels.hpp"
+#endif
+#if !defined(TRMF_UNIT) || TRMF_UNIT == 9
+#include "robust_kernels.hpp"
 #endif
 #if !defined(TRMF_UNIT)
 #include "cg_persist_args.hpp"     // the declaration only: the body is unit_persist.hip's business
@@ -149,6 +153,13 @@ namespace trmf {
 #define TRMF_UNIT_ONLINE(X)                                                                                                  \
     X void assim_factor_kernel<1>(AssimFactorArgs); X void assim_factor_kernel<2>(AssimFactorArgs);                          \
     X void assim_factor_kernel<3>(AssimFactorArgs); X void assim_factor_kernel<4>(AssimFactorArgs);
+
+// robust online updates (robust_kernels.hpp): the part and the solve kernel as NT = 1..4 (k <= 64); the prior kernel is not a template
+#define TRMF_UNIT_ROBUST(X)                                                                                                  \
+    X void assim_robust_part_kernel<1>(AssimRobustArgs); X void assim_robust_part_kernel<2>(AssimRobustArgs);                \
+    X void assim_robust_part_kernel<3>(AssimRobustArgs); X void assim_robust_part_kernel<4>(AssimRobustArgs);                \
+    X void assim_robust_solve_kernel<1>(AssimRobustArgs); X void assim_robust_solve_kernel<2>(AssimRobustArgs);              \
+    X void assim_robust_solve_kernel<3>(AssimRobustArgs); X void assim_robust_solve_kernel<4>(AssimRobustArgs);
 
 // forecast uncertainty (uncertainty_kernels.hpp): the residual pass and the dist kernel as NT = 1..4 (k <= 64) and NT = 0
 // (64 < k <= 1024); the other kernels are not templates

@@ -1290,6 +1290,87 @@ struct TrmfSessionImpl : SessionXPhase {
         if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
         return 0;
     }
+    // ---- outlier-robust online updates (trmf_session_assimilate_robust; robust_kernels.hpp) -------------------------------------
+    // assimilate() with Huber weights (the caller has validated first_row, the lag set, the rank, the storage, c, the sweep count and
+    // the n scales, which arrive as host values on every rank).  The weights depend on the iterate, so the Gram cache is of no use:
+    // per row and sweep one part launch over the row's slices and one solve launch, 2 * sweeps * rows launches on the session's
+    // stream with no host synchronisation before the one flag read.  Neither G nor Bv is touched.  Failure-atomic like assimilate():
+    // rows, weights and sums land in scratch / host staging and are handed over after the flag has been read.
+    struct RobustResult {
+        uint64_t rows = 0, entries = 0, downweighted = 0;
+        double weight_sum = 0, sq_err_before = 0, sq_err_after = 0;
+        int bad_row = -1;
+    };
+    int assimilate_robust(int first_row, double c, int sweeps, const double *scale, RobustResult *res, real *Wout, real *weights_out) {
+        *res = RobustResult{};
+        if (sync()) return kFail;
+        const int nr = T - first_row;
+        if (nr <= 0) return 0;
+        FillStreamScope fill(stream);
+        int slice = kAssimRobustSlice;
+        if (const char *e = test_env("TRMF_ASSIM_ROBUST_SLICE")) slice = std::max(1, atoi(e));      // tests: several slices per row on a small shape
+        const uint64_t nw = dense ? (uint64_t)nr * (uint64_t)n : host_row_ptr[T] - host_row_ptr[first_row];
+        auto slices_of = [&](int i) { const uint64_t len = dense ? (uint64_t)n : host_row_ptr[i + 1] - host_row_ptr[i]; return (int)((len + slice - 1) / slice); };
+        int max_slices = 1;
+        for (int i = first_row; i < T; i++) max_slices = std::max(max_slices, slices_of(i));
+        std::vector<real> hthr((size_t)n);
+        for (int j = 0; j < n; j++) hthr[j] = (real)c * (real)scale[j];
+        DevBuf<real> Wn, flat, wcur, prior, thr, wts, slab;
+        DevBuf<int> flag;
+        DevBuf<double> errs, slab_d, rowsum;
+        SyncStreamOnExit drain(stream);
+        if (Wn.alloc((size_t)nr * KP) || (Wout && flat.alloc((size_t)nr * k, false)) || wcur.alloc(KP) || prior.alloc(KP) || thr.upload(hthr.data(), n) ||
+            wts.alloc(nw, false) || slab.alloc((size_t)max_slices * assim_robust_slot_reals(KP), false) || slab_d.alloc((size_t)2 * max_slices, false) ||
+            rowsum.alloc((size_t)2 * nr, false) || flag.alloc(1, false) || errs.alloc((size_t)2 * nr, false)) return kFail;
+        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
+        AssimRobustArgs ra{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr, H.p, W.p, Wn.p,
+                           Wout ? flat.p : nullptr, wcur.p, prior.p, thr.p, wts.p, slab.p, slab_d.p, rowsum.p, lag_set.p, theta.p, flag.p,
+                           (real)lambdaI + (real)lambdaAR, (real)lambdaAR, first_row, T, first_row, n, k, KP, nlag, slice, 0, 0};
+        hipLaunchKernelGGL(assim_robust_prior_kernel, dim3(1), dim3(64), 0, stream, ra);
+        TRMF_HIP_CHECK(hipGetLastError());
+        for (int i = first_row; i < T; i++) {
+            ra.i = i; ra.nslices = slices_of(i);
+            for (int s = 1; s <= sweeps; s++) {
+                ra.last = s == sweeps ? 1 : 0;
+                if (!with_nt(NT, [&](auto N) {
+                        if (ra.nslices > 0) hipLaunchKernelGGL(assim_robust_part_kernel<decltype(N)::value>, dim3(ra.nslices), dim3(256), 0, stream, ra);
+                        hipLaunchKernelGGL(assim_robust_solve_kernel<decltype(N)::value>, dim3(1), dim3(256), 0, stream, ra);
+                    })) return unsupported_rank();
+            }
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        {   // the squared errors of the range with W as it is and as it will be (unweighted)
+            AssimErrArgs ea{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr, H.p,
+                            W.p, Wn.p, 0, first_row, errs.p, first_row, nr, n, KP, full ? 1 : 0};
+            hipLaunchKernelGGL(assim_err_kernel, dim3(nr), dim3(256), 0, stream, ea);
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        int bad = kAssimNoBadRow;
+        std::vector<double> herr((size_t)2 * nr), hsum((size_t)2 * nr);
+        std::vector<real> hflat(Wout ? (size_t)nr * k : 0), hwts(weights_out ? (size_t)nw : 0);
+        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, herr.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(hsum.data(), rowsum.p, hsum.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (Wout) TRMF_HIP_CHECK(hipMemcpyAsync(hflat.data(), flat.p, hflat.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
+        if (weights_out && nw) TRMF_HIP_CHECK(hipMemcpyAsync(hwts.data(), wts.p, hwts.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (bad != kAssimNoBadRow) { res->bad_row = bad; return 0; }
+        // ---- commit ----
+        TRMF_HIP_CHECK(hipMemcpyAsync(W.p + (size_t)first_row * KP, Wn.p, (size_t)nr * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new W
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        res->rows = (uint64_t)nr;
+        res->entries = nw;
+        double down = 0;
+        for (int r = 0; r < nr; r++) {                              // row order: the same sums on every rank and every call
+            res->sq_err_before += herr[2 * r]; res->sq_err_after += herr[2 * r + 1];
+            down += hsum[2 * r]; res->weight_sum += hsum[2 * r + 1];
+        }
+        res->downweighted = (uint64_t)down;
+        if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
+        if (weights_out && nw) std::memcpy(weights_out, hwts.data(), hwts.size() * sizeof(real));
+        return 0;
+    }
     // New regularisation weights for the iterations enqueued from now on: the session's own copies (F-solve, Theta-solve, the
     // full-observation path's shared Gram) and the X-side parameter block every X-solve kernel receives by value.
     int set_lambdas(double lI, double lAR, double lLag) {

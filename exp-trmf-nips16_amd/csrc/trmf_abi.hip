@@ -561,6 +561,66 @@ int32_t trmf_session_assimilate(TrmfSession *s, int32_t first_row, TrmfAssimilat
     return 0;
 }
 
+// Robust online update: like trmf_session_assimilate, every argument -- the scales included, which every rank receives as the same
+// host values -- is checked on the calling thread before any rank's worker runs.
+int32_t trmf_session_assimilate_robust(TrmfSession *s, int32_t first_row, double c, int32_t sweeps, const double *scale, TrmfRobustSums *out,
+                                       void *Wnew, void *weights) {
+    if (!s) { set_error("null session"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (f->k > kMaxRank) {
+        set_error("assimilate_robust: online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
+        return kFail;
+    }
+    if (f->has_lag0) { set_error("assimilate_robust: the lag set contains lag 0 (a row would be its own prior)"); return kFail; }
+    if (f->full && !f->dense) {
+        set_error("assimilate_robust: sparse storage with missing == 0 is not covered (an absent entry there is an observation without a slot "
+                  "to report its weight in); store the matrix dense");
+        return kFail;
+    }
+    if (first_row < f->midx || first_row > f->T) {
+        set_error("assimilate_robust: first_row " + std::to_string(first_row) + " outside [" + std::to_string(f->midx) + " (the largest lag), " +
+                  std::to_string(f->T) + " (rows)]");
+        return kFail;
+    }
+    if (!(c > 0)) { set_error("assimilate_robust: c must be positive (infinity: the plain filter)"); return kFail; }
+    if (sweeps < 1 || sweeps > kAssimRobustMaxSweeps) {
+        set_error("assimilate_robust: sweeps " + std::to_string(sweeps) + " outside 1.." + std::to_string(kAssimRobustMaxSweeps));
+        return kFail;
+    }
+    if (!scale && !f->nz_set) { set_error("assimilate_robust: no scale given and no noise fitted or set (trmf_session_fit_noise / _set_noise)"); return kFail; }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    std::vector<double> sc((size_t)f->n);
+    if (scale) std::copy(scale, scale + f->n, sc.begin());
+    else {
+        if (HND(s)->rank0([&](TrmfSessionImpl *t) { return t->noise(sc.data(), nullptr); })) return kFail;
+        for (double &v : sc) v = std::sqrt(v);
+    }
+    for (int j = 0; j < f->n; j++)
+        if (!(std::isfinite(sc[j]) && sc[j] > 0)) {
+            set_error("assimilate_robust: the scale of series " + std::to_string(j) + " is not finite and positive" +
+                      (scale ? "" : " (the square root of the resident sigma2)"));
+            return kFail;
+        }
+    const bool grouped = HND(s)->group != nullptr;
+    std::vector<TrmfSessionImpl::RobustResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
+    if (HND(s)->all([&](TrmfSessionImpl *t) {
+            const int slot = grouped ? t->comm->rank : 0;
+            return t->assimilate_robust(first_row, c, sweeps, sc.data(), &res[slot], slot == 0 ? (real *)Wnew : nullptr, slot == 0 ? (real *)weights : nullptr);
+        })) return kFail;
+    for (const auto &r : res)
+        if (r.bad_row >= 0) {
+            set_error("assimilate_robust: row " + std::to_string(r.bad_row) + ": a pivot of the weighted G + (lambdaI + lambdaAR) I is not positive and "
+                      "finite (lambdaI + lambdaAR == 0 and a rank-deficient row?); nothing was changed");
+            return kFail;
+        }
+    if (out) {
+        out->rows = res[0].rows; out->entries = res[0].entries; out->downweighted = res[0].downweighted;
+        out->weight_sum = res[0].weight_sum; out->sq_err_before = res[0].sq_err_before; out->sq_err_after = res[0].sq_err_after;
+    }
+    return 0;
+}
+
 // Forecast uncertainty: the arguments are checked on the calling thread before any rank's worker runs (see trmf_session_set_heldout);
 // a training matrix without a stored entry is found by every rank alike and reported here, not by a failing worker task.
 int32_t trmf_session_fit_noise(TrmfSession *s, TrmfNoiseStats *out) {

@@ -167,20 +167,37 @@ class Model(object):
         return forecast_std(self.H, self.lag_set, self.lag_val, noise[0], noise[1], window, transform=self.transform)
 
     # ---- online update ----------------------------------------------------------------------------
-    def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True):
+    def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True, robust_c=None, robust_sweeps=4, scale=None):
         """A new ``Model`` grown by the ``Ynew.shape[0]`` timestamps of ``Ynew`` (raw values; a transform of this model is
         applied first): H, the lag weights and the rows this model has stay as they are, every new row of W is solved from its
         own observations and the AR prior of the rows before it (``trmf.online.filter_rows``; the host form of
-        ``Session.update``).  This model is left untouched."""
-        from .online import filter_rows
+        ``Session.update``).  This model is left untouched.  With ``robust_c`` the rows are solved with Huber weights
+        (``trmf.online.robust_filter_rows``: ``robust_sweeps`` rounds, ``scale`` per series, default ``sqrt(self.noise[0])`` of
+        ``fit_noise``); the last sweep's weights are kept as ``robust_weights`` of the new model, whose ``noise`` is this model's."""
+        from .online import filter_rows, robust_filter_rows
         if self.transform is not None:
             if smat.issparse(Ynew):
                 raise ValueError('assimilate: a series transform needs dense rows')
             Ynew = self.transform.preprocess(np.asarray(Ynew)).astype(self.W.dtype)
         grown = np.zeros((self.m + Ynew.shape[0], self.k), dtype=self.W.dtype, order='C')
         grown[:self.m] = self.W
-        grown = filter_rows(grown, self.H, self.lag_set, self.lag_val, Ynew, self.m, lambdaI, lambdaAR, missing)
-        return Model.from_arrays(grown, self.H.copy(), self.lag_val.copy(), self.lag_set.copy(), transform=self.transform)
+        weights = None
+        if robust_c is None:
+            grown = filter_rows(grown, self.H, self.lag_set, self.lag_val, Ynew, self.m, lambdaI, lambdaAR, missing)
+        else:
+            if scale is None:
+                noise = getattr(self, 'noise', None)
+                if noise is None:
+                    raise ValueError('assimilate: robust_c needs a scale per series or a fitted noise (Model.fit_noise)')
+                scale = np.sqrt(np.asarray(noise[0], dtype=np.float64))
+            grown, weights = robust_filter_rows(grown, self.H, self.lag_set, self.lag_val, Ynew, self.m, lambdaI, lambdaAR, missing,
+                                                scale, robust_c, robust_sweeps)
+        out = Model.from_arrays(grown, self.H.copy(), self.lag_val.copy(), self.lag_set.copy(), transform=self.transform)
+        if weights is not None:
+            out.robust_weights = weights
+            if getattr(self, 'noise', None) is not None:
+                out.noise = self.noise
+        return out
 
     # ---- construction ------------------------------------------------------------------------------
     @staticmethod

@@ -9,7 +9,8 @@ in ascending order, is the minimiser of its own observations plus the AR prior f
     W[i]    = A_i^-1 (sum_{j in Omega_i} y_ij h_j + lambdaAR p_i)
 
 A filter, not a smoother: rows before ``first_row`` never see the new data.  ``filter_rows`` is the specification the device
-tests compare against and the host path of ``Model.assimilate``.
+tests compare against and the host path of ``Model.assimilate``.  ``robust_filter_rows`` is the same filter with Huber weights
+(``trmf_session_assimilate_robust``): a cell far outside its series' residual scale is down-weighted, and the weights are returned.
 """
 import numpy as np
 import scipy.linalg
@@ -71,3 +72,95 @@ def filter_rows(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, mis
             raise ValueError('filter_rows: row {}: G + (lambdaI + lambdaAR) I is not positive definite'.format(i))
         out[i] = scipy.linalg.cho_solve((L, True), b, check_finite=False)
     return out
+
+
+def robust_filter_rows(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, missing, scale, c=3.0, sweeps=4):
+    """``filter_rows`` with Huber weights: the specification of ``trmf_session_assimilate_robust``.  A cell whose residual is
+    beyond ``c * scale[j]`` of its series enters its row's system with the weight ``c * scale[j] / |r|`` instead of 1::
+
+        w^0 = p_i;  for s = 1 .. sweeps:   r_j = y_ij - w^{s-1} . h_j,   omega_j = t_j / |r_j| if |r_j| > t_j else 1   (t_j = c scale_j)
+                                           w^s = (sum omega_j h_j h_j^T + lam I)^-1 (sum omega_j y_ij h_j + lambdaAR p_i)
+
+    (iteratively reweighted least squares on Huber's loss; a fixed number of sweeps, no convergence test).  Returns
+    ``(W_out, weights)``: the weights of the LAST sweep (formed from ``w^{sweeps-1}``), one per stored entry in CSR order for a
+    sparse ``Yrows`` with ``missing``, a ``(T - first_row) x n`` matrix for an array (a cell that is no observation reads 1).
+    ``c = inf`` is the plain filter.  Sparse rows without ``missing`` are refused: an absent entry there is an observation
+    without a slot to report a weight in.  ``ValueError`` in ``filter_rows``' cases and for a scale that is not finite and
+    positive, ``c`` not positive, ``sweeps < 1``, a row whose weighted system is not positive definite."""
+    W = np.asarray(W)
+    dt = W.dtype
+    T, k = W.shape
+    back = np.asarray(lag_set).astype(np.int64)
+    if back.size and back.min() == 0:
+        raise ValueError('robust_filter_rows: the lag set contains lag 0 (a row would be its own prior)')
+    reach = int(back.max()) if back.size else 0
+    first_row = int(first_row)
+    if first_row < reach or first_row > T:
+        raise ValueError('robust_filter_rows: first_row {} outside [{} (the largest lag), {} (rows)]'.format(first_row, reach, T))
+    if Yrows.shape[0] != T - first_row or (T > first_row and Yrows.shape[1] != H.shape[0]):
+        raise ValueError('robust_filter_rows: Yrows is {}, rows {}..{} of {} series were expected'.format(Yrows.shape, first_row, T, H.shape[0]))
+    sparse = smat.issparse(Yrows)
+    if sparse and not missing:
+        raise ValueError('robust_filter_rows: sparse rows without missing are not covered (an absent entry would be an observation '
+                         'without a slot to report its weight in); pass the rows as an array')
+    n = H.shape[0]
+    scale = np.asarray(scale, dtype=np.float64)
+    if scale.ndim == 0:
+        scale = np.full(n, float(scale))
+    if scale.shape != (n,):
+        raise ValueError('robust_filter_rows: scale has shape {}, one value per series ({}) was expected'.format(scale.shape, n))
+    bad = np.flatnonzero(~(np.isfinite(scale) & (scale > 0)))
+    if bad.size:
+        raise ValueError('robust_filter_rows: scale[{}] = {!r} is not finite and positive'.format(int(bad[0]), float(scale[bad[0]])))
+    c = float(c)
+    if not c > 0:
+        raise ValueError('robust_filter_rows: c must be positive (inf: the plain filter), not {!r}'.format(c))
+    sweeps = int(sweeps)
+    if sweeps < 1:
+        raise ValueError('robust_filter_rows: sweeps must be at least 1, not {}'.format(sweeps))
+    H = np.asarray(H, dtype=dt)
+    theta = np.asarray(lag_val, dtype=dt)
+    lamAR = dt.type(lambdaAR)
+    lam = dt.type(lambdaI) + lamAR
+    thr = dt.type(c) * scale.astype(dt)
+    Yr = Yrows.tocsr() if sparse else np.asarray(Yrows)
+    out = W.copy()
+    weights = np.ones(Yr.data.shape[0] if sparse else (T - first_row, n), dtype=dt)
+    eye = np.eye(k, dtype=dt)
+    for i in range(first_row, T):
+        r = i - first_row
+        if sparse:
+            lo, hi = Yr.indptr[r], Yr.indptr[r + 1]
+            cols, y = Yr.indices[lo:hi], Yr.data[lo:hi].astype(dt)
+        elif missing:
+            cols = np.nonzero(Yr[r])[0]
+            y = Yr[r, cols].astype(dt)
+        else:
+            cols, y = np.arange(n), Yr[r].astype(dt)
+        Hi, ti = H[cols], thr[cols]
+        prior = np.sum(out[i - back] * theta, axis=0) if back.size else np.zeros(k, dtype=dt)
+        w = prior
+        om = np.ones(len(y), dtype=dt)
+        for _ in range(sweeps):
+            res = np.abs(y - Hi.dot(w))
+            om = np.ones(len(y), dtype=dt)
+            far = res > ti
+            om[far] = ti[far] / res[far]
+            Hw = Hi * om[:, None]
+            A = Hw.T.dot(Hi) + lam * eye
+            b = Hw.T.dot(y) + lamAR * prior
+            try:
+                if not np.all(np.isfinite(A)):
+                    raise np.linalg.LinAlgError('not finite')
+                L = np.linalg.cholesky(A)
+                if not (np.all(np.isfinite(L)) and np.all(np.diagonal(L) > 0)):
+                    raise np.linalg.LinAlgError('pivot')
+            except np.linalg.LinAlgError:
+                raise ValueError('robust_filter_rows: row {}: the weighted G + (lambdaI + lambdaAR) I is not positive definite'.format(i))
+            w = scipy.linalg.cho_solve((L, True), b, check_finite=False)
+        out[i] = w
+        if sparse:
+            weights[lo:hi] = om
+        else:
+            weights[r, cols] = om
+    return out, weights

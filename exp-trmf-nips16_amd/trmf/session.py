@@ -53,6 +53,16 @@ class TrmfAssimilateSums(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TrmfRobustSums(ctypes.Structure):
+    """Sums of a robust online update (include/trmf_abi.h): those of ``TrmfAssimilateSums``, the number of down-weighted entries
+    and the sum of the weights."""
+    _fields_ = [('rows', c_uint64), ('entries', c_uint64), ('downweighted', c_uint64), ('weight_sum', c_double),
+                ('sq_err_before', c_double), ('sq_err_after', c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class TrmfNoiseStats(ctypes.Structure):
     """Summary of a noise fit (include/trmf_abi.h)."""
     _fields_ = [('pooled_sigma2', c_double), ('sigma2_min', c_double), ('sigma2_max', c_double), ('series_pooled', c_uint64),
@@ -139,6 +149,9 @@ def bind(lib):
     if hasattr(lib, 'trmf_session_assimilate'):       # (absent from libraries built before the online updates)
         lib.trmf_session_assimilate.argtypes = [c_void_p, c_int32, POINTER(TrmfAssimilateSums), c_void_p]
         lib.trmf_session_assimilate.restype = c_int32
+    if hasattr(lib, 'trmf_session_assimilate_robust'):    # (absent from libraries built before the robust online updates)
+        lib.trmf_session_assimilate_robust.argtypes = [c_void_p, c_int32, c_double, c_int32, c_void_p, POINTER(TrmfRobustSums), c_void_p, c_void_p]
+        lib.trmf_session_assimilate_robust.restype = c_int32
     if hasattr(lib, 'trmf_session_fit_noise'):        # (absent from libraries built before the forecast uncertainty)
         lib.trmf_session_fit_noise.argtypes = [c_void_p, POINTER(TrmfNoiseStats)]; lib.trmf_session_fit_noise.restype = c_int32
         lib.trmf_session_noise.argtypes = [c_void_p, c_void_p, c_void_p]; lib.trmf_session_noise.restype = c_int32
@@ -172,6 +185,14 @@ def train_profile(dtype):
     return prof.as_dict() if lib_for(dtype).trmf_last_train_profile(byref(prof)) == 0 else None
 
 
+def _stored_per_row(pm):
+    """Stored entries per row of a sparse ``PyMatrix`` (None for a dense one): ``Session`` keeps them to size the weights that
+    ``assimilate_robust`` reports per stored entry."""
+    if pm.type != PyMatrix.SPARSE:
+        return None
+    return np.diff(np.ctypeslib.as_array(pm.row_ptr, shape=(int(pm.rows) + 1,)).astype(np.int64))
+
+
 def check_lag_penalty(lambdaLagL1, lag_refit=False):
     """The front end's argument check of the sparse lag weights: a finite ``lambdaLagL1 >= 0`` as a float, ``lag_refit`` as a bool."""
     try:
@@ -203,6 +224,7 @@ class Session(object):
             lambdaI, lambdaAR, lambdaLag, period_W, period_H, period_Lag, int(missing), verbose)
         if not self.handle:
             raise RuntimeError('trmf_session_create failed: ' + self.lib.trmf_last_error().decode())
+        self._stored = _stored_per_row(self.pyY)
         if not log_norms:       # the reference computes the ||.||^2 log lines only under verbose
             self.lib.trmf_session_log_norms(self.handle, 0)
         if timing != 1:         # phase events (ms_* of stats()) on every `timing`-th iteration only / never (0): they cost ~25 us apiece
@@ -242,6 +264,8 @@ class Session(object):
         replaced by a model with ``rows()`` timestamps before the next ``download()``."""
         block = Ynew if isinstance(Ynew, PyMatrix) else PyMatrix(Ynew, dtype=self.model.W.dtype)
         self._check(self.lib.trmf_session_append_rows(self.handle, byref(block)), 'trmf_session_append_rows')
+        if self._stored is not None:
+            self._stored = np.concatenate([self._stored, _stored_per_row(block)])
         return self
 
     def assimilate(self, first_row, return_latent=False):
@@ -263,17 +287,55 @@ class Session(object):
                     'trmf_session_assimilate')
         return (sums.as_dict(), Wnew) if return_latent else sums.as_dict()
 
-    def update(self, Ynew, iters=0):
+    def assimilate_robust(self, first_row, c=3.0, sweeps=4, scale=None, return_latent=False, return_weights=False):
+        """``assimilate`` with Huber weights (``trmf.online.robust_filter_rows`` is the same computation in NumPy): an entry whose
+        residual lies beyond ``c * scale[j]`` of its series enters its row's system with the weight ``c * scale[j] / |r|``
+        instead of 1, over ``sweeps`` rounds of reweighting per row.  ``scale``: n positive values (or one for all), default the
+        square roots of the resident noise table (``fit_noise`` / ``set_noise``), which is the in-sample residual scale: ``c``
+        below about 2 then flags ordinary cells.  Returns ``{'rows', 'entries', 'downweighted', 'weight_sum', 'sq_err_before',
+        'sq_err_after'}``, followed by ``Wnew`` with ``return_latent`` and by the last sweep's weights with ``return_weights``:
+        one per stored entry of the rows in CSR order (``missing``), or a ``(rows() - first_row) x n`` matrix (dense storage
+        without ``missing``).  A weight below 1 marks an anomalous cell.  A refused call (everything ``assimilate`` refuses; no
+        scale and no resident noise; a scale that is not finite and positive; ``c`` not positive; ``sweeps`` outside 1..64; sparse
+        storage without ``missing``) raises and leaves the session as it was."""
+        first_row = int(first_row)
+        dt = self.model.W.dtype
+        nr = max(self.rows() - first_row, 0)
+        sc = None
+        if scale is not None:
+            sc = np.asarray(scale, dtype=np.float64)
+            if sc.ndim == 0:
+                sc = np.full(self.model.n, float(sc))
+            if sc.shape != (self.model.n,):
+                raise ValueError('assimilate_robust: scale has shape {}, one value per series ({}) was expected'.format(sc.shape, self.model.n))
+            sc = np.ascontiguousarray(sc)
+        sums = TrmfRobustSums()
+        Wnew = np.empty((nr, self.model.k), dtype=dt) if return_latent else None
+        weights = None
+        if return_weights:
+            if self._stored is not None:
+                weights = np.empty(int(self._stored[first_row:].sum()) if nr and first_row >= 0 else 0, dtype=dt)
+            else:
+                weights = np.empty((nr, self.model.n), dtype=dt)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        self._check(self.lib.trmf_session_assimilate_robust(self.handle, first_row, float(c), int(sweeps), ptr(sc), byref(sums), ptr(Wnew), ptr(weights)),
+                    'trmf_session_assimilate_robust')
+        out = (sums.as_dict(),) + ((Wnew,) if return_latent else ()) + ((weights,) if return_weights else ())
+        return out if len(out) > 1 else out[0]
+
+    def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None):
         """Absorb the new timestamps ``Ynew`` (as for ``append_rows``): append them, assimilate the new block, run ``iters``
         ALS iterations if asked for.  ``self.model`` is replaced by a host model of ``rows()`` timestamps (H, lag weights, lag
-        set and transform carried over; its arrays are filled by the next ``download()``).  Returns the sums of ``assimilate``."""
+        set and transform carried over; its arrays are filled by the next ``download()``).  Returns the sums of ``assimilate``;
+        with ``robust_c`` the block is absorbed by ``assimilate_robust(before, robust_c, robust_sweeps, scale)`` and its sums
+        are returned."""
         before = self.rows()
         self.append_rows(Ynew)
         old = self.model
         grown = np.zeros((self.rows(), old.k), dtype=old.W.dtype, order='C')
         grown[:min(before, old.m)] = old.W[:before]
         self.model = type(old).from_arrays(grown, old.H.copy(), old.lag_val.copy(), old.lag_set.copy(), transform=old.transform)
-        sums = self.assimilate(before)
+        sums = self.assimilate(before) if robust_c is None else self.assimilate_robust(before, robust_c, robust_sweeps, scale)
         if iters:
             self.run(int(iters))
         return sums

@@ -35,7 +35,7 @@ def _as_training_matrix(block, missing):
     return smat.csr_matrix(block) if missing else block
 
 
-def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag=None, assimilate=False):
+def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag=None, assimilate=False, robust=None):
     """Yield the trained model of every window from one resident session.  With a transform (dense Y, full
     observation) the session holds the RAW matrix and applies each window's refitted coefficients on the device."""
     from .session import Session
@@ -46,9 +46,11 @@ def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing,
             sess.set_transform(model.transform)
         sess.run(max_iter).download()
         yield model
+        if robust is not None:
+            _ensure_noise(sess)
         for prev_cut, cut in zip(cuts[:-1], cuts[1:]):
             if assimilate:      # online: the new rows are filtered in, nothing is retrained
-                sess.update(_as_training_matrix(Y[prev_cut:cut], missing))
+                sess.update(_as_training_matrix(Y[prev_cut:cut], missing), **(robust or {}))
                 yield sess.download()
                 continue
             # host-side model of the new size: same warm start the device applies, same RNG consumption as the
@@ -62,8 +64,16 @@ def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing,
             yield model
 
 
+def _ensure_noise(sess):
+    """The robust filter's default scale: fitted once on window 0's model unless a table is already resident."""
+    try:
+        sess.noise()
+    except RuntimeError:
+        sess.fit_noise()
+
+
 def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag=None,
-                             assimilate=False, interval_level=None):
+                             assimilate=False, interval_level=None, robust=None):
     """The whole rolling evaluation from one resident session: every window is trained, forecast and scored on the device
     (``Session.forecast`` with the window's truth), the next window's rows are appended and, if asked for, a transform
     refitted on the grown prefix is handed over.  No factor is downloaded and no host model is rebuilt between windows.  With an
@@ -80,10 +90,15 @@ def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_
                 sess.append_rows(_as_training_matrix(Y[cuts[i - 1]:cut], missing))
                 if transform is not None:
                     sess.set_transform(NormalizedTransform(Y[:cut]))
-            if assimilate and i > 0:
-                sess.assimilate(cuts[i - 1])        # online: the appended rows are filtered in, nothing is retrained
+            if assimilate and i > 0:      # online: the appended rows are filtered in, nothing is retrained
+                if robust is None:
+                    sess.assimilate(cuts[i - 1])
+                else:
+                    sess.assimilate_robust(cuts[i - 1], robust['robust_c'], robust['robust_sweeps'])
             else:
                 sess.run(max_iter)
+                if robust is not None:
+                    _ensure_noise(sess)
             truth = np.ascontiguousarray(Y[cut:cut + window_size])
             sess.forecast(window_size, threshold=threshold, truth=truth, return_forecast=False)
             if interval_level is not None:
@@ -107,13 +122,17 @@ def _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, tr
 
 def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5, lambdaAR=50, lambdaLag=0.5,
                      max_iter=20, missing=True, threshold=0, transform=None, threads=16, verbose=0, seed=0,
-                     resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False, update='retrain', interval_level=None):
+                     resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False, update='retrain', interval_level=None,
+                     robust_c=None, robust_sweeps=4):
     """``interval_level`` (e.g. 0.9; needs ``forecast_on_device=True``): every window also fits the noise of its trained model and
     scores the predictive distribution of its forecast on the device; the result is ``(Metrics, IntervalMetrics)``, the ``Metrics``
     being exactly those of the call without it.
     ``update='assimilate'``: window 0 is trained with ``max_iter`` iterations, every later window appends its rows and
     absorbs them by the forward filter (``Session.update``) instead of retraining; it needs the resident path and refuses a
     per-window transform (a refitted transform rescales the whole history, which an online update does not revisit).
+    ``robust_c`` (with ``update='assimilate'`` only): the later windows are absorbed by the Huber-weighted filter
+    (``Session.assimilate_robust`` with ``robust_sweeps`` rounds); the noise is fitted once after window 0 unless a table is
+    already resident, and its square roots are the scale.
     ``lambdaLagL1`` / ``lag_refit``: sparse lag weights (``Session.set_lag_penalty``) on every path.
     ``forecast_on_device=True`` keeps the forecasts and their scoring on the device as well (one session, no download and no
     host model per window); it needs the resident path and a dense ``Y``, and says so where that does not hold."""
@@ -128,6 +147,11 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
     if update not in ('retrain', 'assimilate'):
         raise ValueError("update must be 'retrain' or 'assimilate', not {!r}".format(update))
     online = update == 'assimilate'
+    robust = None
+    if robust_c is not None:
+        if not online:
+            raise ValueError("robust_c: the robust filter absorbs new rows online (update='assimilate'); retraining solves plain least squares")
+        robust = dict(robust_c=float(robust_c), robust_sweeps=int(robust_sweeps))
     if online:
         if transform is not None:
             raise ValueError("update='assimilate': a per-window transform rescales the whole history, which an online update does not revisit")
@@ -149,10 +173,10 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
             raise ValueError('forecast_on_device: a transform with missing=True is refitted on the host per window; '
                              'the device applies one only to dense full-observation training (missing=False)')
         return _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag, online,
-                                        interval_level)
+                                        interval_level, robust)
     # resident: a NumPy Y, and a transform only where the device can apply it (dense full-observation training)
     if resident and isinstance(Y, np.ndarray) and (transform is None or (not missing and Y.dtype in (np.float32, np.float64))):
-        models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag, online)
+        models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag, online, robust)
     else:
         models = _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, threads, verbose, lag)
     forecasts = np.zeros((horizon, n), dtype=Y.dtype, order='C')

@@ -345,6 +345,41 @@ typedef struct {
 TRMF_API int32_t trmf_session_assimilate(TrmfSession *s, int32_t first_row, TrmfAssimilateSums *out /* or NULL */,
                                          void *Wnew /* or NULL: (rows - first_row) x k, row-major */);
 
+/* --- outlier-robust online updates: the forward filter with Huber weights -----------------------------------------------
+ * trmf_session_assimilate trusts every incoming value: one spiked reading bends its row of W and travels through the AR prior
+ * into every later row and forecast.  Here a cell whose residual lies beyond c scale_j of its series enters its row's system
+ * with the weight c scale_j / |r| instead of 1 (iteratively reweighted least squares on Huber's loss), and the weights come back:
+ * they are the anomaly signal.  Over the rows i = first_row .. rows - 1 in ascending order, with Omega_i, p_i, y and the lambdas as
+ * for trmf_session_assimilate, lam = lambdaI + lambdaAR and t_j = c scale_j (c and scale_j cast to the element type first):
+ *   w^0 = p_i;  for s = 1 .. sweeps:
+ *       r_j = y_ij - w^{s-1} . h_j,   omega_j = t_j / |r_j| if |r_j| > t_j else 1                      (j in Omega_i)
+ *       w^s = (sum_j omega_j h_j h_j^T + lam I)^-1 (sum_j omega_j y_ij h_j + lambdaAR p_i)            Cholesky in the element type
+ *   W[i] = w^sweeps;   the weights reported are those of the last sweep (formed from w^{sweeps-1})
+ * c = infinity is the plain filter (omega = 1 throughout).  A fixed number of sweeps, not a convergence test.  The values weighted
+ * are the ones the session trains on (the transformed ones under trmf_session_set_series_transform); the resident sigma2 is in
+ * that scale already.
+ *
+ * Blocking, ordered after every run() enqueued before; every rank computes the same rows on its own copy (no exchange) and ends
+ * up with the same bits; repeated calls from the same state give the same bits.  The iteration counter, the statistics, the mark,
+ * the forecast and interval scores, the noise tables and the measured multi-rank decisions are untouched.
+ *   scale    n finite positive values, or NULL: the square roots of the resident sigma2 table (trmf_session_fit_noise / _set_noise)
+ *   out      NULL, or: rows, entries, sq_err_before / sq_err_after as in TrmfAssimilateSums (unweighted); downweighted = the number
+ *            of omega < 1; weight_sum = sum of omega in fp64 in a fixed order
+ *   Wnew     NULL, or (rows - first_row) x k reals, row-major: the new rows
+ *   weights  NULL, or one real per stored entry of the rows in the session's CSR order (missing != 0; a cell stored twice is two
+ *            observations with a weight each), or (rows - first_row) x n reals, row-major (dense storage, missing == 0)
+ * 0 (first_row == rows: nothing to do, zero sums), or -1 with trmf_last_error() and W, every output and the session as they were:
+ * everything trmf_session_assimilate refuses (the message names the first row with a bad pivot); scale == NULL with no noise fitted
+ * or set; a scale that is not finite and positive; c not positive or NaN; sweeps outside 1..64; sparse storage with missing == 0
+ * (an absent entry there is an observation without a slot to report a weight in); a device failure. */
+typedef struct {
+    uint64_t rows, entries, downweighted;
+    double weight_sum, sq_err_before, sq_err_after;
+} TrmfRobustSums;
+TRMF_API int32_t trmf_session_assimilate_robust(TrmfSession *s, int32_t first_row, double c, int32_t sweeps,
+                                                const double *scale /* n, or NULL: sqrt of the resident sigma2 table */,
+                                                TrmfRobustSums *out /* or NULL */, void *Wnew /* or NULL */, void *weights /* or NULL */);
+
 /* --- forecast uncertainty: noise fit, predictive standard deviation and interval scores ---------------------------------
  * TRMF read as a linear-Gaussian state-space model (the paper's own reading): y_ij = w_i . h_j + eps_ij with eps_ij ~ N(0, sigma_j^2),
  * every latent dimension t an AR process with innovation variance q_t.  With m the largest lag and T = trmf_session_rows():
