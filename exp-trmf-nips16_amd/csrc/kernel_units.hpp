@@ -17,12 +17,13 @@
 //   unit_online.hip    assim_factor_kernel (4), assim_chain_kernel, assim_err_kernel: the forward filter of trmf_session_assimilate
 //   unit_robust.hip    assim_robust_part_kernel (4), assim_robust_solve_kernel (4), assim_robust_prior_kernel: trmf_session_assimilate_robust
 //   unit_uncertainty.hip  noise_resid_kernel (5), forecast_dist_kernel (5), the noise / psi kernels: trmf_session_fit_noise, _forecast_dist
+//   unit_adapt.hip     adapt_series_kernel (4), adapt_part_kernel (4), the full-observation forms: trmf_session_adapt_series
 //
 // A unit defines TRMF_UNIT before including this file; the non-template kernels of the shared headers are compiled by the main
 // unit only (#if !defined(TRMF_UNIT) around them).
 #pragma once
 
-// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online; the kernels of these families
+// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online, 10 online loadings; the kernels of these families
 // have their BODIES only where TRMF_UNIT_BODIES is defined -- the main unit sees declarations, so that it neither compiles them
 // nor runs them through the optimiser as `extern template` would (available_externally bodies: 3 of its 3.5 minutes))
 #if defined(TRMF_UNIT) || defined(TRMF_SINGLE_UNIT)
@@ -53,6 +54,9 @@
 #endif
 #if !defined(TRMF_UNIT) || TRMF_UNIT == 9
 #include "robust_kernels.hpp"
+#endif
+#if !defined(TRMF_UNIT) || TRMF_UNIT == 10
+#include "adapt_kernels.hpp"
 #endif
 #if !defined(TRMF_UNIT)
 #include "cg_persist_args.hpp"     // the declaration only: the body is unit_persist.hip's business
@@ -168,6 +172,14 @@ namespace trmf {
     X void noise_resid_kernel<3>(NoiseResidArgs); X void noise_resid_kernel<4>(NoiseResidArgs);                              \
     X void forecast_dist_kernel<0>(DistArgs); X void forecast_dist_kernel<1>(DistArgs); X void forecast_dist_kernel<2>(DistArgs); \
     X void forecast_dist_kernel<3>(DistArgs); X void forecast_dist_kernel<4>(DistArgs);
+
+// online loading updates (adapt_kernels.hpp): the per-series kernel and the init pass's part kernel as NT = 1..4 (k <= 64); the
+// kernels of the full-observation forms are not templates
+#define TRMF_UNIT_ADAPT(X)                                                                                                   \
+    X void adapt_series_kernel<1>(AdaptArgs); X void adapt_series_kernel<2>(AdaptArgs);                                      \
+    X void adapt_series_kernel<3>(AdaptArgs); X void adapt_series_kernel<4>(AdaptArgs);                                      \
+    X void adapt_part_kernel<1>(AdaptArgs); X void adapt_part_kernel<2>(AdaptArgs);                                          \
+    X void adapt_part_kernel<3>(AdaptArgs); X void adapt_part_kernel<4>(AdaptArgs);
 
 #define TRMF_DEFINE_KERNEL template __global__
 

@@ -398,6 +398,7 @@ struct TrmfSessionImpl : SessionXPhase {
         std::vector<real> one((size_t)n, real(1)), zero((size_t)n, real(0));
         if (tr_a.upload(a ? a : one.data(), n) || tr_b.upload(b ? b : zero.data(), n)) return kFail;
         has_transform = true;
+        adapt_stale();                                              // the series statistics absorbed values in the old scale
         return apply_series_transform();
     }
     int apply_series_transform() {
@@ -759,6 +760,7 @@ struct TrmfSessionImpl : SessionXPhase {
         const size_t nw = (size_t)(T + 1) * KP, nh = (size_t)(n + 1) * KP, nt = (size_t)nlag * k;
         if (markW.n != nw || markH.n != nh) { set_error("rewind: the session has grown since the mark (append_rows)"); return kFail; }
         if (sync()) return kFail;
+        adapt_stale();                                              // the series statistics absorbed the W that is replaced here
         TRMF_HIP_CHECK(hipMemcpyAsync(W.p, markW.p, nw * sizeof(real), hipMemcpyDeviceToDevice, stream));
         TRMF_HIP_CHECK(hipMemcpyAsync(H.p, markH.p, nh * sizeof(real), hipMemcpyDeviceToDevice, stream));
         if (nt) TRMF_HIP_CHECK(hipMemcpyAsync(theta.p, markT.p, nt * sizeof(real), hipMemcpyDeviceToDevice, stream));
@@ -1282,6 +1284,7 @@ struct TrmfSessionImpl : SessionXPhase {
         if (bad != kAssimNoBadRow) { res->bad_row = bad; return 0; }
         // ---- commit ----
         TRMF_HIP_CHECK(hipMemcpyAsync(W.p + (size_t)first_row * KP, Wn.p, (size_t)nr * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        if (first_row < ad_rows) adapt_stale();                     // rows the series statistics absorbed have changed
         if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new W
         TRMF_HIP_CHECK(hipStreamSynchronize(stream));
         res->rows = (uint64_t)nr;
@@ -1357,6 +1360,7 @@ struct TrmfSessionImpl : SessionXPhase {
         if (bad != kAssimNoBadRow) { res->bad_row = bad; return 0; }
         // ---- commit ----
         TRMF_HIP_CHECK(hipMemcpyAsync(W.p + (size_t)first_row * KP, Wn.p, (size_t)nr * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        if (first_row < ad_rows) adapt_stale();                     // rows the series statistics absorbed have changed
         if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new W
         TRMF_HIP_CHECK(hipStreamSynchronize(stream));
         res->rows = (uint64_t)nr;
@@ -1369,6 +1373,131 @@ struct TrmfSessionImpl : SessionXPhase {
         res->downweighted = (uint64_t)down;
         if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
         if (weights_out && nw) std::memcpy(weights_out, hwts.data(), hwts.size() * sizeof(real));
+        return 0;
+    }
+    // ---- online loading updates (trmf_session_series_stats_init / _adapt_series; adapt_kernels.hpp) -----------------------------------
+    // One pass for both calls (the caller has validated the rank, gamma and the state of the tables).  init: the tables over all
+    // rows from zero, H untouched (the pass's solve is discarded with its flag).  Otherwise: the active generation scaled by gamma^m
+    // plus the entries not yet absorbed, then every h_j.  Everything lands in the inactive generation and in scratch; the generation,
+    // the absorbed counts and H move after the one flag read.  No collective: every rank holds the whole Y and W and computes the
+    // same bits.  A bad pivot or a pool that cannot hold the tables is not a failure of this rank's task (res->bad_series /
+    // res->no_memory; nothing is committed): the entry point reports it on the calling thread, so the barrier of a TRMF_DEVICES
+    // group stays whole.
+    struct AdaptResult {
+        uint64_t series = 0, rows = 0, entries = 0;
+        double sq_err_before = 0, sq_err_after = 0, max_abs_change = 0;
+        int bad_series = -1, no_memory = 0;
+    };
+    int adapt_series(bool init, double forget, AdaptResult *res, real *Hout) {
+        *res = AdaptResult{};
+        if (sync()) return kFail;
+        FillStreamScope fill(stream);
+        const double gam = init ? forget : ad_gamma;
+        const int row0 = init ? 0 : ad_rows, m = T - row0;
+        const size_t PK = adapt_packed(k), nS = full ? PK : (size_t)n * PK, nR = (size_t)n * k;
+        if (init && !ad_exists) {
+            if (ad_S[0].alloc(nS, false) || ad_S[1].alloc(nS, false) || ad_r[0].alloc(nR, false) || ad_r[1].alloc(nR, false)) {
+                for (int q = 0; q < 2; q++) { ad_S[q].release(); ad_r[q].release(); }
+                res->no_memory = 1;
+                return 0;
+            }
+            ad_exists = true; ad_valid = false; ad_cur = 0;
+        }
+        const int in = ad_cur, out = 1 - ad_cur;
+        // the weights of the rows walked, gamma^(T - 1 - t), and the decay of what the tables hold
+        std::vector<real> hom;
+        if (gam != 1.0) {
+            hom.resize((size_t)std::max(m, 1));
+            for (int i = 0; i < m; i++) hom[i] = (real)std::pow(gam, (double)(T - 1 - (row0 + i)));
+        }
+        const real decay = (real)std::pow(gam, (double)m);
+        // sparse storage: where each column's walk starts; the init pass cuts long columns into items
+        std::vector<uint32_t> hstart, hfirst, hitems;
+        if (!dense) {
+            hstart.resize((size_t)n);
+            for (int j = 0; j < n; j++) hstart[j] = (uint32_t)(host_col_ptr[j] + (init ? 0u : ad_cnt[j]));
+        }
+        if (init && !full) {
+            uint64_t chunk = std::max<uint64_t>(kAdaptChunk, (nnz + kAdaptMaxItems - 1) / kAdaptMaxItems);
+            if (const char *e = test_env("TRMF_ADAPT_CHUNK")) chunk = (uint64_t)std::max(1, atoi(e));      // tests: several items per series on a small shape
+            hfirst.resize((size_t)n + 1);
+            for (int j = 0; j < n; j++) {
+                hfirst[j] = (uint32_t)(hitems.size() / 2);
+                if (host_col_ptr[j + 1] - host_col_ptr[j] > chunk)
+                    for (uint64_t b = host_col_ptr[j]; b < host_col_ptr[j + 1]; b += chunk) {
+                        hitems.push_back((uint32_t)b); hitems.push_back((uint32_t)std::min<uint64_t>(b + chunk, host_col_ptr[j + 1]));
+                    }
+            }
+            hfirst[n] = (uint32_t)(hitems.size() / 2);
+        }
+        const uint32_t nitems = (uint32_t)(hitems.size() / 2);
+        DevBuf<real> Hn, chg, mx, om, slab, U;
+        DevBuf<uint32_t> d_start, d_first, d_items;
+        DevBuf<int> flag;
+        DevBuf<double> errs;
+        SyncStreamOnExit drain(stream);
+        if (Hn.alloc((size_t)n * KP) || chg.alloc(n, false) || mx.alloc(1) || flag.alloc(1, false) || errs.alloc((size_t)4 * std::max(m, 1), false) ||
+            (!hom.empty() && om.upload(hom.data(), hom.size())) || (!dense && d_start.upload(hstart.data(), hstart.size())) ||
+            (nitems && (d_first.upload(hfirst.data(), hfirst.size()) || d_items.upload(hitems.data(), hitems.size()) ||
+                        slab.alloc((size_t)nitems * adapt_part_reals(k), false))) ||
+            (full && U.alloc((size_t)k * k, false))) return kFail;
+        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
+        const real *omp = hom.empty() ? nullptr : om.p;
+        const real *Sin = init ? nullptr : ad_S[in].p, *rin = init ? nullptr : ad_r[in].p;
+        if (!full) {
+            AdaptArgs a{Yc_ptr.p, Yc_idx.p, Yc_val.p, d_start.p, W.p, omp, Sin, rin, ad_S[out].p, ad_r[out].p, nitems ? d_first.p : nullptr,
+                        nitems ? d_items.p : nullptr, nitems ? slab.p : nullptr, H.p, Hn.p, chg.p, flag.p, decay, (real)lambdaI, row0, n, k, KP};
+            if (!with_nt(NT, [&](auto N) {
+                    if (nitems) hipLaunchKernelGGL(adapt_part_kernel<decltype(N)::value>, dim3(nitems), dim3(64), 0, stream, a);
+                    hipLaunchKernelGGL(adapt_series_kernel<decltype(N)::value>, dim3(n), dim3(64), 0, stream, a);
+                })) return unsupported_rank();
+        } else {
+            AdaptFullArgs a{dense ? nullptr : Yc_ptr.p, dense ? nullptr : Yc_idx.p, dense ? nullptr : Yc_val.p, dense ? nullptr : d_start.p,
+                            dense ? Yd_nt.p : nullptr, W.p, omp, Sin, rin, ad_S[out].p, ad_r[out].p, U.p, H.p, Hn.p, chg.p, decay, row0, T, n, k, KP, NT};
+            hipLaunchKernelGGL(adapt_full_gram_kernel, dim3((unsigned)((PK + 255) / 256)), dim3(256), 0, stream, a);
+            hipLaunchKernelGGL(adapt_full_rhs_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, a);
+            AssimFactorArgs fa{ad_S[out].p, (size_t)0, 1, U.p, flag.p, (real)lambdaI, 0, 1, k};       // the one shared system: "series 0" names it
+            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3(1), dim3(256), 0, stream, fa); }))
+                return unsupported_rank();
+            hipLaunchKernelGGL(adapt_full_subst_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, a);
+        }
+        TRMF_HIP_CHECK(hipGetLastError());
+        if (init) {                                                 // H stays: only the tables are handed over
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+            ad_cur = out; ad_valid = true; ad_gamma = forget; ad_rows = T;
+            if (!dense) { ad_cnt.resize((size_t)n); for (int j = 0; j < n; j++) ad_cnt[j] = (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j]); }
+            res->series = (uint64_t)n; res->rows = (uint64_t)T;
+            res->entries = full ? (uint64_t)T * (uint64_t)n : nnz;
+            return 0;
+        }
+        hipLaunchKernelGGL(adapt_max_kernel, dim3(1), dim3(256), 0, stream, chg.p, n, mx.p);
+        if (m > 0) {   // the squared errors of the absorbed rows with H as it is and as it will be (assim_err_kernel's reading of an entry)
+            for (int pass = 0; pass < 2; pass++) {
+                AssimErrArgs ea{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr,
+                                pass ? Hn.p : H.p, W.p, W.p, 0, 0, errs.p + (size_t)2 * m * pass, row0, m, n, KP, full ? 1 : 0};
+                hipLaunchKernelGGL(assim_err_kernel, dim3(m), dim3(256), 0, stream, ea);
+            }
+        }
+        TRMF_HIP_CHECK(hipGetLastError());
+        int bad = kAdaptNoBadSeries;
+        real hmx = 0;
+        std::vector<double> herr((size_t)4 * std::max(m, 1), 0.0);
+        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(&hmx, mx.p, sizeof(real), hipMemcpyDeviceToHost, stream));
+        if (m > 0) TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, (size_t)4 * m * sizeof(double), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (bad != kAdaptNoBadSeries) { res->bad_series = bad; return 0; }
+        if (Hout && download_padded(Hn, Hout, (size_t)n)) return kFail;
+        // ---- commit ----
+        TRMF_HIP_CHECK(hipMemcpyAsync(H.p, Hn.p, (size_t)n * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new H
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        ad_cur = out; ad_rows = T;
+        if (!dense) for (int j = 0; j < n; j++) ad_cnt[j] = (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j]);
+        res->series = (uint64_t)n; res->rows = (uint64_t)m;
+        res->entries = full ? (uint64_t)m * (uint64_t)n : host_row_ptr[T] - host_row_ptr[row0];
+        for (int r = 0; r < m; r++) { res->sq_err_before += herr[2 * r]; res->sq_err_after += herr[(size_t)2 * m + 2 * r]; }
+        res->max_abs_change = (double)hmx;
         return 0;
     }
     // New regularisation weights for the iterations enqueued from now on: the session's own copies (F-solve, Theta-solve, the

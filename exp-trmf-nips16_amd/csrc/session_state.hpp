@@ -227,6 +227,17 @@ struct SessionState {
     DevBuf<double> iv_table[2];
     int iv_cur = 0;
     uint64_t iv_rows = 0;
+    // ---- online loading updates (trmf_session_series_stats_init / _adapt_series; adapt_kernels.hpp) ---------------------------------
+    // Per series the packed S_j and r_j (one shared S on the full-observation forms), absent until asked for, resident on every
+    // rank.  Two generations: a call reads ad_cur and writes the other, and ad_cur moves only once the flag has been read.  ad_cnt:
+    // sparse storage, the stored entries of each column already absorbed (append_rows puts new entries behind them).  Stale once
+    // a row they absorbed may have changed (adapt_stale(): run, rewind, assimilate below ad_rows, a new series transform).
+    DevBuf<real> ad_S[2], ad_r[2];
+    std::vector<uint32_t> ad_cnt;
+    int ad_cur = 0, ad_rows = 0;
+    bool ad_exists = false, ad_valid = false;
+    double ad_gamma = 1;
+    void adapt_stale() { ad_valid = false; }
     // fp32: four systems per wavefront (fsolve_quad_kernel); fp64: one system per wavefront, factorised in the MFMA
     // accumulator layout (fsolve_mfma_kernel)
     // X-side Gram build across ranks: sharded rows + all-gather of G (64 MB at config 3) pays only when a

@@ -341,7 +341,7 @@ TrmfSession *trmf_session_create(const PyMatrix *Y, const uint32_t *lag_set, uin
 int32_t trmf_session_run(TrmfSession *s, int32_t iters) {
     if (!s) return kFail;
     DeviceGuard guard;
-    return guard.ok ? HND(s)->all([&](TrmfSessionImpl *t) { return t->run(iters); }) : kFail;
+    return guard.ok ? HND(s)->all([&](TrmfSessionImpl *t) { if (iters > 0) t->adapt_stale(); return t->run(iters); }) : kFail;   // (W is about to change)
 }
 int32_t trmf_session_log_norms(TrmfSession *s, int32_t on) {
     if (!s) return kFail;
@@ -618,6 +618,67 @@ int32_t trmf_session_assimilate_robust(TrmfSession *s, int32_t first_row, double
         out->rows = res[0].rows; out->entries = res[0].entries; out->downweighted = res[0].downweighted;
         out->weight_sum = res[0].weight_sum; out->sq_err_before = res[0].sq_err_before; out->sq_err_after = res[0].sq_err_after;
     }
+    return 0;
+}
+
+// Online loading updates: the arguments and the state of the tables are checked on the calling thread before any rank's worker runs
+// (see trmf_session_set_heldout); a bad pivot or a pool without room is found by every rank alike and reported here.
+static int adapt_call(TrmfSession *s, bool init, double forget, TrmfAdaptSums *out, void *Hnew) {
+    const std::string what = init ? "series_stats_init" : "adapt_series";
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (f->k > kMaxRank) {
+        set_error(what + ": online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
+        return kFail;
+    }
+    if (init && !(forget > 0 && forget <= 1)) { set_error("series_stats_init: forget must lie in (0, 1]"); return kFail; }
+    if (!init && !f->ad_exists) { set_error("adapt_series: no series statistics (trmf_session_series_stats_init first)"); return kFail; }
+    if (!init && !f->ad_valid) {
+        set_error("adapt_series: the series statistics are stale: rows they absorbed may have changed (run, rewind, assimilate below the absorbed "
+                  "rows, or a new series transform); initialise them again (trmf_session_series_stats_init)");
+        return kFail;
+    }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    const bool grouped = HND(s)->group != nullptr;
+    std::vector<TrmfSessionImpl::AdaptResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
+    if (HND(s)->all([&](TrmfSessionImpl *t) {
+            const int slot = grouped ? t->comm->rank : 0;
+            return t->adapt_series(init, forget, &res[slot], slot == 0 ? (real *)Hnew : nullptr);
+        })) return kFail;
+    for (const auto &r : res) {
+        if (r.no_memory) {
+            const size_t PK = adapt_packed(f->k);
+            const double bytes = 2.0 * ((f->full ? (double)PK : (double)f->n * (double)PK) + (double)f->n * f->k) * sizeof(real);
+            set_error("series_stats_init: the device pool cannot hold the series statistics (two generations of n k (k + 1) / 2 + n k reals: " +
+                      std::to_string((unsigned long long)bytes) + " bytes); nothing was changed");
+            return kFail;
+        }
+        if (r.bad_series >= 0) {
+            set_error("adapt_series: series " + std::to_string(r.bad_series) + ": a pivot of S + lambdaI I is not positive and finite (lambdaI == 0 and "
+                      "a series with fewer independent rows than the rank?); nothing was changed");
+            return kFail;
+        }
+    }
+    if (out) {
+        out->series = res[0].series; out->rows = res[0].rows; out->entries = res[0].entries;
+        out->sq_err_before = res[0].sq_err_before; out->sq_err_after = res[0].sq_err_after; out->max_abs_change = res[0].max_abs_change;
+    }
+    return 0;
+}
+int32_t trmf_session_series_stats_init(TrmfSession *s, double forget) {
+    if (!s) { set_error("null session"); return kFail; }
+    return adapt_call(s, true, forget, nullptr, nullptr);
+}
+int32_t trmf_session_adapt_series(TrmfSession *s, TrmfAdaptSums *out, void *Hnew) {
+    if (!s) { set_error("null session"); return kFail; }
+    return adapt_call(s, false, 1.0, out, Hnew);
+}
+int32_t trmf_session_series_stats_info(TrmfSession *s, int32_t *valid, int32_t *absorbed_rows, double *forget) {
+    if (!s) { set_error("null session"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (valid) *valid = !f->ad_exists ? 0 : f->ad_valid ? 1 : -1;
+    if (absorbed_rows) *absorbed_rows = f->ad_exists ? f->ad_rows : 0;
+    if (forget) *forget = f->ad_exists ? f->ad_gamma : 1.0;
     return 0;
 }
 

@@ -167,13 +167,17 @@ class Model(object):
         return forecast_std(self.H, self.lag_set, self.lag_val, noise[0], noise[1], window, transform=self.transform)
 
     # ---- online update ----------------------------------------------------------------------------
-    def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True, robust_c=None, robust_sweeps=4, scale=None):
+    def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0):
         """A new ``Model`` grown by the ``Ynew.shape[0]`` timestamps of ``Ynew`` (raw values; a transform of this model is
         applied first): H, the lag weights and the rows this model has stay as they are, every new row of W is solved from its
         own observations and the AR prior of the rows before it (``trmf.online.filter_rows``; the host form of
         ``Session.update``).  This model is left untouched.  With ``robust_c`` the rows are solved with Huber weights
         (``trmf.online.robust_filter_rows``: ``robust_sweeps`` rounds, ``scale`` per series, default ``sqrt(self.noise[0])`` of
-        ``fit_noise``); the last sweep's weights are kept as ``robust_weights`` of the new model, whose ``noise`` is this model's."""
+        ``fit_noise``); the last sweep's weights are kept as ``robust_weights`` of the new model, whose ``noise`` is this model's.
+        With ``adapt`` the loadings follow (the host form of ``Session.update(adapt=True)``): this model must carry
+        ``series_stats`` (``init_series_stats``); a copy of them absorbs the new rows of the filtered W (unweighted, also under
+        ``robust_c``) and the new model's H is their ridge solution with ``lambdaI`` (``trmf.online.series_ridge`` as a recursion).
+        ``forget`` is fixed when the statistics are built: a different value here is refused."""
         from .online import filter_rows, robust_filter_rows
         if self.transform is not None:
             if smat.issparse(Ynew):
@@ -193,11 +197,34 @@ class Model(object):
             grown, weights = robust_filter_rows(grown, self.H, self.lag_set, self.lag_val, Ynew, self.m, lambdaI, lambdaAR, missing,
                                                 scale, robust_c, robust_sweeps)
         out = Model.from_arrays(grown, self.H.copy(), self.lag_val.copy(), self.lag_set.copy(), transform=self.transform)
+        stats = getattr(self, 'series_stats', None)
+        if adapt:
+            import copy
+            if stats is None:
+                raise ValueError('assimilate: adapt needs series statistics (Model.init_series_stats) before the first block')
+            if float(forget) != stats.forget:
+                raise ValueError('assimilate: forget {!r} differs from the {!r} the series statistics were built with'.format(forget, stats.forget))
+            if bool(missing) != stats.missing:
+                raise ValueError('assimilate: missing differs from the setting the series statistics were built with')
+            stats = copy.deepcopy(stats).absorb(grown, Ynew)
+            out.H[:] = stats.solve(lambdaI)
+            out.series_stats = stats
         if weights is not None:
             out.robust_weights = weights
             if getattr(self, 'noise', None) is not None:
                 out.noise = self.noise
         return out
+
+    def init_series_stats(self, Y, forget=1.0, missing=True):
+        """Attach the per-series statistics of ``assimilate(adapt=True)`` (``trmf.online.SeriesStats``), built over the training
+        matrix ``Y`` (raw values; a transform of this model is applied first) with W as it is.  H is not changed."""
+        from .online import SeriesStats
+        if self.transform is not None:
+            if smat.issparse(Y):
+                raise ValueError('init_series_stats: a series transform needs dense rows')
+            Y = self.transform.preprocess(np.asarray(Y)).astype(self.W.dtype)
+        self.series_stats = SeriesStats(self.W, Y, forget, missing)
+        return self
 
     # ---- construction ------------------------------------------------------------------------------
     @staticmethod

@@ -164,3 +164,128 @@ def robust_filter_rows(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambda
         else:
             weights[r, cols] = om
     return out, weights
+
+
+# ---- online loading updates: the rows of H refitted from new rows (trmf_session_series_stats_init / _adapt_series) ---------------
+def _series_entries(Y, missing):
+    """Per series the (timestamps, values) of its observations in stored order.  Sparse ``Y``: the stored entries of the column
+    (a cell stored twice is two observations); an array: its non-zeros with ``missing``, every row without."""
+    n = Y.shape[1]
+    if smat.issparse(Y):
+        Yc = Y if Y.format == 'csc' else Y.tocsc()
+        return [(Yc.indices[Yc.indptr[j]:Yc.indptr[j + 1]].astype(np.int64), Yc.data[Yc.indptr[j]:Yc.indptr[j + 1]]) for j in range(n)]
+    Ya = np.asarray(Y)
+    if missing:
+        return [(np.nonzero(Ya[:, j])[0], Ya[np.nonzero(Ya[:, j])[0], j]) for j in range(n)]
+    rows = np.arange(Ya.shape[0])
+    return [(rows, Ya[:, j]) for j in range(n)]
+
+
+def _check_forget(forget, what):
+    forget = float(forget)
+    if not (0.0 < forget <= 1.0):
+        raise ValueError('{}: forget must lie in (0, 1], not {!r}'.format(what, forget))
+    return forget
+
+
+def _ridge_solve(S, r, lam, j, what):
+    """(S + lam I)^-1 r.  The Cholesky factorisation decides whether the system is positive definite (the device's test); the
+    solution is LAPACK's general solve (LU with partial pivoting, residual-stable row by row), which on the ridge-conditioned
+    systems of a series with fewer entries than unknowns lands closer to the exact solution than the two triangular solves do."""
+    A = S + lam * np.eye(S.shape[0], dtype=S.dtype)
+    try:
+        if not np.all(np.isfinite(A)):
+            raise np.linalg.LinAlgError('not finite')
+        L = np.linalg.cholesky(A)
+        if not (np.all(np.isfinite(L)) and np.all(np.diagonal(L) > 0)):
+            raise np.linalg.LinAlgError('pivot')
+    except np.linalg.LinAlgError:
+        raise ValueError('{}: series {}: S + lambdaI I is not positive definite'.format(what, j))
+    return np.linalg.solve(A, r)
+
+
+def series_ridge(W, Y, lambdaI, forget=1.0, missing=True):
+    """The loadings the history asks for with ``W`` (T x k) as it is: the specification of ``trmf_session_adapt_series``.  Per
+    series ``j`` the weighted ridge ::
+
+        S_j = sum_t om_t w_t w_t^T,   r_j = sum_t om_t y_tj w_t,   om_t = forget^(T - 1 - t),   h_j = (S_j + lambdaI I)^-1 r_j
+
+    over the stored entries of column ``j`` of a sparse ``Y`` (a cell stored twice is two observations) or the non-zeros of an
+    array (``missing``); without ``missing`` ``S`` is shared, the sum over every row, an absent entry reading as 0.
+    ``forget == 1`` is the training F-solve for the current ``W``.  All arithmetic is in the dtype of ``W``; ``lambdaI`` is cast
+    to it, and the ridge is not decayed.  Returns H (n x k).  ``ValueError`` for ``forget`` outside (0, 1], a row count that does
+    not match, or a series whose system is not positive definite (possible only with ``lambdaI == 0``; the message names it)."""
+    W = np.asarray(W)
+    dt = W.dtype
+    T, k = W.shape
+    forget = _check_forget(forget, 'series_ridge')
+    if Y.shape[0] != T:
+        raise ValueError('series_ridge: Y has {} rows, W {}'.format(Y.shape[0], T))
+    lam = dt.type(lambdaI)
+    om = (forget ** (T - 1 - np.arange(T, dtype=np.float64))).astype(dt)
+    H = np.zeros((Y.shape[1], k), dtype=dt)
+    Sall = (W * om[:, None]).T.dot(W) if not missing else None
+    for j, (rows, y) in enumerate(_series_entries(Y, missing)):
+        Wj = W[rows] * om[rows][:, None]
+        S = Wj.T.dot(W[rows]) if missing else Sall
+        H[j] = _ridge_solve(S, Wj.T.dot(np.asarray(y, dtype=dt)), lam, j, 'series_ridge')
+    return H
+
+
+class SeriesStats(object):
+    """``series_ridge`` as a recursion -- recursive least squares with forgetting, the form the device keeps resident: ``S_j`` and
+    ``r_j`` per series (one shared ``S`` without ``missing``), built over ``Y`` with ``W`` as it is, then grown block by block ::
+
+        S <- forget^m S + sum_new forget^(T - 1 - t) w_t w_t^T        (r likewise; m new rows, T the new row count)
+
+    one rank-1 update per entry in stored order, as the device adds them, all in the dtype of ``W``.  ``solve(lambdaI)`` gives
+    the loadings.  With
+    ``forget == 1`` it equals ``series_ridge`` over the grown matrix up to the summation order; in float32 it is the yardstick
+    the device is held to."""
+
+    def __init__(self, W, Y, forget=1.0, missing=True):
+        W = np.asarray(W)
+        self.forget = _check_forget(forget, 'SeriesStats')
+        self.missing = bool(missing)
+        self.dtype = W.dtype
+        self.k = W.shape[1]
+        self.n = Y.shape[1]
+        self.rows = 0
+        self.S = np.zeros((self.n if self.missing else 1, self.k, self.k), dtype=self.dtype)
+        self.r = np.zeros((self.n, self.k), dtype=self.dtype)
+        self.absorb(W, Y)
+
+    def absorb(self, W, Ynew):
+        """Absorb the rows ``self.rows .. T-1`` of ``W`` (T x k, as it is now) with their observations ``Ynew`` (T - self.rows rows)."""
+        W = np.asarray(W)
+        T = W.shape[0]
+        m = T - self.rows
+        if W.shape[1] != self.k or W.dtype != self.dtype:
+            raise ValueError('SeriesStats.absorb: W is {} {}, {} columns of {} were expected'.format(W.shape, W.dtype, self.k, self.dtype))
+        if m < 0 or Ynew.shape[0] != m or Ynew.shape[1] != self.n:
+            raise ValueError('SeriesStats.absorb: Ynew is {}, rows {}..{} of {} series were expected'.format(Ynew.shape, self.rows, T, self.n))
+        dt = self.dtype
+        decay = dt.type(self.forget ** m)
+        self.S *= decay
+        self.r *= decay
+        om = (self.forget ** (m - 1 - np.arange(m, dtype=np.float64))).astype(dt)
+        Wn = W[self.rows:]
+        if not self.missing:
+            for t in range(m):
+                self.S[0] += np.outer(om[t] * Wn[t], Wn[t])
+        for j, (rows, y) in enumerate(_series_entries(Ynew, self.missing)):
+            y = np.asarray(y, dtype=dt)
+            for e, t in enumerate(rows):
+                aw = om[t] * Wn[t]
+                if self.missing:
+                    self.S[j] += np.outer(aw, Wn[t])
+                self.r[j] += aw * y[e]
+        self.rows = T
+        return self
+
+    def solve(self, lambdaI):
+        lam = self.dtype.type(lambdaI)
+        H = np.zeros((self.n, self.k), dtype=self.dtype)
+        for j in range(self.n):
+            H[j] = _ridge_solve(self.S[j if self.missing else 0], self.r[j], lam, j, 'SeriesStats.solve')
+        return H

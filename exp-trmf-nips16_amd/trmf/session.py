@@ -63,6 +63,16 @@ class TrmfRobustSums(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TrmfAdaptSums(ctypes.Structure):
+    """Sums of an online loading update (include/trmf_abi.h): series refitted, rows and entries absorbed, the squared error of the
+    absorbed entries with H as it was / as it is, the largest change of an element of H."""
+    _fields_ = [('series', c_uint64), ('rows', c_uint64), ('entries', c_uint64), ('sq_err_before', c_double), ('sq_err_after', c_double),
+                ('max_abs_change', c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class TrmfNoiseStats(ctypes.Structure):
     """Summary of a noise fit (include/trmf_abi.h)."""
     _fields_ = [('pooled_sigma2', c_double), ('sigma2_min', c_double), ('sigma2_max', c_double), ('series_pooled', c_uint64),
@@ -152,6 +162,11 @@ def bind(lib):
     if hasattr(lib, 'trmf_session_assimilate_robust'):    # (absent from libraries built before the robust online updates)
         lib.trmf_session_assimilate_robust.argtypes = [c_void_p, c_int32, c_double, c_int32, c_void_p, POINTER(TrmfRobustSums), c_void_p, c_void_p]
         lib.trmf_session_assimilate_robust.restype = c_int32
+    if hasattr(lib, 'trmf_session_adapt_series'):     # (absent from libraries built before the online loading updates)
+        lib.trmf_session_series_stats_init.argtypes = [c_void_p, c_double]; lib.trmf_session_series_stats_init.restype = c_int32
+        lib.trmf_session_adapt_series.argtypes = [c_void_p, POINTER(TrmfAdaptSums), c_void_p]; lib.trmf_session_adapt_series.restype = c_int32
+        lib.trmf_session_series_stats_info.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_double)]
+        lib.trmf_session_series_stats_info.restype = c_int32
     if hasattr(lib, 'trmf_session_fit_noise'):        # (absent from libraries built before the forecast uncertainty)
         lib.trmf_session_fit_noise.argtypes = [c_void_p, POINTER(TrmfNoiseStats)]; lib.trmf_session_fit_noise.restype = c_int32
         lib.trmf_session_noise.argtypes = [c_void_p, c_void_p, c_void_p]; lib.trmf_session_noise.restype = c_int32
@@ -323,22 +338,59 @@ class Session(object):
         out = (sums.as_dict(),) + ((Wnew,) if return_latent else ()) + ((weights,) if return_weights else ())
         return out if len(out) > 1 else out[0]
 
-    def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None):
+    def init_series_stats(self, forget=1.0):
+        """Build the resident per-series statistics ``S_j``, ``r_j`` of ``adapt_series`` over all rows with W as it is, weighted by
+        ``forget ** (rows() - 1 - t)`` (``forget`` in (0, 1]; 1: no forgetting).  One pass as heavy as an F-solve; H is not
+        changed.  The tables cost ``n k (k + 1) / 2`` reals twice (one shared ``S`` without ``missing``)."""
+        self._check(self.lib.trmf_session_series_stats_init(self.handle, float(forget)), 'trmf_session_series_stats_init')
+
+    def adapt_series(self, return_loadings=False):
+        """Online loading update on the device: the rows appended since the statistics were last brought up to date are absorbed
+        into them (``S <- forget^m S + sum_new forget^(rows-1-t) w_t w_t^T`` with W as it is now, ``r`` likewise) and every row of H
+        is refitted, ``h_j = (S_j + lambdaI I)^-1 r_j`` (``trmf.online.series_ridge`` is the same computation in NumPy, a direct
+        sum).  W and the lag weights stay.  Huber weights of ``assimilate_robust`` are not part of the statistics: the cells enter
+        unweighted.  Returns ``{'series', 'rows', 'entries', 'sq_err_before', 'sq_err_after', 'max_abs_change'}``, or ``(sums,
+        Hnew)`` with ``return_loadings``.  A refused call (no statistics, or stale ones after ``run``, ``rewind``, ``assimilate``
+        below the absorbed rows or a new transform; rank above 64; a series whose system is not positive definite, possible only
+        with ``lambdaI == 0``) raises and leaves the session as it was."""
+        sums = TrmfAdaptSums()
+        Hnew = np.empty((self.model.n, self.model.k), dtype=self.model.W.dtype) if return_loadings else None
+        self._check(self.lib.trmf_session_adapt_series(self.handle, byref(sums), Hnew.ctypes.data if Hnew is not None and Hnew.size else None),
+                    'trmf_session_adapt_series')
+        return (sums.as_dict(), Hnew) if return_loadings else sums.as_dict()
+
+    def series_stats_info(self):
+        """``{'valid', 'stale', 'absorbed_rows', 'forget'}`` of the resident series statistics (absent ones: neither valid nor stale)."""
+        v, rows, g = c_int32(0), c_int32(0), c_double(1.0)
+        self._check(self.lib.trmf_session_series_stats_info(self.handle, byref(v), byref(rows), byref(g)), 'trmf_session_series_stats_info')
+        return {'valid': v.value == 1, 'stale': v.value == -1, 'absorbed_rows': int(rows.value), 'forget': float(g.value)}
+
+    def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0):
         """Absorb the new timestamps ``Ynew`` (as for ``append_rows``): append them, assimilate the new block, run ``iters``
         ALS iterations if asked for.  ``self.model`` is replaced by a host model of ``rows()`` timestamps (H, lag weights, lag
         set and transform carried over; its arrays are filled by the next ``download()``).  Returns the sums of ``assimilate``;
         with ``robust_c`` the block is absorbed by ``assimilate_robust(before, robust_c, robust_sweeps, scale)`` and its sums
-        are returned."""
+        are returned.  With ``adapt`` the loadings follow: the series statistics are initialised with ``forget`` before the
+        append if the session has none (existing ones keep their own), ``adapt_series`` runs after the block has been assimilated
+        and ``(sums, adapt_sums)`` is returned."""
         before = self.rows()
+        if adapt:
+            info = self.series_stats_info()
+            if info['stale']:       # before anything is appended: a refused update leaves the session as it was
+                raise RuntimeError('update: the series statistics are stale (run, rewind, assimilate below the absorbed rows or a new '
+                                   'transform since they were built); initialise them again (init_series_stats)')
+            if not info['valid']:
+                self.init_series_stats(forget)
         self.append_rows(Ynew)
         old = self.model
         grown = np.zeros((self.rows(), old.k), dtype=old.W.dtype, order='C')
         grown[:min(before, old.m)] = old.W[:before]
         self.model = type(old).from_arrays(grown, old.H.copy(), old.lag_val.copy(), old.lag_set.copy(), transform=old.transform)
         sums = self.assimilate(before) if robust_c is None else self.assimilate_robust(before, robust_c, robust_sweeps, scale)
+        adapted = self.adapt_series() if adapt else None
         if iters:
             self.run(int(iters))
-        return sums
+        return (sums, adapted) if adapt else sums
 
     def set_transform(self, transform):
         """Train on ``transform.preprocess`` of the raw dense Y held by the session (``None``: the raw values); the

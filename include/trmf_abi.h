@@ -380,6 +380,59 @@ TRMF_API int32_t trmf_session_assimilate_robust(TrmfSession *s, int32_t first_ro
                                                 const double *scale /* n, or NULL: sqrt of the resident sigma2 table */,
                                                 TrmfRobustSums *out /* or NULL */, void *Wnew /* or NULL */, void *weights /* or NULL */);
 
+/* --- online loading updates: refit H from new rows without retraining ----------------------------------------------------
+ * The other half of the online updates above: those absorb new timestamps into rows of W with H fixed; these refit the series
+ * loadings H from new rows in O(new data) with W fixed.  The F-solve of series j depends on the history only through
+ *   S_j = sum_t om_t w_t w_t^T,   r_j = sum_t om_t y_tj w_t     t over Omega_j, the stored entries of column j (missing != 0;
+ *                                                               a cell stored twice is two observations)
+ *   h_j = (S_j + lambdaI I)^-1 r_j                              the system the training F-solve builds
+ * With om_t = gamma^(rows - 1 - t), gamma in (0, 1], the sums decay and old data fades: recursive least squares with forgetting.
+ * gamma == 1 gives what a full F-solve over the grown history gives for the current W.  On the full-observation forms (dense
+ * storage; sparse storage with missing == 0, where an absent entry reads 0) S is shared: the sum over every row, and r_j sums
+ * the stored entries.
+ *
+ * Resident state, absent until trmf_session_series_stats_init: per series the packed upper triangle of S_j (k (k + 1) / 2 reals in
+ * the element type) and r_j (k reals) -- one shared S plus the r_j on the full-observation forms -- in two generations (a call
+ * reads one and writes the other: n k (k + 1) / 2 reals twice), gamma, the number of rows absorbed, and for sparse storage the
+ * number of stored entries of each column already absorbed (append_rows puts a block's entries behind the column's old ones,
+ * whether or not the input is canonical, so the entries not yet absorbed are always the column's tail).
+ *
+ * trmf_session_series_stats_init(s, forget): builds the tables over all rows with W as it is and om_t = forget^(rows - 1 - t); one
+ *   pass as heavy as an F-solve.  H is not changed.  gamma is fixed until the next init.
+ * trmf_session_adapt_series(s, out, Hnew): with m = rows - absorbed rows,  S <- gamma^m S + sum_new gamma^(rows - 1 - t) w_t w_t^T
+ *   and r likewise, the sums over the entries not yet absorbed in stored order with W as it is now; then every series'
+ *   h_j = (S_j + lambdaI I)^-1 r_j by Cholesky in the element type and both substitutions.  lambdaI is the session's current one
+ *   cast to the element type; the ridge is not decayed.  y is the value the session trains on (the transformed one under an
+ *   active series transform).  H is replaced: forecast*, assimilate*, download, objective and the next run see the new one.  A
+ *   series without a stored entry gets h_j = 0 when lambdaI > 0.  m == 0 is allowed (H refitted from the tables as they are,
+ *   for example after trmf_session_set_lambdas).  Under trmf_session_assimilate_robust the cells still enter these sums
+ *   UNWEIGHTED: the Huber weights are not part of the statistics.
+ * trmf_session_series_stats_info: valid = 1 (usable), 0 (absent), -1 (stale); the rows absorbed; gamma.
+ *
+ * The tables go stale when a row they absorbed may have changed: trmf_session_run, trmf_session_rewind, trmf_session_assimilate /
+ * _assimilate_robust with first_row below the absorbed rows, trmf_session_set_series_transform.  Stale tables are refused with a
+ * message that says to initialise again.  append_rows, set_lambdas, fit_noise / set_noise and forecast* leave them valid.
+ *
+ * Blocking, ordered after every run() enqueued before; every rank computes every series on its own copy (no exchange) and ends
+ * up with the same bits; repeated identical call sequences give the same bits (no floating-point atomics, fixed summation
+ * orders).  adapt_series does not touch the iteration counter, the statistics, the mark, the forecast and interval scores, the
+ * noise tables or the measured multi-rank decisions.
+ *   out    NULL, or: series refitted; rows and entries absorbed by this call; sq_err_before / sq_err_after = sum over the absorbed
+ *          entries of (y - w_t . h_j)^2 with H as it was / as it is now, in fp64 and a fixed order (trmf_session_assimilate's
+ *          reading of an entry); max_abs_change = max |H_new - H_old|
+ *   Hnew   NULL, or n x k reals, row-major: the new loadings
+ * 0, or -1 with trmf_last_error() and H, the tables, the outputs and the session as they were: rank k > 64 (like the other online
+ * features); forget outside (0, 1]; no tables, or stale ones; an S_j + lambdaI I with a pivot that is not positive and finite
+ * (possible only with lambdaI == 0 and a series with fewer independent rows than k; the message names the smallest such series);
+ * a device pool that cannot hold the tables; a device failure. */
+typedef struct {
+    uint64_t series, rows, entries;
+    double sq_err_before, sq_err_after, max_abs_change;
+} TrmfAdaptSums;
+TRMF_API int32_t trmf_session_series_stats_init(TrmfSession *s, double forget);
+TRMF_API int32_t trmf_session_adapt_series(TrmfSession *s, TrmfAdaptSums *out /* or NULL */, void *Hnew /* or NULL: n x k, row-major */);
+TRMF_API int32_t trmf_session_series_stats_info(TrmfSession *s, int32_t *valid, int32_t *absorbed_rows, double *forget);
+
 /* --- forecast uncertainty: noise fit, predictive standard deviation and interval scores ---------------------------------
  * TRMF read as a linear-Gaussian state-space model (the paper's own reading): y_ij = w_i . h_j + eps_ij with eps_ij ~ N(0, sigma_j^2),
  * every latent dimension t an AR process with innovation variance q_t.  With m the largest lag and T = trmf_session_rows():
