@@ -1375,6 +1375,157 @@ struct TrmfSessionImpl : SessionXPhase {
         if (weights_out && nw) std::memcpy(weights_out, hwts.data(), hwts.size() * sizeof(real));
         return 0;
     }
+    // ---- the fixed-interval smoother (trmf_session_smooth; smooth_kernels.hpp) ------------------------------------------------------
+    // Rows [first_row, T) of W become the joint minimiser of the objective restricted to them (the caller has validated first_row,
+    // the lag set, the rank, the window against the cap, rtol and max_iter).  Stage A is assimilate()'s: Grams and right-hand sides
+    // of the window by the X phase's builders, the factors of ALL rows at once (they precondition every step).  Stage B is the
+    // PCG, three launches per step on the session's stream; the stop is decided on the device, and the host only follows it
+    // through one pinned word: it stays kSmoothLook steps ahead of the device and stops enqueuing when it sees the stop (launches
+    // after the stop return at once, so the bits do not depend on how far ahead it was).  A word that does not move for 2 s is answered
+    // by a stream synchronisation and a re-read, never by enqueuing the remaining steps blind.  Everything lands in scratch; W changes
+    // by ONE device copy after the flag and the sums have been read.  A call that reaches max_iter commits as well: every CG
+    // iterate lowers J_win.  No collective: every rank holds the whole Y and W and computes the same bits.
+    struct SmoothResult {
+        uint64_t rows = 0, entries = 0;
+        int iterations = 0, converged = 0;
+        double residual = 0, sq_err_before = 0, sq_err_after = 0, objective_before = 0, objective_after = 0;
+        int bad_row = -1;
+    };
+    static int smooth_max_rows() {
+        int cap = kSmoothMaxRows;
+        if (const char *e = test_env("TRMF_SMOOTH_MAX_ROWS")) cap = std::max(1, atoi(e));      // tests: the refusal on a small shape
+        return cap;
+    }
+    static constexpr int kSmoothLook = 4;
+    unsigned int smooth_seq = 0;
+    int smooth(int first_row, double rtol, int max_iter, SmoothResult *res, real *Wout) {
+        *res = SmoothResult{};
+        if (sync()) return kFail;
+        const int m = T - first_row;
+        if (m <= 0) return 0;
+        if (ensure_cg_note()) { set_error("smooth: no pinned host memory for the word the stop is followed through"); return kFail; }
+        unsigned int *note = cg_note + 8;                       // a word of its own in the X-solve's pinned line
+        FillStreamScope fill(stream);
+        DevBuf<real> Wn, flat, U, vec, part;
+        DevBuf<int> flag;
+        DevBuf<double> errs, objs;
+        DevBuf<SmoothState> state;
+        SyncStreamOnExit drain(stream);
+        const size_t V = (size_t)m * 64;
+        if (Wn.alloc((size_t)m * KP) || (Wout && flat.alloc((size_t)m * k, false)) || U.alloc((size_t)m * k * k, false) || vec.alloc(7 * V) ||
+            part.alloc((size_t)2 * m) || flag.alloc(1, false) || errs.alloc((size_t)2 * m, false) || objs.alloc((size_t)4 * m, false) || state.alloc(1))
+            return kFail;
+        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
+        // stage A
+        if (full) {
+            if (y_times_factor(false, H.p, Bv.p, dense ? 0u : (uint32_t)first_row, (uint32_t)T)) return kFail;        // rows of Y H
+            if (small_gram(H.p, n, real(0), GSx.p, stream)) return kFail;                                             // H^T H
+        } else if (launch_gram_x_rows((uint32_t)first_row, (uint32_t)T)) return kFail;
+        TRMF_HIP_CHECK(hipGetLastError());
+        const real lamAR = (real)lambdaAR, lamI = (real)lambdaI;
+        {
+            AssimFactorArgs fa{Gmat(), full ? (size_t)0 : xp.gstride, gpacked ? 1 : 0, U.p, flag.p, lamI + lamAR, first_row, m, k};
+            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3((m + 3) / 4), dim3(256), 0, stream, fa); }))
+                return unsupported_rank();
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        // stage B
+        const unsigned int seq = ++smooth_seq & 0x1ffffu;
+        __atomic_store_n(note, 0u, __ATOMIC_RELEASE);
+        SmoothArgs sa{};
+        sa.W = W.p; sa.Bv = Bv.p; sa.G = Gmat(); sa.gstride = full ? (size_t)0 : xp.gstride; sa.packed = gpacked ? 1 : 0; sa.U = U.p;
+        sa.lag_set = lag_set.p; sa.theta = theta.p;
+        sa.x = vec.p; sa.r = vec.p + V; sa.z = vec.p + 2 * V; sa.q = vec.p + 3 * V; sa.e = vec.p + 4 * V; sa.p[0] = vec.p + 5 * V; sa.p[1] = vec.p + 6 * V;
+        sa.part_rz = part.p; sa.part_pq = part.p + m; sa.st = state.p; sa.flag = flag.p; sa.note = note; sa.note_seq = seq;
+        sa.tol2 = rtol * rtol; sa.lamI = lamI; sa.lamAR = lamAR;
+        sa.first_row = first_row; sa.m = m; sa.k = k; sa.KP = KP; sa.NT = NT; sa.nlag = nlag;
+        sa.lds_theta = smooth_theta_lds_bytes(nlag) <= kLdsDefault && !test_env("TRMF_FORECAST_GLOBAL") ? 1 : 0;
+        const size_t lds_th = sa.lds_theta ? smooth_theta_lds_bytes(nlag) : 0, lds_up = smooth_update_lds_bytes(k);
+        const dim3 rows4((m + 3) / 4);
+        auto step = [&](int mode, int j) {
+            hipLaunchKernelGGL(smooth_ar_kernel, mode == SMOOTH_LAST ? dim3(1) : rows4, dim3(256), lds_th, stream, sa, mode, j);
+            if (mode == SMOOTH_LAST) return;
+            hipLaunchKernelGGL(smooth_apply_kernel, rows4, dim3(256), lds_th, stream, sa, mode, j);
+            hipLaunchKernelGGL(smooth_update_kernel, dim3(m), dim3(64), lds_up, stream, sa, mode, j);
+        };
+        step(SMOOTH_INIT, 0);
+        TRMF_HIP_CHECK(hipGetLastError());
+        bool note_live = true;
+        for (int j = 0; j < max_iter; j++) {
+            step(SMOOTH_STEP, j);
+            TRMF_HIP_CHECK(hipGetLastError());
+            if (j < kSmoothLook) continue;
+            if (!note_live) {                                   // without the word: read the stop itself every kSmoothLook steps
+                if (j % kSmoothLook) continue;
+                int done = 0;
+                TRMF_HIP_CHECK(hipMemcpyAsync(&done, &state.p->done, sizeof(int), hipMemcpyDeviceToHost, stream));
+                TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+                if (done) break;
+                continue;
+            }
+            // wait until step j - kSmoothLook has been decided: the device is then still kSmoothLook steps behind the queue's end
+            const unsigned int need = (unsigned int)(j - kSmoothLook);
+            const double t_wait = now_s();
+            bool stopped = false;
+            for (unsigned int spins = 0;; spins++) {
+                const unsigned int v = __atomic_load_n(note, __ATOMIC_ACQUIRE);
+                if ((v >> 15) == seq) {
+                    if (v & 1u) { stopped = true; break; }
+                    if (((v >> 1) & 0x3fffu) >= need) break;
+                }
+                if ((spins & 1023u) == 1023u && now_s() - t_wait > 2.0) {
+                    // the word has not moved for 2 s (a loaded device): drain the queue and read it again instead of running ahead blind
+                    TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+                    const unsigned int w = __atomic_load_n(note, __ATOMIC_ACQUIRE);
+                    if ((w >> 15) != seq) note_live = false;        // the device never wrote it: pace by synchronising from here on
+                    stopped = (w >> 15) == seq && (w & 1u);
+                    break;
+                }
+                __builtin_ia32_pause();
+            }
+            if (stopped) break;
+        }
+        step(SMOOTH_LAST, max_iter);                             // the last step's r.z and its stop test (a no-op after a stop)
+        {
+            SmoothFinishArgs fa{W.p, sa.x, lag_set.p, theta.p, Wn.p, Wout ? flat.p : nullptr, objs.p, first_row, m, k, KP, NT, nlag};
+            hipLaunchKernelGGL(smooth_finish_kernel, rows4, dim3(256), 0, stream, fa);
+            AssimErrArgs ea{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr, H.p,
+                            W.p, Wn.p, 0, first_row, errs.p, first_row, m, n, KP, full ? 1 : 0};
+            hipLaunchKernelGGL(assim_err_kernel, dim3(m), dim3(256), 0, stream, ea);
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        int bad = kAssimNoBadRow;
+        SmoothState hst{};
+        std::vector<double> herr((size_t)2 * m), hobj((size_t)4 * m);
+        std::vector<real> hflat(Wout ? (size_t)m * k : 0);
+        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(&hst, state.p, sizeof(SmoothState), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, herr.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(hobj.data(), objs.p, hobj.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (Wout) TRMF_HIP_CHECK(hipMemcpyAsync(hflat.data(), flat.p, hflat.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (bad != kAssimNoBadRow) { res->bad_row = bad; return 0; }
+        // ---- commit ----
+        TRMF_HIP_CHECK(hipMemcpyAsync(W.p + (size_t)first_row * KP, Wn.p, (size_t)m * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        if (first_row < ad_rows) adapt_stale();                     // rows the series statistics absorbed have changed
+        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new W
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        res->rows = (uint64_t)m;
+        res->entries = full ? (uint64_t)m * (uint64_t)n : host_row_ptr[T] - host_row_ptr[first_row];
+        res->converged = hst.done ? 1 : 0;
+        res->iterations = hst.done ? hst.iters : max_iter;
+        const double rz_end = hst.rz[res->iterations & 1];
+        res->residual = hst.rz0 > 0 ? std::sqrt(std::max(rz_end, 0.0) / hst.rz0) : 0.0;
+        double w2[2] = {0, 0}, e2[2] = {0, 0};
+        for (int r = 0; r < m; r++) {                               // row order: the same sums on every rank and every call
+            res->sq_err_before += herr[2 * r]; res->sq_err_after += herr[2 * r + 1];
+            w2[0] += hobj[4 * r]; e2[0] += hobj[4 * r + 1]; w2[1] += hobj[4 * r + 2]; e2[1] += hobj[4 * r + 3];
+        }
+        res->objective_before = 0.5 * (res->sq_err_before + (double)lamI * w2[0] + (double)lamAR * e2[0]);
+        res->objective_after = 0.5 * (res->sq_err_after + (double)lamI * w2[1] + (double)lamAR * e2[1]);
+        if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
+        return 0;
+    }
     // ---- online loading updates (trmf_session_series_stats_init / _adapt_series; adapt_kernels.hpp) -----------------------------------
     // One pass for both calls (the caller has validated the rank, gamma and the state of the tables).  init: the tables over all
     // rows from zero, H untouched (the pass's solve is discarded with its flag).  Otherwise: the active generation scaled by gamma^m

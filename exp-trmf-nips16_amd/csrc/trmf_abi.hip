@@ -621,6 +621,54 @@ int32_t trmf_session_assimilate_robust(TrmfSession *s, int32_t first_row, double
     return 0;
 }
 
+// Fixed-interval smoother: like trmf_session_assimilate, every argument is checked on the calling thread before any rank's worker
+// runs; a bad pivot of a preconditioner block is found on the device by every rank alike and reported here.
+int32_t trmf_session_smooth(TrmfSession *s, int32_t first_row, double rtol, int32_t max_iter, TrmfSmoothSums *out, void *Wnew) {
+    if (!s) { set_error("null session"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (f->k > kMaxRank) {
+        set_error("smooth: online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
+        return kFail;
+    }
+    if (f->has_lag0) { set_error("smooth: the lag set contains lag 0 (a row would be its own prior)"); return kFail; }
+    if (first_row < f->midx || first_row > f->T) {
+        set_error("smooth: first_row " + std::to_string(first_row) + " outside [" + std::to_string(f->midx) + " (the largest lag), " +
+                  std::to_string(f->T) + " (rows)]");
+        return kFail;
+    }
+    const int cap = TrmfSessionImpl::smooth_max_rows();
+    if (f->T - first_row > cap) {
+        set_error("smooth: a window of " + std::to_string(f->T - first_row) + " rows is above the cap of " + std::to_string(cap) +
+                  " rows (the factors of every window row stay resident for the solve)");
+        return kFail;
+    }
+    if (!std::isfinite(rtol)) { set_error("smooth: rtol must be finite (<= 0: the default of the element type)"); return kFail; }
+    if (max_iter > kSmoothMaxIter) { set_error("smooth: max_iter " + std::to_string(max_iter) + " above " + std::to_string(kSmoothMaxIter)); return kFail; }
+    if (rtol <= 0) rtol = kSmoothDefaultRtol;
+    if (max_iter <= 0) max_iter = kSmoothDefaultMaxIter;
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    const bool grouped = HND(s)->group != nullptr;
+    std::vector<TrmfSessionImpl::SmoothResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
+    if (HND(s)->all([&](TrmfSessionImpl *t) {
+            const int slot = grouped ? t->comm->rank : 0;
+            return t->smooth(first_row, rtol, max_iter, &res[slot], slot == 0 ? (real *)Wnew : nullptr);
+        })) return kFail;
+    for (const auto &r : res)
+        if (r.bad_row >= 0) {
+            set_error("smooth: row " + std::to_string(r.bad_row) + ": a pivot of G + (lambdaI + lambdaAR) I is not positive and finite "
+                      "(lambdaI + lambdaAR == 0 and a rank-deficient row?); nothing was changed");
+            return kFail;
+        }
+    if (out) {
+        const auto &r = res[0];
+        out->rows = r.rows; out->entries = r.entries; out->iterations = r.iterations; out->converged = r.converged; out->residual = r.residual;
+        out->sq_err_before = r.sq_err_before; out->sq_err_after = r.sq_err_after;
+        out->objective_before = r.objective_before; out->objective_after = r.objective_after;
+    }
+    return 0;
+}
+
 // Online loading updates: the arguments and the state of the tables are checked on the calling thread before any rank's worker runs
 // (see trmf_session_set_heldout); a bad pivot or a pool without room is found by every rank alike and reported here.
 static int adapt_call(TrmfSession *s, bool init, double forget, TrmfAdaptSums *out, void *Hnew) {

@@ -167,7 +167,8 @@ class Model(object):
         return forecast_std(self.H, self.lag_set, self.lag_val, noise[0], noise[1], window, transform=self.transform)
 
     # ---- online update ----------------------------------------------------------------------------
-    def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0):
+    def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0,
+                   smooth_back=0, Yback=None):
         """A new ``Model`` grown by the ``Ynew.shape[0]`` timestamps of ``Ynew`` (raw values; a transform of this model is
         applied first): H, the lag weights and the rows this model has stay as they are, every new row of W is solved from its
         own observations and the AR prior of the rows before it (``trmf.online.filter_rows``; the host form of
@@ -177,12 +178,31 @@ class Model(object):
         With ``adapt`` the loadings follow (the host form of ``Session.update(adapt=True)``): this model must carry
         ``series_stats`` (``init_series_stats``); a copy of them absorbs the new rows of the filtered W (unweighted, also under
         ``robust_c``) and the new model's H is their ridge solution with ``lambdaI`` (``trmf.online.series_ridge`` as a recursion).
-        ``forget`` is fixed when the statistics are built: a different value here is refused."""
-        from .online import filter_rows, robust_filter_rows
+        ``forget`` is fixed when the statistics are built: a different value here is refused.
+        With ``smooth_back > 0`` the new rows and the ``smooth_back`` rows before them (clipped at the largest lag) are then
+        smoothed (``trmf.online.smooth_rows``; the host form of ``Session.update(smooth_back=)``): a model keeps no training
+        matrix, so ``Yback`` must hold the last ``smooth_back`` rows this model was trained on (raw values, like ``Ynew``).
+        Together with ``robust_c`` that is refused: the smoother weights every cell fully."""
+        from .online import filter_rows, robust_filter_rows, smooth_rows
+        smooth_back = int(smooth_back)
+        if smooth_back < 0:
+            raise ValueError('assimilate: smooth_back must not be negative, not {}'.format(smooth_back))
+        if smooth_back > 0:
+            if robust_c is not None:
+                raise ValueError('assimilate: smooth_back together with robust_c is refused: the smoother weights every cell fully and '
+                                 'would undo the Huber weights of the robust filter')
+            if adapt:
+                raise ValueError('assimilate: smooth_back together with adapt is refused: the rows before the block are the ones the series statistics have absorbed: smoothing them makes the statistics stale')
+            if Yback is None or Yback.shape != (smooth_back, self.n):
+                raise ValueError('assimilate: smooth_back needs Yback, the last {} rows of the training matrix ({} series)'.format(smooth_back, self.n))
+            if smat.issparse(Yback) != smat.issparse(Ynew):
+                raise ValueError('assimilate: Yback and Ynew must both be sparse or both be arrays')
         if self.transform is not None:
             if smat.issparse(Ynew):
                 raise ValueError('assimilate: a series transform needs dense rows')
             Ynew = self.transform.preprocess(np.asarray(Ynew)).astype(self.W.dtype)
+            if smooth_back > 0:
+                Yback = self.transform.preprocess(np.asarray(Yback)).astype(self.W.dtype)
         grown = np.zeros((self.m + Ynew.shape[0], self.k), dtype=self.W.dtype, order='C')
         grown[:self.m] = self.W
         weights = None
@@ -196,6 +216,11 @@ class Model(object):
                 scale = np.sqrt(np.asarray(noise[0], dtype=np.float64))
             grown, weights = robust_filter_rows(grown, self.H, self.lag_set, self.lag_val, Ynew, self.m, lambdaI, lambdaAR, missing,
                                                 scale, robust_c, robust_sweeps)
+        if smooth_back > 0:
+            first = max(self.m - smooth_back, int(self.lag_set.max()) if len(self.lag_set) else 0)
+            tail = Yback[smooth_back - (self.m - first):] if first < self.m else Yback[:0]
+            window = smat.vstack([smat.csr_matrix(tail), smat.csr_matrix(Ynew)]).tocsr() if smat.issparse(Ynew) else np.vstack([np.asarray(tail), np.asarray(Ynew)])
+            grown = smooth_rows(grown, self.H, self.lag_set, self.lag_val, window, first, lambdaI, lambdaAR, missing)
         out = Model.from_arrays(grown, self.H.copy(), self.lag_val.copy(), self.lag_set.copy(), transform=self.transform)
         stats = getattr(self, 'series_stats', None)
         if adapt:

@@ -9,7 +9,8 @@ in ascending order, is the minimiser of its own observations plus the AR prior f
     W[i]    = A_i^-1 (sum_{j in Omega_i} y_ij h_j + lambdaAR p_i)
 
 A filter, not a smoother: rows before ``first_row`` never see the new data.  ``filter_rows`` is the specification the device
-tests compare against and the host path of ``Model.assimilate``.  ``robust_filter_rows`` is the same filter with Huber weights
+tests compare against and the host path of ``Model.assimilate``.  ``smooth_rows`` is the smoother (``trmf_session_smooth``): the
+joint minimiser over a window of tail rows, which also counts the AR penalties of the later rows a row appears in.  ``robust_filter_rows`` is the same filter with Huber weights
 (``trmf_session_assimilate_robust``): a cell far outside its series' residual scale is down-weighted, and the weights are returned.
 """
 import numpy as np
@@ -164,6 +165,135 @@ def robust_filter_rows(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambda
         else:
             weights[r, cols] = om
     return out, weights
+
+
+# ---- the fixed-interval smoother: the window's rows as the joint minimiser (trmf_session_smooth) ---------------------------------
+def _window_guards(what, W, H, lag_set, Yrows, first_row):
+    """filter_rows' guards under another name: (T, k, lags as int64, reach, first_row)."""
+    T, k = W.shape
+    back = np.asarray(lag_set).astype(np.int64)
+    if back.size and back.min() == 0:
+        raise ValueError('{}: the lag set contains lag 0 (a row would be its own prior)'.format(what))
+    reach = int(back.max()) if back.size else 0
+    first_row = int(first_row)
+    if first_row < reach or first_row > T:
+        raise ValueError('{}: first_row {} outside [{} (the largest lag), {} (rows)]'.format(what, first_row, reach, T))
+    if Yrows.shape[0] != T - first_row or (T > first_row and Yrows.shape[1] != H.shape[0]):
+        raise ValueError('{}: Yrows is {}, rows {}..{} of {} series were expected'.format(what, Yrows.shape, first_row, T, H.shape[0]))
+    return T, k, back, reach, first_row
+
+
+def _row_observations(Yr, r, sparse, missing, n, dt):
+    """(columns, values) of row r of the window as filter_rows reads them."""
+    if sparse:
+        lo, hi = Yr.indptr[r], Yr.indptr[r + 1]
+        cols, y = Yr.indices[lo:hi], Yr.data[lo:hi].astype(dt)
+        if not missing:                                      # every series counts: absent entries read as 0
+            full = np.zeros(n, dtype=dt)
+            np.add.at(full, cols, y)
+            cols, y = slice(None), full
+        return cols, y
+    if missing:
+        cols = np.nonzero(Yr[r])[0]
+        return cols, Yr[r, cols].astype(dt)
+    return slice(None), Yr[r].astype(dt)
+
+
+def _ar_operator(back, theta, m):
+    """B as k banded m x m matrices (k, m, m): (B x)_i = x_i - sum_{l : i - lag_l >= 0} theta_l o x_{i - lag_l}, window indices."""
+    k = theta.shape[1]
+    B = np.zeros((k, m, m), dtype=theta.dtype)
+    idx = np.arange(m)
+    B[:, idx, idx] = 1
+    for l, lag in enumerate(back):
+        rows = idx[idx >= lag]
+        if rows.size:
+            B[:, rows, rows - lag] -= theta[l][:, None]
+    return B
+
+
+def smooth_rows(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, missing):
+    """A copy of ``W`` (T x k) whose rows ``first_row .. T-1`` are the JOINT minimiser of the training objective restricted to
+    them, with H, the lag weights and every earlier row fixed: the specification of ``trmf_session_smooth`` ::
+
+        J_win = 1/2 sum_{i>=f} sum_{j in Omega_i} (y_ij - w_i . h_j)^2 + 1/2 lambdaI sum_{i>=f} |w_i|^2 + 1/2 lambdaAR sum_{i>=f} |e_i|^2
+        e_i   = w_i - sum_l lag_val[l] * w_{i - lag_set[l]}                    (rows < f enter e_i as constants)
+
+    Where ``filter_rows`` fits a row to its own observations and the rows before it, this also counts the AR penalties of the
+    later rows in which the row appears.  The gradient is linear: with ``D`` the block diagonal of ``G_i + lambdaI I``, ``B`` the
+    banded AR operator of the window and ``h`` the head rows' share of ``e``, the rows solve ``(D + lambdaAR B^T B) x = b +
+    lambdaAR B^T h``; the system is assembled and solved directly by a (banded) Cholesky factorisation.  ``Yrows``, ``missing``,
+    the dtype rule and the guards are ``filter_rows``'; a row whose ``G_i + (lambdaI + lambdaAR) I`` is not positive definite is
+    refused by name as there (the device preconditions with these blocks)."""
+    W = np.asarray(W)
+    dt = W.dtype
+    T, k, back, reach, first_row = _window_guards('smooth_rows', W, H, lag_set, Yrows, first_row)
+    out = W.copy()
+    m = T - first_row
+    if m == 0:
+        return out
+    H = np.asarray(H, dtype=dt)
+    theta = np.asarray(lag_val, dtype=dt).reshape(len(back), k)
+    lamI, lamAR = dt.type(lambdaI), dt.type(lambdaAR)
+    sparse = smat.issparse(Yrows)
+    Yr = Yrows.tocsr() if sparse else np.asarray(Yrows)
+    eye = np.eye(k, dtype=dt)
+    A4 = np.zeros((m, k, m, k), dtype=dt)
+    rhs = np.zeros((m, k), dtype=dt)
+    head = np.zeros((m, k), dtype=dt)                        # the head rows' share of e: e = B x - head
+    for r in range(m):
+        i = first_row + r
+        cols, y = _row_observations(Yr, r, sparse, missing, H.shape[0], dt)
+        Hi = H[cols]
+        G = Hi.T.dot(Hi)
+        block = G + (lamI + lamAR) * eye
+        try:
+            if not np.all(np.isfinite(block)):
+                raise np.linalg.LinAlgError('not finite')
+            L = np.linalg.cholesky(block)
+            if not (np.all(np.isfinite(L)) and np.all(np.diagonal(L) > 0)):
+                raise np.linalg.LinAlgError('pivot')
+        except np.linalg.LinAlgError:
+            raise ValueError('smooth_rows: row {}: G + (lambdaI + lambdaAR) I is not positive definite'.format(i))
+        A4[r, :, r, :] = G + lamI * eye
+        rhs[r] = Hi.T.dot(y)
+        for l, lag in enumerate(back):
+            if r - lag < 0:
+                head[r] += theta[l] * W[i - lag]
+    B = _ar_operator(back, theta, m)
+    dims = np.arange(k)
+    A4[:, dims, :, dims] += lamAR * np.einsum('cji,cjl->cil', B, B)
+    rhs += lamAR * np.einsum('cji,jc->ic', B, head)
+    N = m * k
+    A = A4.reshape(N, N)
+    u = min(N - 1, reach * k + k - 1)                        # the half bandwidth in (row, dimension) order
+    ab = np.zeros((u + 1, N), dtype=dt)
+    for d in range(u + 1):
+        ab[u - d, d:] = np.diagonal(A, d)
+    try:
+        cb = scipy.linalg.cholesky_banded(ab, lower=False, check_finite=True)
+    except (np.linalg.LinAlgError, ValueError):
+        raise ValueError('smooth_rows: the system of rows {}..{} is not positive definite'.format(first_row, T))
+    out[first_row:] = scipy.linalg.cho_solve_banded((cb, False), rhs.reshape(N), check_finite=False).reshape(m, k)
+    return out
+
+
+def window_objective(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, missing):
+    """``J_win`` of ``smooth_rows`` for the rows of ``W`` as they are, in float64 (``objective_before`` / ``objective_after`` of
+    ``trmf_session_smooth``; canonical rows: no cell stored twice)."""
+    W = np.asarray(W, dtype=np.float64)
+    T, k, back, reach, first_row = _window_guards('window_objective', W, H, lag_set, Yrows, first_row)
+    H = np.asarray(H, dtype=np.float64)
+    theta = np.asarray(lag_val, dtype=np.float64).reshape(len(back), k)
+    sparse = smat.issparse(Yrows)
+    Yr = Yrows.tocsr() if sparse else np.asarray(Yrows)
+    fit = ridge = ar = 0.0
+    for i in range(first_row, T):
+        cols, y = _row_observations(Yr, i - first_row, sparse, missing, H.shape[0], np.dtype(np.float64))
+        res = y - H[cols].dot(W[i])
+        e = W[i] - np.sum(W[i - back] * theta, axis=0) if back.size else W[i]
+        fit += float(res.dot(res)); ridge += float(W[i].dot(W[i])); ar += float(e.dot(e))
+    return 0.5 * (fit + float(lambdaI) * ridge + float(lambdaAR) * ar)
 
 
 # ---- online loading updates: the rows of H refitted from new rows (trmf_session_series_stats_init / _adapt_series) ---------------

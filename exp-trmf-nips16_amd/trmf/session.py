@@ -63,6 +63,16 @@ class TrmfRobustSums(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TrmfSmoothSums(ctypes.Structure):
+    """Sums of a smoother call (include/trmf_abi.h): those of ``TrmfAssimilateSums``, the CG steps taken, whether the stop test held,
+    the relative preconditioned residual at the end and the window objective before / after."""
+    _fields_ = [('rows', c_uint64), ('entries', c_uint64), ('iterations', c_int32), ('converged', c_int32), ('residual', c_double),
+                ('sq_err_before', c_double), ('sq_err_after', c_double), ('objective_before', c_double), ('objective_after', c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class TrmfAdaptSums(ctypes.Structure):
     """Sums of an online loading update (include/trmf_abi.h): series refitted, rows and entries absorbed, the squared error of the
     absorbed entries with H as it was / as it is, the largest change of an element of H."""
@@ -162,6 +172,9 @@ def bind(lib):
     if hasattr(lib, 'trmf_session_assimilate_robust'):    # (absent from libraries built before the robust online updates)
         lib.trmf_session_assimilate_robust.argtypes = [c_void_p, c_int32, c_double, c_int32, c_void_p, POINTER(TrmfRobustSums), c_void_p, c_void_p]
         lib.trmf_session_assimilate_robust.restype = c_int32
+    if hasattr(lib, 'trmf_session_smooth'):           # (absent from libraries built before the smoother)
+        lib.trmf_session_smooth.argtypes = [c_void_p, c_int32, c_double, c_int32, POINTER(TrmfSmoothSums), c_void_p]
+        lib.trmf_session_smooth.restype = c_int32
     if hasattr(lib, 'trmf_session_adapt_series'):     # (absent from libraries built before the online loading updates)
         lib.trmf_session_series_stats_init.argtypes = [c_void_p, c_double]; lib.trmf_session_series_stats_init.restype = c_int32
         lib.trmf_session_adapt_series.argtypes = [c_void_p, POINTER(TrmfAdaptSums), c_void_p]; lib.trmf_session_adapt_series.restype = c_int32
@@ -338,6 +351,27 @@ class Session(object):
         out = (sums.as_dict(),) + ((Wnew,) if return_latent else ()) + ((weights,) if return_weights else ())
         return out if len(out) > 1 else out[0]
 
+    def smooth(self, first_row, rtol=None, max_iter=None, return_latent=False):
+        """Fixed-interval smoother on the device: rows ``first_row .. rows()-1`` of W become the JOINT minimiser of the training
+        objective restricted to them, with H, the lag weights and every earlier row fixed (``trmf.online.smooth_rows`` is the same
+        statement in NumPy, solved directly) -- what the X-solve would give for those rows if nothing else moved, by preconditioned
+        conjugate gradients over the window.  ``rtol``: the stop ``r.z <= rtol^2 (r.z)_0`` (default 1e-5 in float32, 2e-14 in
+        float64); ``max_iter`` (default 500): a call that reaches it still commits, with ``converged == 0``.  Returns ``{'rows',
+        'entries', 'iterations', 'converged', 'residual', 'sq_err_before', 'sq_err_after', 'objective_before', 'objective_after'}``,
+        or ``(sums, Wnew)`` with ``return_latent``.  A refused call (everything ``assimilate`` refuses, a window of more than 1024
+        rows, an ``rtol`` that is not finite) raises and leaves the session as it was."""
+        first_row = int(first_row)
+        sums = TrmfSmoothSums()
+        Wnew = None
+        if return_latent:
+            Wnew = np.empty((max(self.rows() - first_row, 0), self.model.k), dtype=self.model.W.dtype)
+        self._check(self.lib.trmf_session_smooth(self.handle, first_row, 0.0 if rtol is None else float(rtol), 0 if max_iter is None else int(max_iter),
+                                                 byref(sums), Wnew.ctypes.data if Wnew is not None and Wnew.size else None), 'trmf_session_smooth')
+        return (sums.as_dict(), Wnew) if return_latent else sums.as_dict()
+
+    def _reach(self):
+        return int(self.model.lag_set.max()) if len(self.model.lag_set) else 0
+
     def init_series_stats(self, forget=1.0):
         """Build the resident per-series statistics ``S_j``, ``r_j`` of ``adapt_series`` over all rows with W as it is, weighted by
         ``forget ** (rows() - 1 - t)`` (``forget`` in (0, 1]; 1: no forgetting).  One pass as heavy as an F-solve; H is not
@@ -365,14 +399,25 @@ class Session(object):
         self._check(self.lib.trmf_session_series_stats_info(self.handle, byref(v), byref(rows), byref(g)), 'trmf_session_series_stats_info')
         return {'valid': v.value == 1, 'stale': v.value == -1, 'absorbed_rows': int(rows.value), 'forget': float(g.value)}
 
-    def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0):
+    def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0, smooth_back=0):
         """Absorb the new timestamps ``Ynew`` (as for ``append_rows``): append them, assimilate the new block, run ``iters``
         ALS iterations if asked for.  ``self.model`` is replaced by a host model of ``rows()`` timestamps (H, lag weights, lag
         set and transform carried over; its arrays are filled by the next ``download()``).  Returns the sums of ``assimilate``;
         with ``robust_c`` the block is absorbed by ``assimilate_robust(before, robust_c, robust_sweeps, scale)`` and its sums
         are returned.  With ``adapt`` the loadings follow: the series statistics are initialised with ``forget`` before the
         append if the session has none (existing ones keep their own), ``adapt_series`` runs after the block has been assimilated
-        and ``(sums, adapt_sums)`` is returned."""
+        and ``(sums, adapt_sums)`` is returned.  With ``smooth_back > 0`` the block and the ``smooth_back`` rows before it are then
+        smoothed, ``smooth(before - smooth_back)`` clipped at the largest lag; its sums are returned as ``sums['smooth']``.  Together with ``robust_c`` that is refused: the smoother
+        weights every cell fully and would undo the Huber weights; so is ``adapt``: the rows before the block are the ones the
+        series statistics have absorbed."""
+        smooth_back = int(smooth_back)
+        if smooth_back < 0:
+            raise ValueError('update: smooth_back must not be negative, not {}'.format(smooth_back))
+        if smooth_back > 0 and robust_c is not None:
+            raise ValueError('update: smooth_back together with robust_c is refused: the smoother weights every cell fully and would '
+                             'undo the Huber weights of the robust filter')
+        if smooth_back > 0 and adapt:
+            raise ValueError('update: smooth_back together with adapt is refused: the rows before the block are the ones the series statistics have absorbed: smoothing them makes the statistics stale')
         before = self.rows()
         if adapt:
             info = self.series_stats_info()
@@ -387,6 +432,8 @@ class Session(object):
         grown[:min(before, old.m)] = old.W[:before]
         self.model = type(old).from_arrays(grown, old.H.copy(), old.lag_val.copy(), old.lag_set.copy(), transform=old.transform)
         sums = self.assimilate(before) if robust_c is None else self.assimilate_robust(before, robust_c, robust_sweeps, scale)
+        if smooth_back > 0:
+            sums['smooth'] = self.smooth(max(before - smooth_back, self._reach()))
         adapted = self.adapt_series() if adapt else None
         if iters:
             self.run(int(iters))

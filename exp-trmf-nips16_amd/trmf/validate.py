@@ -35,7 +35,7 @@ def _as_training_matrix(block, missing):
     return smat.csr_matrix(block) if missing else block
 
 
-def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag=None, assimilate=False, robust=None, adapt=None):
+def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag=None, assimilate=False, robust=None, adapt=None, smooth_back=0):
     """Yield the trained model of every window from one resident session.  With a transform (dense Y, full
     observation) the session holds the RAW matrix and applies each window's refitted coefficients on the device."""
     from .session import Session
@@ -50,7 +50,7 @@ def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing,
             _ensure_noise(sess)
         for prev_cut, cut in zip(cuts[:-1], cuts[1:]):
             if assimilate:      # online: the new rows are filtered in, nothing is retrained
-                sess.update(_as_training_matrix(Y[prev_cut:cut], missing), **dict(robust or {}, **(adapt or {})))
+                sess.update(_as_training_matrix(Y[prev_cut:cut], missing), **dict(robust or {}, **dict(adapt or {}, **({'smooth_back': smooth_back} if smooth_back else {}))))
                 yield sess.download()
                 continue
             # host-side model of the new size: same warm start the device applies, same RNG consumption as the
@@ -73,7 +73,7 @@ def _ensure_noise(sess):
 
 
 def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag=None,
-                             assimilate=False, interval_level=None, robust=None, adapt=None):
+                             assimilate=False, interval_level=None, robust=None, adapt=None, smooth_back=0):
     """The whole rolling evaluation from one resident session: every window is trained, forecast and scored on the device
     (``Session.forecast`` with the window's truth), the next window's rows are appended and, if asked for, a transform
     refitted on the grown prefix is handed over.  No factor is downloaded and no host model is rebuilt between windows.  With an
@@ -95,6 +95,8 @@ def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_
                     sess.assimilate(cuts[i - 1])
                 else:
                     sess.assimilate_robust(cuts[i - 1], robust['robust_c'], robust['robust_sweeps'])
+                if smooth_back:           # ... the block and the rows before it smoothed
+                    sess.smooth(max(cuts[i - 1] - smooth_back, max(lag_set)))
                 if adapt is not None:     # ... and the loadings follow
                     sess.adapt_series()
             else:
@@ -127,7 +129,7 @@ def _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, tr
 def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5, lambdaAR=50, lambdaLag=0.5,
                      max_iter=20, missing=True, threshold=0, transform=None, threads=16, verbose=0, seed=0,
                      resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False, update='retrain', interval_level=None,
-                     robust_c=None, robust_sweeps=4, adapt_series=False, forget=1.0):
+                     robust_c=None, robust_sweeps=4, adapt_series=False, forget=1.0, smooth_back=0):
     """``interval_level`` (e.g. 0.9; needs ``forecast_on_device=True``): every window also fits the noise of its trained model and
     scores the predictive distribution of its forecast on the device; the result is ``(Metrics, IntervalMetrics)``, the ``Metrics``
     being exactly those of the call without it.
@@ -140,6 +142,9 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
     ``adapt_series`` (with ``update='assimilate'`` only): after every absorbed window the loadings H are refitted from the
     resident series statistics (``Session.adapt_series``; initialised after window 0 with ``forget``), so that H follows the
     data as well; the default leaves H as window 0 trained it.
+    ``smooth_back`` (with ``update='assimilate'`` only, not with ``robust_c``): after every absorbed window the block and the
+    ``smooth_back`` rows before it become the joint minimiser of the objective over that window (``Session.smooth``), so that the rows
+    a forecast starts from also count the rows after them; 0 leaves the filter's rows.
     ``lambdaLagL1`` / ``lag_refit``: sparse lag weights (``Session.set_lag_penalty``) on every path.
     ``forecast_on_device=True`` keeps the forecasts and their scoring on the device as well (one session, no download and no
     host model per window); it needs the resident path and a dense ``Y``, and says so where that does not hold."""
@@ -166,6 +171,16 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
         if not (0.0 < float(forget) <= 1.0):
             raise ValueError('adapt_series: forget must lie in (0, 1], not {!r}'.format(forget))
         adapt = dict(adapt=True, forget=float(forget))
+    smooth_back = int(smooth_back)
+    if smooth_back < 0:
+        raise ValueError('smooth_back must not be negative, not {}'.format(smooth_back))
+    if smooth_back > 0:
+        if not online:
+            raise ValueError("smooth_back: the smoother revisits rows absorbed online (update='assimilate'); retraining solves them jointly anyway")
+        if robust is not None:
+            raise ValueError('smooth_back together with robust_c is refused: the smoother weights every cell fully and would undo the Huber weights')
+        if adapt is not None:
+            raise ValueError('smooth_back together with adapt_series is refused: the rows before the block are the ones the series statistics have absorbed: smoothing them makes the statistics stale')
     if online:
         if transform is not None:
             raise ValueError("update='assimilate': a per-window transform rescales the whole history, which an online update does not revisit")
@@ -187,10 +202,10 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
             raise ValueError('forecast_on_device: a transform with missing=True is refitted on the host per window; '
                              'the device applies one only to dense full-observation training (missing=False)')
         return _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_iter, missing, threshold, transform, verbose, lag, online,
-                                        interval_level, robust, adapt)
+                                        interval_level, robust, adapt, smooth_back)
     # resident: a NumPy Y, and a transform only where the device can apply it (dense full-observation training)
     if resident and isinstance(Y, np.ndarray) and (transform is None or (not missing and Y.dtype in (np.float32, np.float64))):
-        models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag, online, robust, adapt)
+        models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag, online, robust, adapt, smooth_back)
     else:
         models = _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, threads, verbose, lag)
     forecasts = np.zeros((horizon, n), dtype=Y.dtype, order='C')

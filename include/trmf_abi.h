@@ -433,6 +433,55 @@ TRMF_API int32_t trmf_session_series_stats_init(TrmfSession *s, double forget);
 TRMF_API int32_t trmf_session_adapt_series(TrmfSession *s, TrmfAdaptSums *out /* or NULL */, void *Hnew /* or NULL: n x k, row-major */);
 TRMF_API int32_t trmf_session_series_stats_info(TrmfSession *s, int32_t *valid, int32_t *absorbed_rows, double *forget);
 
+/* --- fixed-interval smoother of the online rows: windowed preconditioned conjugate gradients -----------------------------
+ * The filters above fit row i to its own observations and the AR prior of the rows BEFORE it; the AR penalties of the later rows
+ * i + lag_l, in which w_i appears as well, are ignored, so the tail rows every forecast starts from are not the minimiser of the
+ * model's own objective.  The smoother is: with f = first_row, m = rows - f, and W[0..f), H, the lag weights Theta, the lag set
+ * and the session's current lambdaI, lambdaAR fixed, the rows f .. rows - 1 become the minimiser of the training objective
+ * restricted to them,
+ *   J_win = 1/2 sum_{i>=f} sum_{j in Omega_i} (y_ij - w_i . h_j)^2 + 1/2 lambdaI sum_{i>=f} |w_i|^2 + 1/2 lambdaAR sum_{i>=f} |e_i|^2
+ *   e_i   = w_i - sum_l Theta(l, .) o w_{i - lag_l}                                   (rows < f enter e_i as constants)
+ * with Omega_i and y exactly as for trmf_session_assimilate (missing or not, sparse or dense, the transformed value under an active
+ * series transform).  It is what the X-solve would give for those rows if nothing else moved, at a cost of O(window).  The gradient
+ *   g_i = (G_i + lambdaI I) w_i - b_i + lambdaAR (e_i - sum_{l : i + lag_l < rows} Theta(l, .) o e_{i + lag_l})
+ * is linear in the rows: one SPD system of order m k.  m == 1 is the filter's row; with every lag >= m it is the filter on every
+ * row; always J_win(smoothed) <= J_win(filtered).
+ *
+ * Order of operations: G_i, b_i by the X phase's builders; the Cholesky factors U_i of A_i = G_i + (lambdaI + lambdaAR) I for the
+ * whole window (the filter's blocks: the block-Jacobi preconditioner); preconditioned conjugate gradients in the element type on
+ * the correction to the rows as they stand: r = -g(W), z_i = U_i^-1 U_i^-T r_i, p = z, then per step q = A p (zero head rows),
+ * alpha = (r.z) / (p.q), x += alpha p, r -= alpha q, z, beta = (r.z)_new / (r.z)_old, p = z + beta p.  The dot products are summed
+ * per row in the element type and across rows in fp64, every sum in a fixed order.  The step stops when r.z <= rtol^2 (r.z)_0 or
+ * after max_iter steps.  The first time the stop test holds, one step is spent on replacing the recursively updated residual by
+ * the true one, r = b - A x from the rows as they then are (it counts in `iterations`), and the iteration goes on from p = z for
+ * at least one more step before the test is taken again.  This removes the error a start far from the minimiser leaves in the
+ * first residual; it is done once per call.  A call that reaches max_iter still commits (converged = 0): every CG iterate lowers J_win.
+ *   rtol      <= 0: the default, 1e-5 in the float library (~ 84 eps), 2e-14 in the double library (~ 90 eps)
+ *   max_iter  <= 0: the default, 500 (at most 16383)
+ * The window may hold at most 1024 rows (the factors of all its rows stay resident for the solve: m k^2 reals).
+ *
+ * Blocking, ordered after every run() enqueued before; every rank computes the same rows on its own copy (no exchange) and ends
+ * up with the same bits; repeated calls from the same state give the same bits (no floating-point atomics, fixed summation
+ * orders).  The iteration counter, the statistics, the mark, the forecast and interval scores, the noise tables and the measured
+ * multi-rank decisions are untouched.  The series statistics of trmf_session_adapt_series go stale when first_row lies below the
+ * rows they absorbed (the rule of trmf_session_assimilate).
+ *   out    NULL, or: rows, entries, sq_err_before / sq_err_after as in TrmfAssimilateSums; iterations = CG steps taken;
+ *          converged = 1 when the stop test held, 0 when max_iter was reached; residual = sqrt((r.z) / (r.z)_0) at the end;
+ *          objective_before / objective_after = J_win with the rows as they were / as they are, in fp64 and a fixed order
+ *   Wnew   NULL, or (rows - first_row) x k reals, row-major: the new rows
+ * 0 (first_row == rows: nothing to do, zero sums), or -1 with trmf_last_error() and W, the outputs and the session as they were:
+ * everything trmf_session_assimilate refuses (the message names the first row whose A_i has a bad pivot); a window of more than
+ * 1024 rows; an rtol that is not finite; max_iter above 16383; a device failure. */
+typedef struct {
+    uint64_t rows, entries;
+    int32_t  iterations, converged;        /* converged = 0: max_iter reached */
+    double   residual;                     /* sqrt((r.z) / (r.z)_0) at the end */
+    double   sq_err_before, sq_err_after;  /* as TrmfAssimilateSums */
+    double   objective_before, objective_after;   /* J_win, fp64, fixed order */
+} TrmfSmoothSums;
+TRMF_API int32_t trmf_session_smooth(TrmfSession *s, int32_t first_row, double rtol, int32_t max_iter,
+                                     TrmfSmoothSums *out /* or NULL */, void *Wnew /* or NULL: (rows - first_row) x k */);
+
 /* --- forecast uncertainty: noise fit, predictive standard deviation and interval scores ---------------------------------
  * TRMF read as a linear-Gaussian state-space model (the paper's own reading): y_ij = w_i . h_j + eps_ij with eps_ij ~ N(0, sigma_j^2),
  * every latent dimension t an AR process with innovation variance q_t.  With m the largest lag and T = trmf_session_rows():
