@@ -19,12 +19,13 @@
 //   unit_uncertainty.hip  noise_resid_kernel (5), forecast_dist_kernel (5), the noise / psi kernels: trmf_session_fit_noise, _forecast_dist
 //   unit_adapt.hip     adapt_series_kernel (4), adapt_part_kernel (4), the full-observation forms: trmf_session_adapt_series
 //   unit_smooth.hip    smooth_ar_kernel, smooth_apply_kernel, smooth_update_kernel, smooth_finish_kernel: the windowed PCG of trmf_session_smooth
+//   unit_smooth_robust.hip  smooth_robust_part_kernel (4), smooth_robust_fold_kernel (4): the weighted Grams of trmf_session_smooth_robust
 //
 // A unit defines TRMF_UNIT before including this file; the non-template kernels of the shared headers are compiled by the main
 // unit only (#if !defined(TRMF_UNIT) around them).
 #pragma once
 
-// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online, 10 online loadings, 11 smoother; the kernels of these families
+// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online, 10 online loadings, 11 smoother, 12 robust smoother; the kernels of these families
 // have their BODIES only where TRMF_UNIT_BODIES is defined -- the main unit sees declarations, so that it neither compiles them
 // nor runs them through the optimiser as `extern template` would (available_externally bodies: 3 of its 3.5 minutes))
 #if defined(TRMF_UNIT) || defined(TRMF_SINGLE_UNIT)
@@ -61,6 +62,9 @@
 #endif
 #if !defined(TRMF_UNIT) || TRMF_UNIT == 11
 #include "smooth_kernels.hpp"
+#endif
+#if !defined(TRMF_UNIT) || TRMF_UNIT == 12
+#include "smooth_robust_kernels.hpp"
 #endif
 #if !defined(TRMF_UNIT)
 #include "cg_persist_args.hpp"     // the declaration only: the body is unit_persist.hip's business
@@ -184,6 +188,13 @@ namespace trmf {
     X void adapt_series_kernel<3>(AdaptArgs); X void adapt_series_kernel<4>(AdaptArgs);                                      \
     X void adapt_part_kernel<1>(AdaptArgs); X void adapt_part_kernel<2>(AdaptArgs);                                          \
     X void adapt_part_kernel<3>(AdaptArgs); X void adapt_part_kernel<4>(AdaptArgs);
+
+// robust smoother (smooth_robust_kernels.hpp): the part and the fold kernel as NT = 1..4 (k <= 64)
+#define TRMF_UNIT_SMOOTH_ROBUST(X)                                                                                           \
+    X void smooth_robust_part_kernel<1>(SmoothRobustArgs); X void smooth_robust_part_kernel<2>(SmoothRobustArgs);            \
+    X void smooth_robust_part_kernel<3>(SmoothRobustArgs); X void smooth_robust_part_kernel<4>(SmoothRobustArgs);            \
+    X void smooth_robust_fold_kernel<1>(SmoothRobustArgs); X void smooth_robust_fold_kernel<2>(SmoothRobustArgs);            \
+    X void smooth_robust_fold_kernel<3>(SmoothRobustArgs); X void smooth_robust_fold_kernel<4>(SmoothRobustArgs);
 
 #define TRMF_DEFINE_KERNEL template __global__
 

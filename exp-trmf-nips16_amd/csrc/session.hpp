@@ -1398,47 +1398,14 @@ struct TrmfSessionImpl : SessionXPhase {
     }
     static constexpr int kSmoothLook = 4;
     unsigned int smooth_seq = 0;
-    int smooth(int first_row, double rtol, int max_iter, SmoothResult *res, real *Wout) {
-        *res = SmoothResult{};
-        if (sync()) return kFail;
-        const int m = T - first_row;
-        if (m <= 0) return 0;
-        if (ensure_cg_note()) { set_error("smooth: no pinned host memory for the word the stop is followed through"); return kFail; }
+    // The PCG of one system: INIT, the steps with the pinned-word pacing described above, and the closing stop test.  `sa` carries
+    // the system (W, x0, Bv, G, U), the vectors and a zeroed SmoothState of this solve's own; the word and its sequence number are set here.
+    int smooth_pcg(SmoothArgs &sa, int max_iter) {
+        const int m = sa.m;
         unsigned int *note = cg_note + 8;                       // a word of its own in the X-solve's pinned line
-        FillStreamScope fill(stream);
-        DevBuf<real> Wn, flat, U, vec, part;
-        DevBuf<int> flag;
-        DevBuf<double> errs, objs;
-        DevBuf<SmoothState> state;
-        SyncStreamOnExit drain(stream);
-        const size_t V = (size_t)m * 64;
-        if (Wn.alloc((size_t)m * KP) || (Wout && flat.alloc((size_t)m * k, false)) || U.alloc((size_t)m * k * k, false) || vec.alloc(7 * V) ||
-            part.alloc((size_t)2 * m) || flag.alloc(1, false) || errs.alloc((size_t)2 * m, false) || objs.alloc((size_t)4 * m, false) || state.alloc(1))
-            return kFail;
-        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
-        // stage A
-        if (full) {
-            if (y_times_factor(false, H.p, Bv.p, dense ? 0u : (uint32_t)first_row, (uint32_t)T)) return kFail;        // rows of Y H
-            if (small_gram(H.p, n, real(0), GSx.p, stream)) return kFail;                                             // H^T H
-        } else if (launch_gram_x_rows((uint32_t)first_row, (uint32_t)T)) return kFail;
-        TRMF_HIP_CHECK(hipGetLastError());
-        const real lamAR = (real)lambdaAR, lamI = (real)lambdaI;
-        {
-            AssimFactorArgs fa{Gmat(), full ? (size_t)0 : xp.gstride, gpacked ? 1 : 0, U.p, flag.p, lamI + lamAR, first_row, m, k};
-            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3((m + 3) / 4), dim3(256), 0, stream, fa); }))
-                return unsupported_rank();
-            TRMF_HIP_CHECK(hipGetLastError());
-        }
-        // stage B
         const unsigned int seq = ++smooth_seq & 0x1ffffu;
         __atomic_store_n(note, 0u, __ATOMIC_RELEASE);
-        SmoothArgs sa{};
-        sa.W = W.p; sa.Bv = Bv.p; sa.G = Gmat(); sa.gstride = full ? (size_t)0 : xp.gstride; sa.packed = gpacked ? 1 : 0; sa.U = U.p;
-        sa.lag_set = lag_set.p; sa.theta = theta.p;
-        sa.x = vec.p; sa.r = vec.p + V; sa.z = vec.p + 2 * V; sa.q = vec.p + 3 * V; sa.e = vec.p + 4 * V; sa.p[0] = vec.p + 5 * V; sa.p[1] = vec.p + 6 * V;
-        sa.part_rz = part.p; sa.part_pq = part.p + m; sa.st = state.p; sa.flag = flag.p; sa.note = note; sa.note_seq = seq;
-        sa.tol2 = rtol * rtol; sa.lamI = lamI; sa.lamAR = lamAR;
-        sa.first_row = first_row; sa.m = m; sa.k = k; sa.KP = KP; sa.NT = NT; sa.nlag = nlag;
+        sa.note = note; sa.note_seq = seq;
         sa.lds_theta = smooth_theta_lds_bytes(nlag) <= kLdsDefault && !test_env("TRMF_FORECAST_GLOBAL") ? 1 : 0;
         const size_t lds_th = sa.lds_theta ? smooth_theta_lds_bytes(nlag) : 0, lds_up = smooth_update_lds_bytes(k);
         const dim3 rows4((m + 3) / 4);
@@ -1458,7 +1425,7 @@ struct TrmfSessionImpl : SessionXPhase {
             if (!note_live) {                                   // without the word: read the stop itself every kSmoothLook steps
                 if (j % kSmoothLook) continue;
                 int done = 0;
-                TRMF_HIP_CHECK(hipMemcpyAsync(&done, &state.p->done, sizeof(int), hipMemcpyDeviceToHost, stream));
+                TRMF_HIP_CHECK(hipMemcpyAsync(&done, &sa.st->done, sizeof(int), hipMemcpyDeviceToHost, stream));
                 TRMF_HIP_CHECK(hipStreamSynchronize(stream));
                 if (done) break;
                 continue;
@@ -1486,6 +1453,49 @@ struct TrmfSessionImpl : SessionXPhase {
             if (stopped) break;
         }
         step(SMOOTH_LAST, max_iter);                             // the last step's r.z and its stop test (a no-op after a stop)
+        return 0;
+    }
+    int smooth(int first_row, double rtol, int max_iter, SmoothResult *res, real *Wout) {
+        *res = SmoothResult{};
+        if (sync()) return kFail;
+        const int m = T - first_row;
+        if (m <= 0) return 0;
+        if (ensure_cg_note()) { set_error("smooth: no pinned host memory for the word the stop is followed through"); return kFail; }
+        FillStreamScope fill(stream);
+        DevBuf<real> Wn, flat, U, vec, part;
+        DevBuf<int> flag;
+        DevBuf<double> errs, objs;
+        DevBuf<SmoothState> state;
+        SyncStreamOnExit drain(stream);
+        const size_t V = (size_t)m * 64;
+        if (Wn.alloc((size_t)m * KP) || (Wout && flat.alloc((size_t)m * k, false)) || U.alloc((size_t)m * k * k, false) || vec.alloc(7 * V) ||
+            part.alloc((size_t)2 * m) || flag.alloc(1, false) || errs.alloc((size_t)2 * m, false) || objs.alloc((size_t)4 * m, false) || state.alloc(1))
+            return kFail;
+        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
+        // stage A
+        if (full) {
+            if (y_times_factor(false, H.p, Bv.p, dense ? 0u : (uint32_t)first_row, (uint32_t)T)) return kFail;        // rows of Y H
+            if (small_gram(H.p, n, real(0), GSx.p, stream)) return kFail;                                             // H^T H
+        } else if (launch_gram_x_rows((uint32_t)first_row, (uint32_t)T)) return kFail;
+        TRMF_HIP_CHECK(hipGetLastError());
+        const real lamAR = (real)lambdaAR, lamI = (real)lambdaI;
+        {
+            AssimFactorArgs fa{Gmat(), full ? (size_t)0 : xp.gstride, gpacked ? 1 : 0, U.p, flag.p, lamI + lamAR, first_row, m, k};
+            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3((m + 3) / 4), dim3(256), 0, stream, fa); }))
+                return unsupported_rank();
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        // stage B
+        SmoothArgs sa{};
+        sa.W = W.p; sa.x0 = W.p + (size_t)first_row * KP; sa.Bv = Bv.p; sa.G = Gmat(); sa.gstride = full ? (size_t)0 : xp.gstride; sa.packed = gpacked ? 1 : 0;
+        sa.grow = first_row; sa.U = U.p;
+        sa.lag_set = lag_set.p; sa.theta = theta.p;
+        sa.x = vec.p; sa.r = vec.p + V; sa.z = vec.p + 2 * V; sa.q = vec.p + 3 * V; sa.e = vec.p + 4 * V; sa.p[0] = vec.p + 5 * V; sa.p[1] = vec.p + 6 * V;
+        sa.part_rz = part.p; sa.part_pq = part.p + m; sa.st = state.p; sa.flag = flag.p;
+        sa.tol2 = rtol * rtol; sa.lamI = lamI; sa.lamAR = lamAR;
+        sa.first_row = first_row; sa.m = m; sa.k = k; sa.KP = KP; sa.NT = NT; sa.nlag = nlag;
+        if (smooth_pcg(sa, max_iter)) return kFail;
+        const dim3 rows4((m + 3) / 4);
         {
             SmoothFinishArgs fa{W.p, sa.x, lag_set.p, theta.p, Wn.p, Wout ? flat.p : nullptr, objs.p, first_row, m, k, KP, NT, nlag};
             hipLaunchKernelGGL(smooth_finish_kernel, rows4, dim3(256), 0, stream, fa);
@@ -1524,6 +1534,140 @@ struct TrmfSessionImpl : SessionXPhase {
         res->objective_before = 0.5 * (res->sq_err_before + (double)lamI * w2[0] + (double)lamAR * e2[0]);
         res->objective_after = 0.5 * (res->sq_err_after + (double)lamI * w2[1] + (double)lamAR * e2[1]);
         if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
+        return 0;
+    }
+    // ---- the robust fixed-interval smoother (trmf_session_smooth_robust; smooth_robust_kernels.hpp) -----------------------------------
+    // smooth() on the Huber form of the objective by `sweeps` rounds of reweighting (the caller has validated what smooth() and
+    // assimilate_robust() ask for; the n scales arrive as host values on every rank).  Per sweep: one part launch over the items of
+    // the whole window and one fold launch build the weighted G_i, b_i in scratch of this call's own (the session's G / Bv cache is
+    // not touched), assim_factor_kernel factors the blocks, smooth_pcg() solves from the rows of the sweep before, and
+    // smooth_finish_kernel lays the rows out for the next sweep's part kernel.  Two more part launches in score-only mode give
+    // J_rob's data term before and after.  The host synchronises only where smooth_pcg() follows its word; W changes by ONE device
+    // copy after the flag and the sums have been read.  A sweep that reaches max_iter is kept (converged = 0): every CG iterate
+    // lowers the sweep's majoriser of J_rob.
+    struct RobustSmoothResult {
+        uint64_t rows = 0, entries = 0, downweighted = 0;
+        int sweeps = 0, iterations = 0, converged = 0;
+        double residual = 0, weight_sum = 0, sq_err_before = 0, sq_err_after = 0, objective_before = 0, objective_after = 0;
+        int bad_row = -1;
+    };
+    int smooth_robust(int first_row, double c, int sweeps, const double *scale, double rtol, int max_iter, RobustSmoothResult *res, real *Wout,
+                      real *weights_out) {
+        *res = RobustSmoothResult{};
+        if (sync()) return kFail;
+        const int m = T - first_row;
+        if (m <= 0) return 0;
+        if (ensure_cg_note()) { set_error("smooth_robust: no pinned host memory for the word the stop is followed through"); return kFail; }
+        FillStreamScope fill(stream);
+        int slice = kSmoothRobustSlice;
+        if (const char *e = test_env("TRMF_SMOOTH_ROBUST_SLICE")) slice = std::max(1, atoi(e));      // tests: several items per row on a small shape
+        const uint64_t nw = dense ? (uint64_t)m * (uint64_t)n : host_row_ptr[T] - host_row_ptr[first_row];
+        // the items: a row's entries in spans that depend on its length only
+        std::vector<uint32_t> hitems, hrow((size_t)m + 1);
+        for (int r = 0; r < m; r++) {
+            hrow[r] = (uint32_t)(hitems.size() / 3);
+            const uint64_t e0 = dense ? 0 : host_row_ptr[first_row + r], e1 = dense ? (uint64_t)n : host_row_ptr[first_row + r + 1];
+            const uint64_t span = smooth_robust_span(e1 - e0, slice);
+            for (uint64_t b = e0; b < e1; b += span) {
+                hitems.push_back((uint32_t)r); hitems.push_back((uint32_t)b); hitems.push_back((uint32_t)std::min(b + span, e1));
+            }
+        }
+        const uint32_t nitems = (uint32_t)(hitems.size() / 3);
+        hrow[m] = nitems;
+        if (hitems.empty()) hitems.assign(3, 0u);
+        std::vector<real> hthr((size_t)n);
+        for (int j = 0; j < n; j++) hthr[j] = (real)c * (real)scale[j];
+        DevBuf<real> xc, flat, U, vec, part, thr, wts, slab, Gs, bs;
+        DevBuf<uint32_t> d_items, d_row;
+        DevBuf<int> flag;
+        DevBuf<double> objs, slab_d, score, rowsum;
+        DevBuf<SmoothState> state;
+        SyncStreamOnExit drain(stream);
+        const size_t V = (size_t)m * 64, ni = std::max<size_t>(nitems, 1);
+        if (xc.alloc((size_t)m * KP, false) || (Wout && flat.alloc((size_t)m * k, false)) || U.alloc((size_t)m * k * k, false) || vec.alloc(7 * V) ||
+            part.alloc((size_t)2 * m) || thr.upload(hthr.data(), n) || wts.alloc(std::max<uint64_t>(nw, 1), false) ||
+            slab.alloc(ni * smooth_robust_slot_reals(KP), false) || Gs.alloc((size_t)m * k * k, false) || bs.alloc((size_t)m * KP, false) ||
+            d_items.upload(hitems.data(), hitems.size()) || d_row.upload(hrow.data(), hrow.size()) || flag.alloc(1, false) ||
+            objs.alloc((size_t)4 * m, false) || slab_d.alloc(ni * kSmoothRobustSlotD, false) || score.alloc(2 * ni * kSmoothRobustSlotD, false) ||
+            rowsum.alloc((size_t)2 * m, false) || state.alloc((size_t)sweeps)) return kFail;
+        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(xc.p, W.p + (size_t)first_row * KP, (size_t)m * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        const real lamAR = (real)lambdaAR, lamI = (real)lambdaI;
+        SmoothRobustArgs ra{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr, H.p, xc.p, thr.p,
+                            wts.p, d_items.p, d_row.p, slab.p, slab_d.p, Gs.p, bs.p, rowsum.p, first_row, m, n, k, KP, 0};
+        auto part_launch = [&](int score_only, double *sums) {
+            if (!nitems) return true;
+            SmoothRobustArgs a = ra;
+            a.score = score_only; a.slab_d = sums;
+            return with_nt(NT, [&](auto N) { hipLaunchKernelGGL(smooth_robust_part_kernel<decltype(N)::value>, dim3(nitems), dim3(256), 0, stream, a); });
+        };
+        if (!part_launch(1, score.p)) return unsupported_rank();
+        SmoothArgs sa{};
+        sa.W = W.p; sa.x0 = xc.p; sa.Bv = bs.p; sa.G = Gs.p; sa.gstride = (size_t)k * k; sa.packed = 0; sa.grow = 0; sa.U = U.p;
+        sa.lag_set = lag_set.p; sa.theta = theta.p;
+        sa.x = vec.p; sa.r = vec.p + V; sa.z = vec.p + 2 * V; sa.q = vec.p + 3 * V; sa.e = vec.p + 4 * V; sa.p[0] = vec.p + 5 * V; sa.p[1] = vec.p + 6 * V;
+        sa.part_rz = part.p; sa.part_pq = part.p + m; sa.flag = flag.p;
+        sa.tol2 = rtol * rtol; sa.lamI = lamI; sa.lamAR = lamAR;
+        sa.first_row = first_row; sa.m = m; sa.k = k; sa.KP = KP; sa.NT = NT; sa.nlag = nlag;
+        const dim3 rows4((m + 3) / 4);
+        for (int s = 0; s < sweeps; s++) {
+            if (!part_launch(0, slab_d.p)) return unsupported_rank();
+            AssimFactorArgs fa{Gs.p, (size_t)k * k, 0, U.p, flag.p, lamI + lamAR, 0, m, k};
+            if (!with_nt(NT, [&](auto N) {
+                    hipLaunchKernelGGL(smooth_robust_fold_kernel<decltype(N)::value>, dim3(m), dim3(256), 0, stream, ra);
+                    hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3((m + 3) / 4), dim3(256), 0, stream, fa);
+                })) return unsupported_rank();
+            TRMF_HIP_CHECK(hipGetLastError());
+            sa.st = state.p + s;
+            if (smooth_pcg(sa, max_iter)) return kFail;
+            SmoothFinishArgs fin{W.p, sa.x, lag_set.p, theta.p, xc.p, Wout && s == sweeps - 1 ? flat.p : nullptr, objs.p, first_row, m, k, KP, NT, nlag};
+            hipLaunchKernelGGL(smooth_finish_kernel, rows4, dim3(256), 0, stream, fin);
+            TRMF_HIP_CHECK(hipGetLastError());
+        }
+        if (!part_launch(1, score.p + ni * kSmoothRobustSlotD)) return unsupported_rank();
+        TRMF_HIP_CHECK(hipGetLastError());
+        int bad = kAssimNoBadRow;
+        std::vector<SmoothState> hst((size_t)sweeps);
+        std::vector<double> hobj((size_t)4 * m), hsum((size_t)2 * m), hscore(2 * ni * kSmoothRobustSlotD, 0.0);
+        std::vector<real> hflat(Wout ? (size_t)m * k : 0), hwts(weights_out ? (size_t)nw : 0);
+        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(hst.data(), state.p, hst.size() * sizeof(SmoothState), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(hobj.data(), objs.p, hobj.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(hsum.data(), rowsum.p, hsum.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (nitems) TRMF_HIP_CHECK(hipMemcpyAsync(hscore.data(), score.p, hscore.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (Wout) TRMF_HIP_CHECK(hipMemcpyAsync(hflat.data(), flat.p, hflat.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
+        if (weights_out && nw) TRMF_HIP_CHECK(hipMemcpyAsync(hwts.data(), wts.p, hwts.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (bad != kAssimNoBadRow) { res->bad_row = first_row + bad; return 0; }
+        // ---- commit ----
+        TRMF_HIP_CHECK(hipMemcpyAsync(W.p + (size_t)first_row * KP, xc.p, (size_t)m * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        if (first_row < ad_rows) adapt_stale();                     // rows the series statistics absorbed have changed
+        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new W
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        res->rows = (uint64_t)m;
+        res->entries = nw;
+        res->sweeps = sweeps;
+        res->converged = 1;
+        for (int s = 0; s < sweeps; s++) {
+            const int it = hst[s].done ? hst[s].iters : max_iter;
+            res->iterations += it;
+            if (!hst[s].done) res->converged = 0;
+            if (s == sweeps - 1) res->residual = hst[s].rz0 > 0 ? std::sqrt(std::max(hst[s].rz[it & 1], 0.0) / hst[s].rz0) : 0.0;
+        }
+        double down = 0, w2[2] = {0, 0}, e2[2] = {0, 0}, rho[2] = {0, 0};
+        for (int r = 0; r < m; r++) {                               // row order, then item order: the same sums on every rank and every call
+            down += hsum[2 * r]; res->weight_sum += hsum[2 * r + 1];
+            w2[0] += hobj[4 * r]; e2[0] += hobj[4 * r + 1]; w2[1] += hobj[4 * r + 2]; e2[1] += hobj[4 * r + 3];
+        }
+        for (uint32_t it = 0; it < nitems; it++) {
+            const double *a0 = hscore.data() + (size_t)it * kSmoothRobustSlotD, *a1 = a0 + ni * kSmoothRobustSlotD;
+            rho[0] += a0[2]; res->sq_err_before += a0[3]; rho[1] += a1[2]; res->sq_err_after += a1[3];
+        }
+        res->downweighted = (uint64_t)down;
+        res->objective_before = rho[0] + 0.5 * ((double)lamI * w2[0] + (double)lamAR * e2[0]);
+        res->objective_after = rho[1] + 0.5 * ((double)lamI * w2[1] + (double)lamAR * e2[1]);
+        if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
+        if (weights_out && nw) std::memcpy(weights_out, hwts.data(), hwts.size() * sizeof(real));
         return 0;
     }
     // ---- online loading updates (trmf_session_series_stats_init / _adapt_series; adapt_kernels.hpp) -----------------------------------

@@ -66,11 +66,13 @@ struct SmoothState {
 };
 
 struct SmoothArgs {
-    const real *W;                     // the session's W (column-interleaved, pitch KP): the head rows and x0
+    const real *W;                     // the session's W (column-interleaved, pitch KP): the head rows
+    const real *x0;                    // the window's starting rows, m x KP column-interleaved (trmf_session_smooth: W + first_row * KP)
     const real *Bv;                    // b_i: rows x KP, logical columns
     const real *G;                     // the Gram cache (or the one shared Gram)
     size_t gstride;                    // elements between the Grams of consecutive rows; 0: one shared Gram
     int packed;
+    int grow;                          // the row of G / Bv that window row 0 reads (trmf_session_smooth: first_row; 0: tables of the window's own)
     const real *U;                     // m x (k x k) upper factors of A_i, row-major
     const uint32_t *lag_set;
     const real *theta;                 // Theta(l, t) at t * nlag + l
@@ -187,14 +189,16 @@ __global__ __launch_bounds__(256) void smooth_ar_kernel(SmoothArgs a, int mode, 
     const real *pold = a.p[(j + 1) & 1], *zz = a.z;
     real *pnew = a.p[j & 1];
     real own;
-    if (mode == SMOOTH_INIT) own = on ? a.W[(size_t)(f + r) * a.KP + tp] : real(0);
+    if (mode == SMOOTH_INIT) own = on ? a.x0[(size_t)r * a.KP + tp] : real(0);
     else if (refine) own = a.x[(size_t)r * 64 + c];
     else own = on ? fma(beta, pold[(size_t)r * 64 + c], zz[(size_t)r * 64 + c]) : real(0);
     real acc = 0;
     for (int l = 0; l < a.nlag; l++) {
         const int src = r - th.lag[l];                      // window row of the lagged row; < 0: a head row
         real v = 0;
-        if (mode == SMOOTH_INIT || (refine && src < 0)) {
+        if (mode == SMOOTH_INIT && src >= 0) {
+            if (on) v = a.x0[(size_t)src * a.KP + tp];
+        } else if (mode == SMOOTH_INIT || (refine && src < 0)) {
             if (on) v = a.W[(size_t)(f + src) * a.KP + tp];  // f + src >= 0: first_row >= the largest lag
         } else if (refine) v = a.x[(size_t)src * 64 + c];
         else if (src >= 0 && on) v = fma(beta, pold[(size_t)src * 64 + c], zz[(size_t)src * 64 + c]);
@@ -218,7 +222,7 @@ __global__ __launch_bounds__(256) void smooth_apply_kernel(SmoothArgs a, int mod
     if (mode != SMOOTH_INIT && a.st->refine[j & 1]) mode = SMOOTH_INIT;      // a replacement step: r = b - A x, like the start
     const real *v = mode == SMOOTH_INIT ? a.x : a.p[j & 1];
     const real pv = v[(size_t)r * 64 + c];
-    const real *Gi = a.G + (size_t)(a.first_row + r) * a.gstride;
+    const real *Gi = a.G + (size_t)(a.grow + r) * a.gstride;
     // (G p)_c with lane c walking column c of the symmetric G_i: consecutive lanes read consecutive addresses
     real acc = 0;
     if (a.packed) {
@@ -237,7 +241,7 @@ __global__ __launch_bounds__(256) void smooth_apply_kernel(SmoothArgs a, int mod
     real qv = fma(a.lamAR, ar, fma(a.lamI, pv, acc));
     if (!on) qv = 0;
     if (mode == SMOOTH_INIT) {
-        a.r[(size_t)r * 64 + c] = on ? a.Bv[(size_t)(a.first_row + r) * a.KP + c] - qv : real(0);
+        a.r[(size_t)r * 64 + c] = on ? a.Bv[(size_t)(a.grow + r) * a.KP + c] - qv : real(0);
         return;
     }
     a.q[(size_t)r * 64 + c] = qv;

@@ -669,6 +669,81 @@ int32_t trmf_session_smooth(TrmfSession *s, int32_t first_row, double rtol, int3
     return 0;
 }
 
+// Robust smoother: the checks of trmf_session_smooth and of trmf_session_assimilate_robust, all on the calling thread before any
+// rank's worker runs.
+int32_t trmf_session_smooth_robust(TrmfSession *s, int32_t first_row, double c, int32_t sweeps, const double *scale, double rtol, int32_t max_iter,
+                                   TrmfRobustSmoothSums *out, void *Wnew, void *weights) {
+    if (!s) { set_error("null session"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (f->k > kMaxRank) {
+        set_error("smooth_robust: online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
+        return kFail;
+    }
+    if (f->has_lag0) { set_error("smooth_robust: the lag set contains lag 0 (a row would be its own prior)"); return kFail; }
+    if (f->full && !f->dense) {
+        set_error("smooth_robust: sparse storage with missing == 0 is not covered (an absent entry there is an observation without a slot "
+                  "to report its weight in); store the matrix dense");
+        return kFail;
+    }
+    if (first_row < f->midx || first_row > f->T) {
+        set_error("smooth_robust: first_row " + std::to_string(first_row) + " outside [" + std::to_string(f->midx) + " (the largest lag), " +
+                  std::to_string(f->T) + " (rows)]");
+        return kFail;
+    }
+    const int cap = TrmfSessionImpl::smooth_max_rows();
+    if (f->T - first_row > cap) {
+        set_error("smooth_robust: a window of " + std::to_string(f->T - first_row) + " rows is above the cap of " + std::to_string(cap) +
+                  " rows (the factors of every window row stay resident for the solve)");
+        return kFail;
+    }
+    if (!(c > 0)) { set_error("smooth_robust: c must be positive (infinity: the plain smoother's objective)"); return kFail; }
+    if (sweeps < 1 || sweeps > kSmoothRobustMaxSweeps) {
+        set_error("smooth_robust: sweeps " + std::to_string(sweeps) + " outside 1.." + std::to_string(kSmoothRobustMaxSweeps));
+        return kFail;
+    }
+    if (!std::isfinite(rtol)) { set_error("smooth_robust: rtol must be finite (<= 0: the default of the element type)"); return kFail; }
+    if (max_iter > kSmoothMaxIter) { set_error("smooth_robust: max_iter " + std::to_string(max_iter) + " above " + std::to_string(kSmoothMaxIter)); return kFail; }
+    if (!scale && !f->nz_set) { set_error("smooth_robust: no scale given and no noise fitted or set (trmf_session_fit_noise / _set_noise)"); return kFail; }
+    if (rtol <= 0) rtol = kSmoothDefaultRtol;
+    if (max_iter <= 0) max_iter = kSmoothDefaultMaxIter;
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    std::vector<double> sc((size_t)f->n);
+    if (scale) std::copy(scale, scale + f->n, sc.begin());
+    else {
+        if (HND(s)->rank0([&](TrmfSessionImpl *t) { return t->noise(sc.data(), nullptr); })) return kFail;
+        for (double &v : sc) v = std::sqrt(v);
+    }
+    for (int j = 0; j < f->n; j++)
+        if (!(std::isfinite(sc[j]) && sc[j] > 0)) {
+            set_error("smooth_robust: the scale of series " + std::to_string(j) + " is not finite and positive" +
+                      (scale ? "" : " (the square root of the resident sigma2)"));
+            return kFail;
+        }
+    const bool grouped = HND(s)->group != nullptr;
+    std::vector<TrmfSessionImpl::RobustSmoothResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
+    if (HND(s)->all([&](TrmfSessionImpl *t) {
+            const int slot = grouped ? t->comm->rank : 0;
+            return t->smooth_robust(first_row, c, sweeps, sc.data(), rtol, max_iter, &res[slot], slot == 0 ? (real *)Wnew : nullptr,
+                                    slot == 0 ? (real *)weights : nullptr);
+        })) return kFail;
+    for (const auto &r : res)
+        if (r.bad_row >= 0) {
+            set_error("smooth_robust: row " + std::to_string(r.bad_row) + ": a pivot of the weighted G + (lambdaI + lambdaAR) I is not positive and "
+                      "finite (lambdaI + lambdaAR == 0 and a rank-deficient row?); nothing was changed");
+            return kFail;
+        }
+    if (out) {
+        const auto &r = res[0];
+        out->rows = r.rows; out->entries = r.entries; out->downweighted = r.downweighted;
+        out->sweeps = r.sweeps; out->iterations = r.iterations; out->converged = r.converged; out->reserved = 0;
+        out->residual = r.residual; out->weight_sum = r.weight_sum;
+        out->sq_err_before = r.sq_err_before; out->sq_err_after = r.sq_err_after;
+        out->objective_before = r.objective_before; out->objective_after = r.objective_after;
+    }
+    return 0;
+}
+
 // Online loading updates: the arguments and the state of the tables are checked on the calling thread before any rank's worker runs
 // (see trmf_session_set_heldout); a bad pivot or a pool without room is found by every rank alike and reported here.
 static int adapt_call(TrmfSession *s, bool init, double forget, TrmfAdaptSums *out, void *Hnew) {

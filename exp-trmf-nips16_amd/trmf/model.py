@@ -168,7 +168,7 @@ class Model(object):
 
     # ---- online update ----------------------------------------------------------------------------
     def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0,
-                   smooth_back=0, Yback=None):
+                   smooth_back=0, Yback=None, smooth_robust=False):
         """A new ``Model`` grown by the ``Ynew.shape[0]`` timestamps of ``Ynew`` (raw values; a transform of this model is
         applied first): H, the lag weights and the rows this model has stay as they are, every new row of W is solved from its
         own observations and the AR prior of the rows before it (``trmf.online.filter_rows``; the host form of
@@ -182,13 +182,19 @@ class Model(object):
         With ``smooth_back > 0`` the new rows and the ``smooth_back`` rows before them (clipped at the largest lag) are then
         smoothed (``trmf.online.smooth_rows``; the host form of ``Session.update(smooth_back=)``): a model keeps no training
         matrix, so ``Yback`` must hold the last ``smooth_back`` rows this model was trained on (raw values, like ``Ynew``).
-        Together with ``robust_c`` that is refused: the smoother weights every cell fully."""
-        from .online import filter_rows, robust_filter_rows, smooth_rows
+        Together with ``robust_c`` that is refused (the smoother weights every cell fully) unless ``smooth_robust=True``: the
+        window is then smoothed on Huber's loss (``trmf.online.robust_smooth_rows`` with the same ``robust_c``, ``scale`` and
+        ``robust_sweeps``; the host form of ``Session.update(smooth_robust=True)``), and ``robust_weights`` of the new model are the
+        smoother's, one per cell of the window.  ``smooth_robust=True`` without both ``robust_c`` and ``smooth_back > 0`` is refused."""
+        from .online import filter_rows, robust_filter_rows, smooth_rows, robust_smooth_rows
         smooth_back = int(smooth_back)
         if smooth_back < 0:
             raise ValueError('assimilate: smooth_back must not be negative, not {}'.format(smooth_back))
+        if smooth_robust and (robust_c is None or smooth_back <= 0):
+            raise ValueError('assimilate: smooth_robust=True needs both robust_c and smooth_back > 0 (it back-smooths with the Huber weights '
+                             'of the robust filter)')
         if smooth_back > 0:
-            if robust_c is not None:
+            if robust_c is not None and not smooth_robust:
                 raise ValueError('assimilate: smooth_back together with robust_c is refused: the smoother weights every cell fully and '
                                  'would undo the Huber weights of the robust filter')
             if adapt:
@@ -220,7 +226,11 @@ class Model(object):
             first = max(self.m - smooth_back, int(self.lag_set.max()) if len(self.lag_set) else 0)
             tail = Yback[smooth_back - (self.m - first):] if first < self.m else Yback[:0]
             window = smat.vstack([smat.csr_matrix(tail), smat.csr_matrix(Ynew)]).tocsr() if smat.issparse(Ynew) else np.vstack([np.asarray(tail), np.asarray(Ynew)])
-            grown = smooth_rows(grown, self.H, self.lag_set, self.lag_val, window, first, lambdaI, lambdaAR, missing)
+            if smooth_robust:
+                grown, weights = robust_smooth_rows(grown, self.H, self.lag_set, self.lag_val, window, first, lambdaI, lambdaAR, missing,
+                                                    scale, robust_c, robust_sweeps)
+            else:
+                grown = smooth_rows(grown, self.H, self.lag_set, self.lag_val, window, first, lambdaI, lambdaAR, missing)
         out = Model.from_arrays(grown, self.H.copy(), self.lag_val.copy(), self.lag_set.copy(), transform=self.transform)
         stats = getattr(self, 'series_stats', None)
         if adapt:

@@ -12,6 +12,7 @@ A filter, not a smoother: rows before ``first_row`` never see the new data.  ``f
 tests compare against and the host path of ``Model.assimilate``.  ``smooth_rows`` is the smoother (``trmf_session_smooth``): the
 joint minimiser over a window of tail rows, which also counts the AR penalties of the later rows a row appears in.  ``robust_filter_rows`` is the same filter with Huber weights
 (``trmf_session_assimilate_robust``): a cell far outside its series' residual scale is down-weighted, and the weights are returned.
+``robust_smooth_rows`` is the smoother on the same Huber loss (``trmf_session_smooth_robust``).
 """
 import numpy as np
 import scipy.linalg
@@ -234,18 +235,30 @@ def smooth_rows(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, mis
         return out
     H = np.asarray(H, dtype=dt)
     theta = np.asarray(lag_val, dtype=dt).reshape(len(back), k)
-    lamI, lamAR = dt.type(lambdaI), dt.type(lambdaAR)
     sparse = smat.issparse(Yrows)
     Yr = Yrows.tocsr() if sparse else np.asarray(Yrows)
+    obs = [_row_observations(Yr, r, sparse, missing, H.shape[0], dt) for r in range(m)]
+    out[first_row:] = _solve_window('smooth_rows', W, H, back, theta, reach, first_row, obs, None, dt.type(lambdaI), dt.type(lambdaAR))
+    return out
+
+
+def _solve_window(what, W, H, back, theta, reach, first_row, obs, omega, lamI, lamAR):
+    """The window's rows (m x k) solving ``(D + lambdaAR B^T B) x = b + lambdaAR B^T h`` by a banded Cholesky factorisation, with
+    ``G_i = sum_j omega_ij h_j h_j^T`` and ``b_i = sum_j omega_ij y_ij h_j`` (``omega`` None: every weight 1).  ``obs[r]``: (columns,
+    values) of window row r; ``omega[r]``: its weights."""
+    dt = W.dtype
+    T, k = W.shape
+    m = T - first_row
     eye = np.eye(k, dtype=dt)
     A4 = np.zeros((m, k, m, k), dtype=dt)
     rhs = np.zeros((m, k), dtype=dt)
     head = np.zeros((m, k), dtype=dt)                        # the head rows' share of e: e = B x - head
     for r in range(m):
         i = first_row + r
-        cols, y = _row_observations(Yr, r, sparse, missing, H.shape[0], dt)
+        cols, y = obs[r]
         Hi = H[cols]
-        G = Hi.T.dot(Hi)
+        Hw = Hi if omega is None else Hi * omega[r][:, None]
+        G = Hw.T.dot(Hi)
         block = G + (lamI + lamAR) * eye
         try:
             if not np.all(np.isfinite(block)):
@@ -254,9 +267,9 @@ def smooth_rows(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, mis
             if not (np.all(np.isfinite(L)) and np.all(np.diagonal(L) > 0)):
                 raise np.linalg.LinAlgError('pivot')
         except np.linalg.LinAlgError:
-            raise ValueError('smooth_rows: row {}: G + (lambdaI + lambdaAR) I is not positive definite'.format(i))
+            raise ValueError('{}: row {}: {}G + (lambdaI + lambdaAR) I is not positive definite'.format(what, i, '' if omega is None else 'the weighted '))
         A4[r, :, r, :] = G + lamI * eye
-        rhs[r] = Hi.T.dot(y)
+        rhs[r] = Hw.T.dot(y)
         for l, lag in enumerate(back):
             if r - lag < 0:
                 head[r] += theta[l] * W[i - lag]
@@ -273,9 +286,8 @@ def smooth_rows(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, mis
     try:
         cb = scipy.linalg.cholesky_banded(ab, lower=False, check_finite=True)
     except (np.linalg.LinAlgError, ValueError):
-        raise ValueError('smooth_rows: the system of rows {}..{} is not positive definite'.format(first_row, T))
-    out[first_row:] = scipy.linalg.cho_solve_banded((cb, False), rhs.reshape(N), check_finite=False).reshape(m, k)
-    return out
+        raise ValueError('{}: the system of rows {}..{} is not positive definite'.format(what, first_row, T))
+    return scipy.linalg.cho_solve_banded((cb, False), rhs.reshape(N), check_finite=False).reshape(m, k)
 
 
 def window_objective(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, missing):
@@ -294,6 +306,103 @@ def window_objective(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR
         e = W[i] - np.sum(W[i - back] * theta, axis=0) if back.size else W[i]
         fit += float(res.dot(res)); ridge += float(W[i].dot(W[i])); ar += float(e.dot(e))
     return 0.5 * (fit + float(lambdaI) * ridge + float(lambdaAR) * ar)
+
+
+# ---- the robust fixed-interval smoother: the smoother on Huber's loss (trmf_session_smooth_robust) --------------------------------
+def _robust_guards(what, n, Yrows, missing, scale, c, sweeps):
+    """robust_filter_rows' guards under another name: (scale as float64 (n,), c, sweeps)."""
+    if smat.issparse(Yrows) and not missing:
+        raise ValueError('{}: sparse rows without missing are not covered (an absent entry would be an observation '
+                         'without a slot to report its weight in); pass the rows as an array'.format(what))
+    scale = np.asarray(scale, dtype=np.float64)
+    if scale.ndim == 0:
+        scale = np.full(n, float(scale))
+    if scale.shape != (n,):
+        raise ValueError('{}: scale has shape {}, one value per series ({}) was expected'.format(what, scale.shape, n))
+    bad = np.flatnonzero(~(np.isfinite(scale) & (scale > 0)))
+    if bad.size:
+        raise ValueError('{}: scale[{}] = {!r} is not finite and positive'.format(what, int(bad[0]), float(scale[bad[0]])))
+    c = float(c)
+    if not c > 0:
+        raise ValueError('{}: c must be positive (inf: every cell weighted fully), not {!r}'.format(what, c))
+    sweeps = int(sweeps)
+    if sweeps < 1:
+        raise ValueError('{}: sweeps must be at least 1, not {}'.format(what, sweeps))
+    return scale, c, sweeps
+
+
+def robust_smooth_rows(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, missing, scale, c=3.0, sweeps=4):
+    """``smooth_rows`` on Huber's loss: the specification of ``trmf_session_smooth_robust``.  With ``t_j = c * scale[j]`` ::
+
+        J_rob = sum_{i>=f} sum_{j in Omega_i} rho_{t_j}(y_ij - w_i . h_j) + 1/2 lambdaI sum_{i>=f} |w_i|^2 + 1/2 lambdaAR sum_{i>=f} |e_i|^2
+        rho_t(r) = 1/2 r^2 if |r| <= t,  t |r| - 1/2 t^2 otherwise
+        x^0 = the rows f .. as they stand;  for s = 1 .. sweeps:
+            omega_ij = t_j / |r_ij| if |r_ij| > t_j else 1,   r_ij = y_ij - x^{s-1}_i . h_j
+            x^s = smooth_rows' system with G_i = sum_j omega_ij h_j h_j^T, b_i = sum_j omega_ij y_ij h_j, solved directly
+
+    (iteratively reweighted least squares: every sweep minimises a quadratic majoriser of ``J_rob``, so ``J_rob`` never rises; a
+    fixed number of sweeps, no convergence test).  Returns ``(W_out, weights)``: the weights of the LAST sweep (formed from
+    ``x^{sweeps-1}``) in ``robust_filter_rows``' layout.  ``c = inf`` is ``smooth_rows``.  The guards are ``smooth_rows``' and
+    ``robust_filter_rows``'."""
+    W = np.asarray(W)
+    dt = W.dtype
+    T, k, back, reach, first_row = _window_guards('robust_smooth_rows', W, H, lag_set, Yrows, first_row)
+    n = H.shape[0]
+    scale, c, sweeps = _robust_guards('robust_smooth_rows', n, Yrows, missing, scale, c, sweeps)
+    sparse = smat.issparse(Yrows)
+    Yr = Yrows.tocsr() if sparse else np.asarray(Yrows)
+    m = T - first_row
+    out = W.copy()
+    weights = np.ones(Yr.data.shape[0] if sparse else (m, n), dtype=dt)
+    if m == 0:
+        return out, weights
+    H = np.asarray(H, dtype=dt)
+    theta = np.asarray(lag_val, dtype=dt).reshape(len(back), k)
+    thr = dt.type(c) * scale.astype(dt)
+    obs = []
+    for r in range(m):
+        cols, y = _row_observations(Yr, r, sparse, missing, n, dt)
+        obs.append((np.arange(n) if isinstance(cols, slice) else cols, y))
+    omega = None
+    for _ in range(sweeps):
+        omega = []
+        for r, (cols, y) in enumerate(obs):
+            res = np.abs(y - H[cols].dot(out[first_row + r]))
+            om = np.ones(len(y), dtype=dt)
+            far = res > thr[cols]
+            om[far] = thr[cols][far] / res[far]
+            omega.append(om)
+        out[first_row:] = _solve_window('robust_smooth_rows', out, H, back, theta, reach, first_row, obs, omega, dt.type(lambdaI), dt.type(lambdaAR))
+    for r, (cols, y) in enumerate(obs):
+        if sparse:
+            weights[Yr.indptr[r]:Yr.indptr[r + 1]] = omega[r]
+        else:
+            weights[r, cols] = omega[r]
+    return out, weights
+
+
+def robust_window_objective(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, lambdaAR, missing, scale, c=3.0):
+    """``J_rob`` of ``robust_smooth_rows`` for the rows of ``W`` as they are, in float64 (``objective_before`` / ``objective_after``
+    of ``trmf_session_smooth_robust``).  ``c = inf`` is ``window_objective``."""
+    W = np.asarray(W, dtype=np.float64)
+    T, k, back, reach, first_row = _window_guards('robust_window_objective', W, H, lag_set, Yrows, first_row)
+    n = H.shape[0]
+    scale, c, _ = _robust_guards('robust_window_objective', n, Yrows, missing, scale, c, 1)
+    H = np.asarray(H, dtype=np.float64)
+    theta = np.asarray(lag_val, dtype=np.float64).reshape(len(back), k)
+    thr = c * scale
+    sparse = smat.issparse(Yrows)
+    Yr = Yrows.tocsr() if sparse else np.asarray(Yrows)
+    fit = ridge = ar = 0.0
+    for i in range(first_row, T):
+        cols, y = _row_observations(Yr, i - first_row, sparse, missing, n, np.dtype(np.float64))
+        res = np.abs(y - H[cols].dot(W[i]))
+        t = thr[cols]
+        with np.errstate(invalid='ignore'):
+            rho = np.where(res > t, t * res - 0.5 * t * t, 0.5 * res * res)
+        e = W[i] - np.sum(W[i - back] * theta, axis=0) if back.size else W[i]
+        fit += float(rho.sum()); ridge += float(W[i].dot(W[i])); ar += float(e.dot(e))
+    return fit + 0.5 * (float(lambdaI) * ridge + float(lambdaAR) * ar)
 
 
 # ---- online loading updates: the rows of H refitted from new rows (trmf_session_series_stats_init / _adapt_series) ---------------

@@ -73,6 +73,17 @@ class TrmfSmoothSums(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TrmfRobustSmoothSums(ctypes.Structure):
+    """Sums of a robust smoother call (include/trmf_abi.h): those of ``TrmfSmoothSums`` over all sweeps (``objective_*`` are the
+    Huber objective), the number of down-weighted entries and the sum of the weights of the last sweep."""
+    _fields_ = [('rows', c_uint64), ('entries', c_uint64), ('downweighted', c_uint64), ('sweeps', c_int32), ('iterations', c_int32),
+                ('converged', c_int32), ('reserved', c_int32), ('residual', c_double), ('weight_sum', c_double), ('sq_err_before', c_double),
+                ('sq_err_after', c_double), ('objective_before', c_double), ('objective_after', c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != 'reserved'}
+
+
 class TrmfAdaptSums(ctypes.Structure):
     """Sums of an online loading update (include/trmf_abi.h): series refitted, rows and entries absorbed, the squared error of the
     absorbed entries with H as it was / as it is, the largest change of an element of H."""
@@ -175,6 +186,10 @@ def bind(lib):
     if hasattr(lib, 'trmf_session_smooth'):           # (absent from libraries built before the smoother)
         lib.trmf_session_smooth.argtypes = [c_void_p, c_int32, c_double, c_int32, POINTER(TrmfSmoothSums), c_void_p]
         lib.trmf_session_smooth.restype = c_int32
+    if hasattr(lib, 'trmf_session_smooth_robust'):    # (absent from libraries built before the robust smoother)
+        lib.trmf_session_smooth_robust.argtypes = [c_void_p, c_int32, c_double, c_int32, c_void_p, c_double, c_int32, POINTER(TrmfRobustSmoothSums),
+                                                   c_void_p, c_void_p]
+        lib.trmf_session_smooth_robust.restype = c_int32
     if hasattr(lib, 'trmf_session_adapt_series'):     # (absent from libraries built before the online loading updates)
         lib.trmf_session_series_stats_init.argtypes = [c_void_p, c_double]; lib.trmf_session_series_stats_init.restype = c_int32
         lib.trmf_session_adapt_series.argtypes = [c_void_p, POINTER(TrmfAdaptSums), c_void_p]; lib.trmf_session_adapt_series.restype = c_int32
@@ -369,6 +384,43 @@ class Session(object):
                                                  byref(sums), Wnew.ctypes.data if Wnew is not None and Wnew.size else None), 'trmf_session_smooth')
         return (sums.as_dict(), Wnew) if return_latent else sums.as_dict()
 
+    def smooth_robust(self, first_row, c=3.0, sweeps=4, scale=None, rtol=None, max_iter=None, return_latent=False, return_weights=False):
+        """``smooth`` on Huber's loss (``trmf.online.robust_smooth_rows`` is the same statement in NumPy, every sweep solved
+        directly): ``sweeps`` rounds of reweighting, each one the smoother's system with every cell weighted by ``c * scale[j] /
+        |r|`` where its residual at the rows of the round before lies beyond ``c * scale[j]``, solved by the smoother's PCG from
+        those rows.  ``c``, ``sweeps``, ``scale`` as for ``assimilate_robust``; ``rtol``, ``max_iter`` as for ``smooth``, per sweep.
+        The Huber objective never rises, also when a sweep stops at ``max_iter`` (``converged == 0``; the call still commits).
+        Returns ``{'rows', 'entries', 'downweighted', 'sweeps', 'iterations', 'converged', 'residual', 'weight_sum', 'sq_err_before',
+        'sq_err_after', 'objective_before', 'objective_after'}`` (``iterations`` over all sweeps, ``residual`` of the last), followed
+        by ``Wnew`` with ``return_latent`` and by the last sweep's weights with ``return_weights`` (the layout of
+        ``assimilate_robust``).  A refused call (everything ``smooth`` and ``assimilate_robust`` refuse) raises and leaves the
+        session as it was."""
+        first_row = int(first_row)
+        dt = self.model.W.dtype
+        nr = max(self.rows() - first_row, 0)
+        sc = None
+        if scale is not None:
+            sc = np.asarray(scale, dtype=np.float64)
+            if sc.ndim == 0:
+                sc = np.full(self.model.n, float(sc))
+            if sc.shape != (self.model.n,):
+                raise ValueError('smooth_robust: scale has shape {}, one value per series ({}) was expected'.format(sc.shape, self.model.n))
+            sc = np.ascontiguousarray(sc)
+        sums = TrmfRobustSmoothSums()
+        Wnew = np.empty((nr, self.model.k), dtype=dt) if return_latent else None
+        weights = None
+        if return_weights:
+            if self._stored is not None:
+                weights = np.empty(int(self._stored[first_row:].sum()) if nr and first_row >= 0 else 0, dtype=dt)
+            else:
+                weights = np.empty((nr, self.model.n), dtype=dt)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        self._check(self.lib.trmf_session_smooth_robust(self.handle, first_row, float(c), int(sweeps), ptr(sc), 0.0 if rtol is None else float(rtol),
+                                                        0 if max_iter is None else int(max_iter), byref(sums), ptr(Wnew), ptr(weights)),
+                    'trmf_session_smooth_robust')
+        out = (sums.as_dict(),) + ((Wnew,) if return_latent else ()) + ((weights,) if return_weights else ())
+        return out if len(out) > 1 else out[0]
+
     def _reach(self):
         return int(self.model.lag_set.max()) if len(self.model.lag_set) else 0
 
@@ -399,7 +451,7 @@ class Session(object):
         self._check(self.lib.trmf_session_series_stats_info(self.handle, byref(v), byref(rows), byref(g)), 'trmf_session_series_stats_info')
         return {'valid': v.value == 1, 'stale': v.value == -1, 'absorbed_rows': int(rows.value), 'forget': float(g.value)}
 
-    def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0, smooth_back=0):
+    def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0, smooth_back=0, smooth_robust=False):
         """Absorb the new timestamps ``Ynew`` (as for ``append_rows``): append them, assimilate the new block, run ``iters``
         ALS iterations if asked for.  ``self.model`` is replaced by a host model of ``rows()`` timestamps (H, lag weights, lag
         set and transform carried over; its arrays are filled by the next ``download()``).  Returns the sums of ``assimilate``;
@@ -407,13 +459,18 @@ class Session(object):
         are returned.  With ``adapt`` the loadings follow: the series statistics are initialised with ``forget`` before the
         append if the session has none (existing ones keep their own), ``adapt_series`` runs after the block has been assimilated
         and ``(sums, adapt_sums)`` is returned.  With ``smooth_back > 0`` the block and the ``smooth_back`` rows before it are then
-        smoothed, ``smooth(before - smooth_back)`` clipped at the largest lag; its sums are returned as ``sums['smooth']``.  Together with ``robust_c`` that is refused: the smoother
-        weights every cell fully and would undo the Huber weights; so is ``adapt``: the rows before the block are the ones the
-        series statistics have absorbed."""
+        smoothed, ``smooth(before - smooth_back)`` clipped at the largest lag; its sums are returned as ``sums['smooth']``.  Together with ``robust_c`` that is refused (the smoother
+        weights every cell fully and would undo the Huber weights) unless ``smooth_robust=True`` is passed: the back-smoothing
+        is then ``smooth_robust`` with the same ``robust_c``, ``scale`` and ``robust_sweeps``.  ``smooth_robust=True`` without both
+        ``robust_c`` and ``smooth_back > 0`` is refused.  ``smooth_back`` with ``adapt`` is refused: the rows before the block are the
+        ones the series statistics have absorbed."""
         smooth_back = int(smooth_back)
         if smooth_back < 0:
             raise ValueError('update: smooth_back must not be negative, not {}'.format(smooth_back))
-        if smooth_back > 0 and robust_c is not None:
+        if smooth_robust and (robust_c is None or smooth_back <= 0):
+            raise ValueError('update: smooth_robust=True needs both robust_c and smooth_back > 0 (it back-smooths with the Huber weights '
+                             'of the robust filter)')
+        if smooth_back > 0 and robust_c is not None and not smooth_robust:
             raise ValueError('update: smooth_back together with robust_c is refused: the smoother weights every cell fully and would '
                              'undo the Huber weights of the robust filter')
         if smooth_back > 0 and adapt:
@@ -433,7 +490,8 @@ class Session(object):
         self.model = type(old).from_arrays(grown, old.H.copy(), old.lag_val.copy(), old.lag_set.copy(), transform=old.transform)
         sums = self.assimilate(before) if robust_c is None else self.assimilate_robust(before, robust_c, robust_sweeps, scale)
         if smooth_back > 0:
-            sums['smooth'] = self.smooth(max(before - smooth_back, self._reach()))
+            first = max(before - smooth_back, self._reach())
+            sums['smooth'] = self.smooth_robust(first, robust_c, robust_sweeps, scale) if smooth_robust else self.smooth(first)
         adapted = self.adapt_series() if adapt else None
         if iters:
             self.run(int(iters))

@@ -96,7 +96,11 @@ def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_
                 else:
                     sess.assimilate_robust(cuts[i - 1], robust['robust_c'], robust['robust_sweeps'])
                 if smooth_back:           # ... the block and the rows before it smoothed
-                    sess.smooth(max(cuts[i - 1] - smooth_back, max(lag_set)))
+                    first = max(cuts[i - 1] - smooth_back, max(lag_set))
+                    if robust is not None:    # (only with smooth_robust=True: the pair is refused otherwise)
+                        sess.smooth_robust(first, robust['robust_c'], robust['robust_sweeps'])
+                    else:
+                        sess.smooth(first)
                 if adapt is not None:     # ... and the loadings follow
                     sess.adapt_series()
             else:
@@ -129,7 +133,7 @@ def _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, tr
 def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5, lambdaAR=50, lambdaLag=0.5,
                      max_iter=20, missing=True, threshold=0, transform=None, threads=16, verbose=0, seed=0,
                      resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False, update='retrain', interval_level=None,
-                     robust_c=None, robust_sweeps=4, adapt_series=False, forget=1.0, smooth_back=0):
+                     robust_c=None, robust_sweeps=4, adapt_series=False, forget=1.0, smooth_back=0, smooth_robust=False):
     """``interval_level`` (e.g. 0.9; needs ``forecast_on_device=True``): every window also fits the noise of its trained model and
     scores the predictive distribution of its forecast on the device; the result is ``(Metrics, IntervalMetrics)``, the ``Metrics``
     being exactly those of the call without it.
@@ -145,6 +149,8 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
     ``smooth_back`` (with ``update='assimilate'`` only, not with ``robust_c``): after every absorbed window the block and the
     ``smooth_back`` rows before it become the joint minimiser of the objective over that window (``Session.smooth``), so that the rows
     a forecast starts from also count the rows after them; 0 leaves the filter's rows.
+    ``smooth_robust=True`` (needs both ``robust_c`` and ``smooth_back > 0``): the pair is accepted and the back-smoothing is
+    ``Session.smooth_robust`` with the same ``robust_c`` and ``robust_sweeps``, on Huber's loss like the filter before it.
     ``lambdaLagL1`` / ``lag_refit``: sparse lag weights (``Session.set_lag_penalty``) on every path.
     ``forecast_on_device=True`` keeps the forecasts and their scoring on the device as well (one session, no download and no
     host model per window); it needs the resident path and a dense ``Y``, and says so where that does not hold."""
@@ -174,13 +180,17 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
     smooth_back = int(smooth_back)
     if smooth_back < 0:
         raise ValueError('smooth_back must not be negative, not {}'.format(smooth_back))
+    if smooth_robust and (robust_c is None or smooth_back <= 0):
+        raise ValueError('smooth_robust=True needs both robust_c and smooth_back > 0 (it back-smooths with the Huber weights of the robust filter)')
     if smooth_back > 0:
         if not online:
             raise ValueError("smooth_back: the smoother revisits rows absorbed online (update='assimilate'); retraining solves them jointly anyway")
-        if robust is not None:
+        if robust is not None and not smooth_robust:
             raise ValueError('smooth_back together with robust_c is refused: the smoother weights every cell fully and would undo the Huber weights')
         if adapt is not None:
             raise ValueError('smooth_back together with adapt_series is refused: the rows before the block are the ones the series statistics have absorbed: smoothing them makes the statistics stale')
+    if smooth_robust:
+        robust['smooth_robust'] = True      # (Session.update's keyword)
     if online:
         if transform is not None:
             raise ValueError("update='assimilate': a per-window transform rescales the whole history, which an online update does not revisit")

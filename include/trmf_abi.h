@@ -482,6 +482,53 @@ typedef struct {
 TRMF_API int32_t trmf_session_smooth(TrmfSession *s, int32_t first_row, double rtol, int32_t max_iter,
                                      TrmfSmoothSums *out /* or NULL */, void *Wnew /* or NULL: (rows - first_row) x k */);
 
+/* --- robust fixed-interval smoother: Huber-weighted windowed PCG ------------------------------------------------------------
+ * trmf_session_smooth weights every cell fully, so one gross outlier among the new cells bends the tail rows; the robust filter
+ * trmf_session_assimilate_robust is not the minimiser of the window's objective.  This call is both: with f = first_row,
+ * thresholds t_j = c scale_j, and H, Theta, the lag set, the rows before f and the session's current lambdaI, lambdaAR fixed, and
+ * Omega_i and y exactly as for trmf_session_assimilate,
+ *   J_rob = sum_{i>=f} sum_{j in Omega_i} rho_{t_j}(y_ij - w_i . h_j) + 1/2 lambdaI sum_{i>=f} |w_i|^2 + 1/2 lambdaAR sum_{i>=f} |e_i|^2
+ *   rho_t(r) = 1/2 r^2 if |r| <= t,  t |r| - 1/2 t^2 otherwise;       e_i as for trmf_session_smooth
+ * is lowered by `sweeps` rounds of iteratively reweighted least squares:
+ *   x^0 = the rows f .. as they stand;   for s = 1 .. sweeps:
+ *       omega_ij = t_j / |r_ij| if |r_ij| > t_j else 1,   r_ij = y_ij - x^{s-1}_i . h_j        (in the element type)
+ *       x^s = the system of trmf_session_smooth with G_i = sum_j omega_ij h_j h_j^T, b_i = sum_j omega_ij y_ij h_j, solved by its
+ *             PCG started from x^{s-1}: the same preconditioner with blocks G_i + (lambdaI + lambdaAR) I from the weighted G_i, the
+ *             same stop rule, rtol and max_iter (and their defaults), one residual replacement per sweep
+ *   W[f ..] = x^sweeps;   the weights reported are those of the last sweep (formed from x^{sweeps-1})
+ * The number of sweeps is fixed.  Each sweep is a majorise-minimise step and every CG iterate lowers the sweep's majoriser, so
+ * J_rob(after) <= J_rob(before) also when a sweep stops at max_iter; such a call still commits, with converged = 0.  c = infinity
+ * minimises J_win of trmf_session_smooth, to rounding and not to the bit (the weighted Grams are summed in another order than the
+ * X phase's).  On dense storage every row gets its own weighted Gram.
+ *
+ * The entries of a row are summed in items of 256 entries (at most 8 items per row: longer rows get longer items), the items of a
+ * row in ascending order.  Blocking, ordered after every run() enqueued before; every rank computes the same rows on its own copy
+ * and ends up with the same bits; repeated calls from the same state give the same bits (no floating-point atomics, fixed
+ * summation orders).  Neither the Gram cache of the X phase nor anything trmf_session_smooth leaves untouched is touched; the
+ * series statistics go stale by the rule of trmf_session_smooth; the recovery snapshot follows the new W.
+ *   scale    NULL (the square root of the resident sigma2 table), or n positive finite values
+ *   out      NULL, or: rows, entries; downweighted = cells with omega < 1 and weight_sum = sum of omega in the last sweep;
+ *            sweeps; iterations = CG steps over all sweeps; converged = 1 only if every sweep's stop test held; residual = that of
+ *            the last sweep; sq_err_before / sq_err_after unweighted, as in TrmfSmoothSums; objective_before / objective_after =
+ *            J_rob with the rows as they were / as they are, in fp64 and a fixed order
+ *   Wnew     NULL, or (rows - first_row) x k reals, row-major: the new rows
+ *   weights  NULL, or the layout of trmf_session_assimilate_robust: one per stored entry of rows first_row .. in CSR order (sparse
+ *            storage, missing != 0), or (rows - first_row) x n row-major (dense storage)
+ * 0 (first_row == rows: nothing to do, zero sums), or -1 with trmf_last_error() and W, the outputs and the session as they were:
+ * everything trmf_session_smooth refuses (the window cap of 1024 rows included) and everything trmf_session_assimilate_robust
+ * refuses (c not positive, sweeps outside 1..64, a scale that is not positive and finite, no scale and no noise table, sparse
+ * storage with missing == 0). */
+typedef struct {
+    uint64_t rows, entries, downweighted;
+    int32_t  sweeps, iterations, converged, reserved;
+    double   residual, weight_sum;
+    double   sq_err_before, sq_err_after;          /* unweighted */
+    double   objective_before, objective_after;    /* J_rob, fp64, fixed order */
+} TrmfRobustSmoothSums;
+TRMF_API int32_t trmf_session_smooth_robust(TrmfSession *s, int32_t first_row, double c, int32_t sweeps,
+                                            const double *scale /* n, or NULL */, double rtol, int32_t max_iter,
+                                            TrmfRobustSmoothSums *out /* or NULL */, void *Wnew /* or NULL */, void *weights /* or NULL */);
+
 /* --- forecast uncertainty: noise fit, predictive standard deviation and interval scores ---------------------------------
  * TRMF read as a linear-Gaussian state-space model (the paper's own reading): y_ij = w_i . h_j + eps_ij with eps_ij ~ N(0, sigma_j^2),
  * every latent dimension t an AR process with innovation variance q_t.  With m the largest lag and T = trmf_session_rows():
