@@ -137,6 +137,52 @@ __device__ __forceinline__ void adapt_walk(const AdaptArgs &a, uint32_t e0, uint
     }
 }
 
+// col (lane c: column c of S, rows s <= c valid) and rr -> lane c's component of (S + lam I)^-1 r: the ridge, the factorisation
+// S + lam I = U^T U in registers with readlane broadcasts, both substitutions through a copy of U in LDS (Us: KMAX x (KMAX + 1),
+// the caller's; the backward pass reads U by rows).  col is destroyed.  bad is raised by a pivot that is not positive and finite.
+// t = min(c, k - 1).  Shared by adapt_series_kernel and adapt_robust_series_kernel (adapt_robust_kernels.hpp).
+template <int KMAX>
+__device__ __forceinline__ real adapt_factor_solve(real (&col)[KMAX], real rr, real lam, bool on, int c, int t, int k, real *Us, bool &bad) {
+    constexpr int SP = KMAX + 1;
+    // the ridge; rows and columns >= k are padded with the identity, so no step needs a guard
+#pragma unroll
+    for (int s = 0; s < KMAX; s++)
+        if (s == c) col[s] = on ? col[s] + lam : real(1);
+#pragma unroll
+    for (int q = 0; q < KMAX; q++) {
+        const real piv = adapt_bcast(col[q], q);
+        bad = bad || !(piv > real(0) && piv < real(INFINITY));
+        const real d = sqrt(piv);
+        const real u = (c == q) ? d : col[q] / d;
+        col[q] = u;
+#pragma unroll
+        for (int s = q + 1; s < KMAX; s++) {
+            col[s] = fma(-adapt_bcast(u, s), u, col[s]);
+            if ((s & 15) == 15) __builtin_amdgcn_sched_barrier(0);       // bound the scalar operands in flight
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (on) {
+#pragma unroll
+        for (int s = 0; s < KMAX; s++)
+            if (s < k) Us[s * SP + c] = s <= c ? col[s] : real(0);
+    }
+    __syncthreads();
+    // column-oriented substitutions, one unknown per lane (assim_chain_kernel)
+    real x = on ? rr : real(0);
+    for (int q = 0; q < k; q++) {                           // U^T z = r
+        const real zq = adapt_bcast(x, q) / Us[q * SP + q];
+        if (c == q) x = zq;
+        else if (c > q) x -= Us[q * SP + t] * zq;
+    }
+    for (int q = k - 1; q >= 0; q--) {                      // U h = z
+        const real xq = adapt_bcast(x, q) / Us[q * SP + q];
+        if (c == q) x = xq;
+        else if (c < q) x -= Us[t * SP + q] * xq;
+    }
+    return x;
+}
+
 template <int NT>
 __global__ __launch_bounds__(64) void adapt_part_kernel(AdaptArgs a) {
     constexpr int KMAX = kTile * NT;
@@ -196,44 +242,9 @@ __global__ __launch_bounds__(64) void adapt_series_kernel(AdaptArgs a) {
             if (s <= c) So[s * k - s * (s - 1) / 2 + c - s] = col[s];
         a.rout[(size_t)j * k + c] = rr;
     }
-    // the ridge; rows and columns >= k are padded with the identity, so no step needs a guard
-#pragma unroll
-    for (int s = 0; s < KMAX; s++)
-        if (s == c) col[s] = on ? col[s] + a.lam : real(1);
     bool bad = false;
-#pragma unroll
-    for (int q = 0; q < KMAX; q++) {
-        const real piv = adapt_bcast(col[q], q);
-        bad = bad || !(piv > real(0) && piv < real(INFINITY));
-        const real d = sqrt(piv);
-        const real u = (c == q) ? d : col[q] / d;
-        col[q] = u;
-#pragma unroll
-        for (int s = q + 1; s < KMAX; s++) {
-            col[s] = fma(-adapt_bcast(u, s), u, col[s]);
-            if ((s & 15) == 15) __builtin_amdgcn_sched_barrier(0);       // bound the scalar operands in flight
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    const real x = adapt_factor_solve<KMAX>(col, rr, a.lam, on, c, t, k, Us, bad);
     if (bad && c == 0) atomicMin(a.flag, j);
-    if (on) {
-#pragma unroll
-        for (int s = 0; s < KMAX; s++)
-            if (s < k) Us[s * SP + c] = s <= c ? col[s] : real(0);
-    }
-    __syncthreads();
-    // column-oriented substitutions, one unknown per lane (assim_chain_kernel)
-    real x = on ? rr : real(0);
-    for (int q = 0; q < k; q++) {                           // U^T z = r
-        const real zq = adapt_bcast(x, q) / Us[q * SP + q];
-        if (c == q) x = zq;
-        else if (c > q) x -= Us[q * SP + t] * zq;
-    }
-    for (int q = k - 1; q >= 0; q--) {                      // U h = z
-        const real xq = adapt_bcast(x, q) / Us[q * SP + q];
-        if (c == q) x = xq;
-        else if (c < q) x -= Us[t * SP + q] * xq;
-    }
     real d = 0;
     if (on) {
         d = fabs(x - a.Hold[(size_t)j * a.KP + cp]);
@@ -243,6 +254,7 @@ __global__ __launch_bounds__(64) void adapt_series_kernel(AdaptArgs a) {
     if (c == 0) a.change[j] = d;
 }
 
+#if !defined(TRMF_UNIT) || TRMF_UNIT == 10    // (adapt_robust_kernels.hpp's unit includes this file for the shared code above)
 // ---- the full-observation forms ------------------------------------------------------------------------------------------------
 // the shared S: one thread per packed element, the new rows in ascending order
 __global__ __launch_bounds__(256) void adapt_full_gram_kernel(AdaptFullArgs a) {
@@ -330,6 +342,7 @@ __global__ __launch_bounds__(256) void adapt_max_kernel(const real *__restrict__
     }
     if (threadIdx.x == 0) *out = sm[0];
 }
+#endif
 #endif
 
 }  // namespace trmf

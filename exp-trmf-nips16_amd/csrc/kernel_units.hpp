@@ -20,12 +20,13 @@
 //   unit_adapt.hip     adapt_series_kernel (4), adapt_part_kernel (4), the full-observation forms: trmf_session_adapt_series
 //   unit_smooth.hip    smooth_ar_kernel, smooth_apply_kernel, smooth_update_kernel, smooth_finish_kernel: the windowed PCG of trmf_session_smooth
 //   unit_smooth_robust.hip  smooth_robust_part_kernel (4), smooth_robust_fold_kernel (4): the weighted Grams of trmf_session_smooth_robust
+//   unit_adapt_robust.hip   adapt_robust_series_kernel (4), adapt_robust_objective_kernel: trmf_session_adapt_series_robust
 //
 // A unit defines TRMF_UNIT before including this file; the non-template kernels of the shared headers are compiled by the main
 // unit only (#if !defined(TRMF_UNIT) around them).
 #pragma once
 
-// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online, 10 online loadings, 11 smoother, 12 robust smoother; the kernels of these families
+// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online, 10 online loadings, 11 smoother, 12 robust smoother, 13 robust online loadings; the kernels of these families
 // have their BODIES only where TRMF_UNIT_BODIES is defined -- the main unit sees declarations, so that it neither compiles them
 // nor runs them through the optimiser as `extern template` would (available_externally bodies: 3 of its 3.5 minutes))
 #if defined(TRMF_UNIT) || defined(TRMF_SINGLE_UNIT)
@@ -65,6 +66,9 @@
 #endif
 #if !defined(TRMF_UNIT) || TRMF_UNIT == 12
 #include "smooth_robust_kernels.hpp"
+#endif
+#if !defined(TRMF_UNIT) || TRMF_UNIT == 13
+#include "adapt_robust_kernels.hpp"     // (includes adapt_kernels.hpp for the shared rank-1 update and factorisation)
 #endif
 #if !defined(TRMF_UNIT)
 #include "cg_persist_args.hpp"     // the declaration only: the body is unit_persist.hip's business
@@ -195,6 +199,11 @@ namespace trmf {
     X void smooth_robust_part_kernel<3>(SmoothRobustArgs); X void smooth_robust_part_kernel<4>(SmoothRobustArgs);            \
     X void smooth_robust_fold_kernel<1>(SmoothRobustArgs); X void smooth_robust_fold_kernel<2>(SmoothRobustArgs);            \
     X void smooth_robust_fold_kernel<3>(SmoothRobustArgs); X void smooth_robust_fold_kernel<4>(SmoothRobustArgs);
+
+// robust online loading updates (adapt_robust_kernels.hpp): the per-series kernel as NT = 1..4 (k <= 64); the objective kernel is not a template
+#define TRMF_UNIT_ADAPT_ROBUST(X)                                                                                            \
+    X void adapt_robust_series_kernel<1>(AdaptRobustArgs); X void adapt_robust_series_kernel<2>(AdaptRobustArgs);            \
+    X void adapt_robust_series_kernel<3>(AdaptRobustArgs); X void adapt_robust_series_kernel<4>(AdaptRobustArgs);
 
 #define TRMF_DEFINE_KERNEL template __global__
 

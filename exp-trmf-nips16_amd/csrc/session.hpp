@@ -1795,6 +1795,94 @@ struct TrmfSessionImpl : SessionXPhase {
         res->max_abs_change = (double)hmx;
         return 0;
     }
+    // ---- robust online loading updates (trmf_session_adapt_series_robust; adapt_robust_kernels.hpp) -----------------------------------
+    // adapt_series() with Huber weights on the entries not yet absorbed (the caller has validated the rank, the storage -- sparse
+    // with missing != 0 --, the state of the tables, c, the sweep count and the n scales, which arrive as host values on every
+    // rank).  One launch of the per-series kernel runs every sweep; one launch of the objective kernel gives J_j before and after.
+    // Everything lands in the inactive generation and in scratch; the generation, the absorbed counts and H move after the one
+    // flag read.  The weights always come back to the host: downweighted and weight_sum are folded from them in series order.
+    struct RobustAdaptResult {
+        uint64_t series = 0, rows = 0, entries = 0, downweighted = 0;
+        double sq_err_before = 0, sq_err_after = 0, max_abs_change = 0, weight_sum = 0, objective_before = 0, objective_after = 0;
+        int bad_series = -1;
+    };
+    int adapt_series_robust(double c, int sweeps, const double *scale, RobustAdaptResult *res, real *Hout, uint64_t *wptr_out, uint32_t *wrows_out,
+                            real *weights_out) {
+        *res = RobustAdaptResult{};
+        if (sync()) return kFail;
+        FillStreamScope fill(stream);
+        const double gam = ad_gamma;
+        const int row0 = ad_rows, m = T - row0;
+        const int in = ad_cur, out = 1 - ad_cur;
+        std::vector<real> hom;
+        if (gam != 1.0) {
+            hom.resize((size_t)std::max(m, 1));
+            for (int i = 0; i < m; i++) hom[i] = (real)std::pow(gam, (double)(T - 1 - (row0 + i)));
+        }
+        const real decay = (real)std::pow(gam, (double)m);
+        std::vector<uint32_t> hstart((size_t)n), hwptr((size_t)n + 1);
+        std::vector<real> hthr((size_t)n);
+        hwptr[0] = 0;
+        for (int j = 0; j < n; j++) {
+            hstart[j] = (uint32_t)(host_col_ptr[j] + ad_cnt[j]);
+            hwptr[j + 1] = hwptr[j] + (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j] - ad_cnt[j]);
+            hthr[j] = (real)c * (real)scale[j];
+        }
+        const size_t nw = hwptr[n];
+        DevBuf<real> Hn, chg, mx, om, thr, wts;
+        DevBuf<uint32_t> d_start, d_wptr, wrw;
+        DevBuf<int> flag;
+        DevBuf<double> errs, obj;
+        SyncStreamOnExit drain(stream);
+        if (Hn.alloc((size_t)n * KP) || chg.alloc(n, false) || mx.alloc(1) || flag.alloc(1, false) || errs.alloc((size_t)4 * std::max(m, 1), false) ||
+            (!hom.empty() && om.upload(hom.data(), hom.size())) || d_start.upload(hstart.data(), hstart.size()) ||
+            d_wptr.upload(hwptr.data(), hwptr.size()) || thr.upload(hthr.data(), hthr.size()) || wts.alloc(std::max<size_t>(nw, 1), false) ||
+            wrw.alloc(std::max<size_t>(nw, 1), false) || obj.alloc((size_t)2 * n, false)) return kFail;
+        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
+        AdaptRobustArgs a{Yc_ptr.p, Yc_idx.p, Yc_val.p, d_start.p, W.p, hom.empty() ? nullptr : om.p, ad_S[in].p, ad_r[in].p, ad_S[out].p, ad_r[out].p,
+                          H.p, Hn.p, chg.p, flag.p, thr.p, d_wptr.p, wts.p, wrw.p, obj.p, decay, (real)lambdaI, row0, n, k, KP, NT, sweeps};
+        if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(adapt_robust_series_kernel<decltype(N)::value>, dim3(n), dim3(64), 0, stream, a); }))
+            return unsupported_rank();
+        hipLaunchKernelGGL(adapt_robust_objective_kernel, dim3(n), dim3(64), 0, stream, a);
+        hipLaunchKernelGGL(adapt_max_kernel, dim3(1), dim3(256), 0, stream, chg.p, n, mx.p);
+        if (m > 0) {   // the squared errors of the absorbed rows with H as it is and as it will be (unweighted; adapt_series' sums)
+            for (int pass = 0; pass < 2; pass++) {
+                AssimErrArgs ea{Yr_ptr.p, Yr_idx.p, Yr_val.p, nullptr, pass ? Hn.p : H.p, W.p, W.p, 0, 0, errs.p + (size_t)2 * m * pass, row0, m, n, KP, 0};
+                hipLaunchKernelGGL(assim_err_kernel, dim3(m), dim3(256), 0, stream, ea);
+            }
+        }
+        TRMF_HIP_CHECK(hipGetLastError());
+        int bad = kAdaptNoBadSeries;
+        real hmx = 0;
+        std::vector<double> herr((size_t)4 * std::max(m, 1), 0.0), hobj((size_t)2 * n);
+        std::vector<real> hwts(nw);
+        std::vector<uint32_t> hwrw(wrows_out ? nw : 0);
+        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(&hmx, mx.p, sizeof(real), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipMemcpyAsync(hobj.data(), obj.p, hobj.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (m > 0) TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, (size_t)4 * m * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (nw) TRMF_HIP_CHECK(hipMemcpyAsync(hwts.data(), wts.p, nw * sizeof(real), hipMemcpyDeviceToHost, stream));
+        if (wrows_out && nw) TRMF_HIP_CHECK(hipMemcpyAsync(hwrw.data(), wrw.p, nw * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (bad != kAdaptNoBadSeries) { res->bad_series = bad; return 0; }
+        if (Hout && download_padded(Hn, Hout, (size_t)n)) return kFail;
+        // ---- commit ----
+        TRMF_HIP_CHECK(hipMemcpyAsync(H.p, Hn.p, (size_t)n * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new H
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        ad_cur = out; ad_rows = T;
+        for (int j = 0; j < n; j++) ad_cnt[j] = (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j]);
+        res->series = (uint64_t)n; res->rows = (uint64_t)m;
+        res->entries = (uint64_t)nw;
+        for (int r = 0; r < m; r++) { res->sq_err_before += herr[2 * r]; res->sq_err_after += herr[(size_t)2 * m + 2 * r]; }
+        for (int j = 0; j < n; j++) { res->objective_before += hobj[2 * j]; res->objective_after += hobj[2 * j + 1]; }       // series order
+        for (size_t e = 0; e < nw; e++) { res->downweighted += hwts[e] < real(1) ? 1u : 0u; res->weight_sum += (double)hwts[e]; }
+        res->max_abs_change = (double)hmx;
+        if (wptr_out) for (int j = 0; j <= n; j++) wptr_out[j] = (uint64_t)hwptr[j];
+        if (wrows_out && nw) std::memcpy(wrows_out, hwrw.data(), nw * sizeof(uint32_t));
+        if (weights_out && nw) std::memcpy(weights_out, hwts.data(), nw * sizeof(real));
+        return 0;
+    }
     // New regularisation weights for the iterations enqueued from now on: the session's own copies (F-solve, Theta-solve, the
     // full-observation path's shared Gram) and the X-side parameter block every X-solve kernel receives by value.
     int set_lambdas(double lI, double lAR, double lLag) {

@@ -796,6 +796,70 @@ int32_t trmf_session_adapt_series(TrmfSession *s, TrmfAdaptSums *out, void *Hnew
     if (!s) { set_error("null session"); return kFail; }
     return adapt_call(s, false, 1.0, out, Hnew);
 }
+// Robust online loading update: the checks of adapt_series and of assimilate_robust's c, sweeps and scale, all on the calling thread
+// before any rank's worker runs; the scales reach every rank as the same host values.
+int32_t trmf_session_adapt_series_robust(TrmfSession *s, double c, int32_t sweeps, const double *scale, TrmfRobustAdaptSums *out, void *Hnew,
+                                         uint64_t *wptr, uint32_t *wrows, void *weights) {
+    if (!s) { set_error("null session"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (f->k > kMaxRank) {
+        set_error("adapt_series_robust: online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
+        return kFail;
+    }
+    if (f->full) {
+        set_error(std::string("adapt_series_robust: ") + (f->dense ? "dense storage" : "sparse storage with missing == 0") +
+                  " is a full-observation form: it keeps ONE shared S for all series, and a weight per cell needs a table per series "
+                  "(sparse storage with missing != 0); use adapt_series");
+        return kFail;
+    }
+    if (!f->ad_exists) { set_error("adapt_series_robust: no series statistics (trmf_session_series_stats_init first)"); return kFail; }
+    if (!f->ad_valid) {
+        set_error("adapt_series_robust: the series statistics are stale: rows they absorbed may have changed (run, rewind, assimilate below the "
+                  "absorbed rows, or a new series transform); initialise them again (trmf_session_series_stats_init)");
+        return kFail;
+    }
+    if (!(c > 0)) { set_error("adapt_series_robust: c must be positive (infinity: the plain update)"); return kFail; }
+    if (sweeps < 1 || sweeps > kAdaptRobustMaxSweeps) {
+        set_error("adapt_series_robust: sweeps " + std::to_string(sweeps) + " outside 1.." + std::to_string(kAdaptRobustMaxSweeps));
+        return kFail;
+    }
+    if (!scale && !f->nz_set) { set_error("adapt_series_robust: no scale given and no noise fitted or set (trmf_session_fit_noise / _set_noise)"); return kFail; }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    std::vector<double> sc((size_t)f->n);
+    if (scale) std::copy(scale, scale + f->n, sc.begin());
+    else {
+        if (HND(s)->rank0([&](TrmfSessionImpl *t) { return t->noise(sc.data(), nullptr); })) return kFail;
+        for (double &v : sc) v = std::sqrt(v);
+    }
+    for (int j = 0; j < f->n; j++)
+        if (!(std::isfinite(sc[j]) && sc[j] > 0)) {
+            set_error("adapt_series_robust: the scale of series " + std::to_string(j) + " is not finite and positive" +
+                      (scale ? "" : " (the square root of the resident sigma2)"));
+            return kFail;
+        }
+    const bool grouped = HND(s)->group != nullptr;
+    std::vector<TrmfSessionImpl::RobustAdaptResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
+    if (HND(s)->all([&](TrmfSessionImpl *t) {
+            const int slot = grouped ? t->comm->rank : 0;
+            const bool lead = slot == 0;
+            return t->adapt_series_robust(c, sweeps, sc.data(), &res[slot], lead ? (real *)Hnew : nullptr, lead ? wptr : nullptr, lead ? wrows : nullptr,
+                                          lead ? (real *)weights : nullptr);
+        })) return kFail;
+    for (const auto &r : res)
+        if (r.bad_series >= 0) {
+            set_error("adapt_series_robust: series " + std::to_string(r.bad_series) + ": a pivot of the weighted S + lambdaI I is not positive and finite "
+                      "(lambdaI == 0 and a series with fewer independent rows than the rank?); nothing was changed");
+            return kFail;
+        }
+    if (out) {
+        const auto &r = res[0];
+        out->series = r.series; out->rows = r.rows; out->entries = r.entries; out->downweighted = r.downweighted;
+        out->sq_err_before = r.sq_err_before; out->sq_err_after = r.sq_err_after; out->max_abs_change = r.max_abs_change;
+        out->weight_sum = r.weight_sum; out->objective_before = r.objective_before; out->objective_after = r.objective_after;
+    }
+    return 0;
+}
 int32_t trmf_session_series_stats_info(TrmfSession *s, int32_t *valid, int32_t *absorbed_rows, double *forget) {
     if (!s) { set_error("null session"); return kFail; }
     const TrmfSessionImpl *f = HND(s)->first();

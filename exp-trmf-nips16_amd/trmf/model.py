@@ -168,7 +168,7 @@ class Model(object):
 
     # ---- online update ----------------------------------------------------------------------------
     def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0,
-                   smooth_back=0, Yback=None, smooth_robust=False):
+                   smooth_back=0, Yback=None, smooth_robust=False, adapt_robust=False):
         """A new ``Model`` grown by the ``Ynew.shape[0]`` timestamps of ``Ynew`` (raw values; a transform of this model is
         applied first): H, the lag weights and the rows this model has stay as they are, every new row of W is solved from its
         own observations and the AR prior of the rows before it (``trmf.online.filter_rows``; the host form of
@@ -185,8 +185,15 @@ class Model(object):
         Together with ``robust_c`` that is refused (the smoother weights every cell fully) unless ``smooth_robust=True``: the
         window is then smoothed on Huber's loss (``trmf.online.robust_smooth_rows`` with the same ``robust_c``, ``scale`` and
         ``robust_sweeps``; the host form of ``Session.update(smooth_robust=True)``), and ``robust_weights`` of the new model are the
-        smoother's, one per cell of the window.  ``smooth_robust=True`` without both ``robust_c`` and ``smooth_back > 0`` is refused."""
+        smoother's, one per cell of the window.  ``smooth_robust=True`` without both ``robust_c`` and ``smooth_back > 0`` is refused.
+        ``adapt_robust=True`` (needs both ``robust_c`` and ``adapt``): the statistics absorb the block with Huber weights of their
+        own (``trmf.online.SeriesStats.absorb_robust`` with the same ``robust_c``, ``scale`` and ``robust_sweeps``; the host form
+        of ``Session.update(adapt_robust=True)``) and ``adapt_weights`` of the new model are its weights; without the flag the
+        cells enter unweighted, as before."""
         from .online import filter_rows, robust_filter_rows, smooth_rows, robust_smooth_rows
+        if adapt_robust and (robust_c is None or not adapt):
+            raise ValueError('assimilate: adapt_robust=True needs both robust_c and adapt (it refits the loadings with the Huber threshold of '
+                             'the robust filter)')
         smooth_back = int(smooth_back)
         if smooth_back < 0:
             raise ValueError('assimilate: smooth_back must not be negative, not {}'.format(smooth_back))
@@ -241,8 +248,12 @@ class Model(object):
                 raise ValueError('assimilate: forget {!r} differs from the {!r} the series statistics were built with'.format(forget, stats.forget))
             if bool(missing) != stats.missing:
                 raise ValueError('assimilate: missing differs from the setting the series statistics were built with')
-            stats = copy.deepcopy(stats).absorb(grown, Ynew)
-            out.H[:] = stats.solve(lambdaI)
+            if adapt_robust:
+                stats = copy.deepcopy(stats)
+                out.H[:], out.adapt_weights = stats.absorb_robust(grown, Ynew, self.H, lambdaI, scale, robust_c, robust_sweeps)
+            else:
+                stats = copy.deepcopy(stats).absorb(grown, Ynew)
+                out.H[:] = stats.solve(lambdaI)
             out.series_stats = stats
         if weights is not None:
             out.robust_weights = weights

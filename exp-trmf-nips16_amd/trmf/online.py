@@ -13,6 +13,8 @@ tests compare against and the host path of ``Model.assimilate``.  ``smooth_rows`
 joint minimiser over a window of tail rows, which also counts the AR penalties of the later rows a row appears in.  ``robust_filter_rows`` is the same filter with Huber weights
 (``trmf_session_assimilate_robust``): a cell far outside its series' residual scale is down-weighted, and the weights are returned.
 ``robust_smooth_rows`` is the smoother on the same Huber loss (``trmf_session_smooth_robust``).
+``series_ridge`` / ``SeriesStats`` refit the loadings H from new rows (``trmf_session_adapt_series``), ``SeriesStats.absorb_robust``
+with Huber weights on the new entries (``trmf_session_adapt_series_robust``; ``robust_series_objective`` is its objective).
 """
 import numpy as np
 import scipy.linalg
@@ -528,3 +530,98 @@ class SeriesStats(object):
         for j in range(self.n):
             H[j] = _ridge_solve(self.S[j if self.missing else 0], self.r[j], lam, j, 'SeriesStats.solve')
         return H
+
+    def _robust_block(self, what, W, Ynew, H):
+        """The guards of ``absorb_robust`` / ``robust_series_objective``: (W, H in the tables' dtype, m, decay, om, W's new rows)."""
+        if not self.missing:
+            raise ValueError('{}: the full-observation form keeps one shared S for all series; a weight per cell needs a table per '
+                             'series (missing=True)'.format(what))
+        W = np.asarray(W)
+        T = W.shape[0]
+        m = T - self.rows
+        if W.shape[1] != self.k or W.dtype != self.dtype:
+            raise ValueError('{}: W is {} {}, {} columns of {} were expected'.format(what, W.shape, W.dtype, self.k, self.dtype))
+        if m < 0 or Ynew.shape[0] != m or Ynew.shape[1] != self.n:
+            raise ValueError('{}: Ynew is {}, rows {}..{} of {} series were expected'.format(what, Ynew.shape, self.rows, T, self.n))
+        H = np.asarray(H)
+        if H.shape != (self.n, self.k):
+            raise ValueError('{}: H is {}, {} were expected'.format(what, H.shape, (self.n, self.k)))
+        dt = self.dtype
+        decay = dt.type(self.forget ** m)
+        om = (self.forget ** (m - 1 - np.arange(m, dtype=np.float64))).astype(dt)
+        return W, H, m, decay, om, W[self.rows:]
+
+    def absorb_robust(self, W, Ynew, H, lambdaI, scale, c=3.0, sweeps=4):
+        """``absorb`` + ``solve`` with Huber weights on the new entries: the specification of ``trmf_session_adapt_series_robust``.
+        Per series ``j``, with ``d = forget^m``, ``om_t`` as in ``absorb``, ``tau_j = c * scale[j]`` and ``h^0 = H[j]`` ::
+
+            for s = 1 .. sweeps:   res_e = y_e - w_t . h^{s-1},   u_e = 1 if |res_e| <= tau_j else tau_j / |res_e|      (e: the new entries)
+                                   S^s = d S_j + sum_e (u_e om_t) w_t w_t^T,   r^s = d r_j + sum_e (u_e om_t) y_e w_t
+                                   h^s = (S^s + lambdaI I)^-1 r^s
+
+        Every sweep restarts from the decayed old tables; only the new entries are reweighted (iteratively reweighted least
+        squares: ``robust_series_objective`` never rises).  The tables become those of the last sweep, so that ``solve(lambdaI)``
+        returns the loadings returned here and a later ``absorb`` continues from them.  One rank-1 update per entry in stored
+        order, all in the dtype of ``W``.  Returns ``(Hnew, weights)``: the weights of the last sweep as a CSC matrix of shape
+        ``m x n`` holding one value per stored entry of ``Ynew`` (a cell stored twice keeps two).  ``c = inf`` is ``absorb`` +
+        ``solve``, bit for bit.  A series without a new entry runs one sweep.  ``ValueError`` in ``absorb``'s cases, for tables
+        without ``missing``, and for ``scale``, ``c``, ``sweeps`` as ``robust_filter_rows``."""
+        W, H, m, decay, om, Wn = self._robust_block('SeriesStats.absorb_robust', W, Ynew, H)
+        scale, c, sweeps = _robust_guards('SeriesStats.absorb_robust', self.n, Ynew, True, scale, c, sweeps)
+        dt = self.dtype
+        H = H.astype(dt)
+        thr = dt.type(c) * scale.astype(dt)
+        Hnew = np.zeros((self.n, self.k), dtype=dt)
+        lam = dt.type(lambdaI)
+        S_out, r_out = np.empty_like(self.S), np.empty_like(self.r)
+        indptr, rows_out, data = np.zeros(self.n + 1, dtype=np.int64), [], []
+        for j, (rows, y) in enumerate(_series_entries(Ynew, True)):
+            y = np.asarray(y, dtype=dt)
+            h = H[j]
+            u = np.ones(len(y), dtype=dt)
+            for _ in range(sweeps if len(y) else 1):
+                res = np.abs(y - Wn[rows].dot(h)) if len(y) else np.zeros(0, dtype=dt)
+                u = np.ones(len(y), dtype=dt)
+                far = res > thr[j]
+                u[far] = thr[j] / res[far]
+                S, r = self.S[j] * decay, self.r[j] * decay
+                for e, t in enumerate(rows):
+                    aw = (u[e] * om[t]) * Wn[t]
+                    S += np.outer(aw, Wn[t])
+                    r += aw * y[e]
+                h = _ridge_solve(S, r, lam, j, 'SeriesStats.absorb_robust')
+            S_out[j], r_out[j], Hnew[j] = S, r, h
+            indptr[j + 1] = indptr[j] + len(y)
+            rows_out.append(np.asarray(rows, dtype=np.int64)); data.append(u)
+        self.S, self.r, self.rows = S_out, r_out, W.shape[0]
+        weights = smat.csc_matrix((np.concatenate(data) if data else np.zeros(0, dtype=dt),
+                                   np.concatenate(rows_out).astype(np.int32) if rows_out else np.zeros(0, dtype=np.int32), indptr.astype(np.int32)), shape=(m, self.n))
+        return Hnew, weights
+
+
+def robust_series_objective(stats, W, Ynew, H, lambdaI, scale, c=3.0):
+    """``sum_j J_j(H[j])`` of ``SeriesStats.absorb_robust`` in float64, for tables ``stats`` that have NOT yet absorbed the rows
+    ``stats.rows .. T-1`` of ``W`` with their observations ``Ynew`` (``objective_before`` / ``objective_after`` of
+    ``trmf_session_adapt_series_robust``) ::
+
+        J_j(h) = h^T (d S_j + lambdaI I) h - 2 h . (d r_j) + sum_e om_t rho_tau(y_e - w_t . h),   rho_tau(x) = x^2 (|x| <= tau), 2 tau |x| - tau^2
+
+    The decayed tables ``d S_j``, ``d r_j`` are formed in the tables' dtype, as the update reads them.  ``c = inf``: the weighted
+    least-squares objective of ``absorb`` + ``solve`` (up to the constant ``sum y^2`` of the history)."""
+    W, H, m, decay, om, Wn = stats._robust_block('robust_series_objective', W, Ynew, H)
+    scale, c, _ = _robust_guards('robust_series_objective', stats.n, Ynew, True, scale, c, 1)
+    tau = c * scale
+    lam = float(stats.dtype.type(lambdaI))
+    H64, W64 = np.asarray(H, dtype=np.float64), np.asarray(Wn, dtype=np.float64)
+    total = 0.0
+    for j, (rows, y) in enumerate(_series_entries(Ynew, True)):
+        h = H64[j]
+        S, r = (stats.S[j] * decay).astype(np.float64), (stats.r[j] * decay).astype(np.float64)
+        J = float(h.dot(S.dot(h)) + lam * h.dot(h) - 2.0 * h.dot(r))
+        if len(y):
+            res = np.abs(np.asarray(y, dtype=np.float64) - W64[rows].dot(h))
+            with np.errstate(invalid='ignore'):
+                rho = np.where(res > tau[j], 2.0 * tau[j] * res - tau[j] * tau[j], res * res)
+            J += float((om[rows].astype(np.float64) * rho).sum())
+        total += J
+    return total

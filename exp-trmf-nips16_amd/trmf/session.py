@@ -94,6 +94,17 @@ class TrmfAdaptSums(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TrmfRobustAdaptSums(ctypes.Structure):
+    """Sums of a robust online loading update (include/trmf_abi.h): those of ``TrmfAdaptSums``, the number of down-weighted
+    entries and the sum of the weights of the last sweep, the Huber objective ``sum_j J_j`` before / after."""
+    _fields_ = [('series', c_uint64), ('rows', c_uint64), ('entries', c_uint64), ('downweighted', c_uint64), ('sq_err_before', c_double),
+                ('sq_err_after', c_double), ('max_abs_change', c_double), ('weight_sum', c_double), ('objective_before', c_double),
+                ('objective_after', c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class TrmfNoiseStats(ctypes.Structure):
     """Summary of a noise fit (include/trmf_abi.h)."""
     _fields_ = [('pooled_sigma2', c_double), ('sigma2_min', c_double), ('sigma2_max', c_double), ('series_pooled', c_uint64),
@@ -195,6 +206,10 @@ def bind(lib):
         lib.trmf_session_adapt_series.argtypes = [c_void_p, POINTER(TrmfAdaptSums), c_void_p]; lib.trmf_session_adapt_series.restype = c_int32
         lib.trmf_session_series_stats_info.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_double)]
         lib.trmf_session_series_stats_info.restype = c_int32
+    if hasattr(lib, 'trmf_session_adapt_series_robust'):      # (absent from libraries built before the robust online loading updates)
+        lib.trmf_session_adapt_series_robust.argtypes = [c_void_p, c_double, c_int32, c_void_p, POINTER(TrmfRobustAdaptSums), c_void_p, c_void_p,
+                                                         c_void_p, c_void_p]
+        lib.trmf_session_adapt_series_robust.restype = c_int32
     if hasattr(lib, 'trmf_session_fit_noise'):        # (absent from libraries built before the forecast uncertainty)
         lib.trmf_session_fit_noise.argtypes = [c_void_p, POINTER(TrmfNoiseStats)]; lib.trmf_session_fit_noise.restype = c_int32
         lib.trmf_session_noise.argtypes = [c_void_p, c_void_p, c_void_p]; lib.trmf_session_noise.restype = c_int32
@@ -435,7 +450,7 @@ class Session(object):
         into them (``S <- forget^m S + sum_new forget^(rows-1-t) w_t w_t^T`` with W as it is now, ``r`` likewise) and every row of H
         is refitted, ``h_j = (S_j + lambdaI I)^-1 r_j`` (``trmf.online.series_ridge`` is the same computation in NumPy, a direct
         sum).  W and the lag weights stay.  Huber weights of ``assimilate_robust`` are not part of the statistics: the cells enter
-        unweighted.  Returns ``{'series', 'rows', 'entries', 'sq_err_before', 'sq_err_after', 'max_abs_change'}``, or ``(sums,
+        unweighted (``adapt_series_robust`` is the weighted update).  Returns ``{'series', 'rows', 'entries', 'sq_err_before', 'sq_err_after', 'max_abs_change'}``, or ``(sums,
         Hnew)`` with ``return_loadings``.  A refused call (no statistics, or stale ones after ``run``, ``rewind``, ``assimilate``
         below the absorbed rows or a new transform; rank above 64; a series whose system is not positive definite, possible only
         with ``lambdaI == 0``) raises and leaves the session as it was."""
@@ -445,13 +460,53 @@ class Session(object):
                     'trmf_session_adapt_series')
         return (sums.as_dict(), Hnew) if return_loadings else sums.as_dict()
 
+    def adapt_series_robust(self, c=3.0, sweeps=4, scale=None, return_loadings=False, return_weights=False):
+        """``adapt_series`` with Huber weights on the entries it absorbs (``trmf.online.SeriesStats.absorb_robust`` is the same
+        statement in NumPy): over ``sweeps`` rounds every new entry whose residual against the loadings of the round before lies
+        beyond ``c * scale[j]`` enters ``S_j`` and ``r_j`` with the weight ``c * scale[j] / |r|`` instead of 1; every round restarts
+        from the decayed old tables, and the last round's tables and loadings are kept.  ``c``, ``sweeps``, ``scale`` as for
+        ``assimilate_robust``.  The weights are this call's own (residuals against H with W as it is now), not the filter's.
+        Sparse storage with ``missing`` only.  Returns ``{'series', 'rows', 'entries', 'downweighted', 'sq_err_before',
+        'sq_err_after', 'max_abs_change', 'weight_sum', 'objective_before', 'objective_after'}`` (the objectives:
+        ``trmf.robust_series_objective``), followed by ``Hnew`` with ``return_loadings`` and by the last sweep's weights with
+        ``return_weights``: a ``scipy.sparse.csc_matrix`` of shape (rows absorbed) x n with one value per absorbed entry (a cell
+        stored twice keeps two).  A refused call (everything ``adapt_series`` refuses; no scale and no resident noise; a scale that
+        is not finite and positive; ``c`` not positive; ``sweeps`` outside 1..64; dense storage or no ``missing``, which keep one
+        shared S) raises and leaves the session as it was."""
+        dt = self.model.W.dtype
+        n = self.model.n
+        sc = None
+        if scale is not None:
+            sc = np.asarray(scale, dtype=np.float64)
+            if sc.ndim == 0:
+                sc = np.full(n, float(sc))
+            if sc.shape != (n,):
+                raise ValueError('adapt_series_robust: scale has shape {}, one value per series ({}) was expected'.format(sc.shape, n))
+            sc = np.ascontiguousarray(sc)
+        sums = TrmfRobustAdaptSums()
+        Hnew = np.empty((n, self.model.k), dtype=dt) if return_loadings else None
+        row0 = self.series_stats_info()['absorbed_rows']
+        m = max(self.rows() - row0, 0)
+        wptr = wrows = weights = None
+        if return_weights:
+            cap = int(self._stored[row0:].sum()) if self._stored is not None and m else 0
+            wptr, wrows, weights = np.zeros(n + 1, dtype=np.uint64), np.zeros(cap, dtype=np.uint32), np.ones(cap, dtype=dt)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        self._check(self.lib.trmf_session_adapt_series_robust(self.handle, float(c), int(sweeps), ptr(sc), byref(sums), ptr(Hnew), ptr(wptr), ptr(wrows),
+                                                              ptr(weights)), 'trmf_session_adapt_series_robust')
+        out = (sums.as_dict(),) + ((Hnew,) if return_loadings else ())
+        if return_weights:
+            out += (smat.csc_matrix((weights, wrows.astype(np.int64) - row0, wptr.astype(np.int64)), shape=(m, n)),)
+        return out if len(out) > 1 else out[0]
+
     def series_stats_info(self):
         """``{'valid', 'stale', 'absorbed_rows', 'forget'}`` of the resident series statistics (absent ones: neither valid nor stale)."""
         v, rows, g = c_int32(0), c_int32(0), c_double(1.0)
         self._check(self.lib.trmf_session_series_stats_info(self.handle, byref(v), byref(rows), byref(g)), 'trmf_session_series_stats_info')
         return {'valid': v.value == 1, 'stale': v.value == -1, 'absorbed_rows': int(rows.value), 'forget': float(g.value)}
 
-    def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0, smooth_back=0, smooth_robust=False):
+    def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0, smooth_back=0, smooth_robust=False,
+               adapt_robust=False):
         """Absorb the new timestamps ``Ynew`` (as for ``append_rows``): append them, assimilate the new block, run ``iters``
         ALS iterations if asked for.  ``self.model`` is replaced by a host model of ``rows()`` timestamps (H, lag weights, lag
         set and transform carried over; its arrays are filled by the next ``download()``).  Returns the sums of ``assimilate``;
@@ -463,10 +518,15 @@ class Session(object):
         weights every cell fully and would undo the Huber weights) unless ``smooth_robust=True`` is passed: the back-smoothing
         is then ``smooth_robust`` with the same ``robust_c``, ``scale`` and ``robust_sweeps``.  ``smooth_robust=True`` without both
         ``robust_c`` and ``smooth_back > 0`` is refused.  ``smooth_back`` with ``adapt`` is refused: the rows before the block are the
-        ones the series statistics have absorbed."""
+        ones the series statistics have absorbed.  Under ``robust_c`` the loading update of ``adapt`` still takes every cell
+        unweighted unless ``adapt_robust=True`` is passed: the block's loading update is then ``adapt_series_robust`` with the same
+        ``robust_c``, ``scale`` and ``robust_sweeps``.  ``adapt_robust=True`` without both ``robust_c`` and ``adapt`` is refused."""
         smooth_back = int(smooth_back)
         if smooth_back < 0:
             raise ValueError('update: smooth_back must not be negative, not {}'.format(smooth_back))
+        if adapt_robust and (robust_c is None or not adapt):
+            raise ValueError('update: adapt_robust=True needs both robust_c and adapt (it refits the loadings with the Huber threshold of '
+                             'the robust filter)')
         if smooth_robust and (robust_c is None or smooth_back <= 0):
             raise ValueError('update: smooth_robust=True needs both robust_c and smooth_back > 0 (it back-smooths with the Huber weights '
                              'of the robust filter)')
@@ -492,7 +552,10 @@ class Session(object):
         if smooth_back > 0:
             first = max(before - smooth_back, self._reach())
             sums['smooth'] = self.smooth_robust(first, robust_c, robust_sweeps, scale) if smooth_robust else self.smooth(first)
-        adapted = self.adapt_series() if adapt else None
+        if adapt_robust:
+            adapted = self.adapt_series_robust(robust_c, robust_sweeps, scale)
+        else:
+            adapted = self.adapt_series() if adapt else None
         if iters:
             self.run(int(iters))
         return (sums, adapted) if adapt else sums

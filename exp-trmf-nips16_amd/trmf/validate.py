@@ -102,7 +102,10 @@ def _score_windows_on_device(Y, lag_set, k, cuts, window_size, seed, hyper, max_
                     else:
                         sess.smooth(first)
                 if adapt is not None:     # ... and the loadings follow
-                    sess.adapt_series()
+                    if adapt.get('adapt_robust'):
+                        sess.adapt_series_robust(robust['robust_c'], robust['robust_sweeps'])
+                    else:
+                        sess.adapt_series()
             else:
                 sess.run(max_iter)
                 if assimilate and adapt is not None:
@@ -133,7 +136,8 @@ def _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, tr
 def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5, lambdaAR=50, lambdaLag=0.5,
                      max_iter=20, missing=True, threshold=0, transform=None, threads=16, verbose=0, seed=0,
                      resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False, update='retrain', interval_level=None,
-                     robust_c=None, robust_sweeps=4, adapt_series=False, forget=1.0, smooth_back=0, smooth_robust=False):
+                     robust_c=None, robust_sweeps=4, adapt_series=False, forget=1.0, smooth_back=0, smooth_robust=False,
+                     adapt_robust=False):
     """``interval_level`` (e.g. 0.9; needs ``forecast_on_device=True``): every window also fits the noise of its trained model and
     scores the predictive distribution of its forecast on the device; the result is ``(Metrics, IntervalMetrics)``, the ``Metrics``
     being exactly those of the call without it.
@@ -151,6 +155,9 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
     a forecast starts from also count the rows after them; 0 leaves the filter's rows.
     ``smooth_robust=True`` (needs both ``robust_c`` and ``smooth_back > 0``): the pair is accepted and the back-smoothing is
     ``Session.smooth_robust`` with the same ``robust_c`` and ``robust_sweeps``, on Huber's loss like the filter before it.
+    ``adapt_robust=True`` (needs both ``robust_c`` and ``adapt_series``): the loadings are refitted by ``Session.adapt_series_robust``
+    with the same ``robust_c`` and ``robust_sweeps``, so that a spiked cell is kept out of H as it is kept out of W; without it the
+    loading update takes every cell unweighted.
     ``lambdaLagL1`` / ``lag_refit``: sparse lag weights (``Session.set_lag_penalty``) on every path.
     ``forecast_on_device=True`` keeps the forecasts and their scoring on the device as well (one session, no download and no
     host model per window); it needs the resident path and a dense ``Y``, and says so where that does not hold."""
@@ -177,6 +184,10 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
         if not (0.0 < float(forget) <= 1.0):
             raise ValueError('adapt_series: forget must lie in (0, 1], not {!r}'.format(forget))
         adapt = dict(adapt=True, forget=float(forget))
+    if adapt_robust:
+        if robust_c is None or not adapt_series:
+            raise ValueError('adapt_robust=True needs both robust_c and adapt_series (it refits the loadings with the Huber threshold of the robust filter)')
+        adapt['adapt_robust'] = True        # (Session.update's keyword)
     smooth_back = int(smooth_back)
     if smooth_back < 0:
         raise ValueError('smooth_back must not be negative, not {}'.format(smooth_back))

@@ -406,7 +406,7 @@ TRMF_API int32_t trmf_session_assimilate_robust(TrmfSession *s, int32_t first_ro
  *   active series transform).  H is replaced: forecast*, assimilate*, download, objective and the next run see the new one.  A
  *   series without a stored entry gets h_j = 0 when lambdaI > 0.  m == 0 is allowed (H refitted from the tables as they are,
  *   for example after trmf_session_set_lambdas).  Under trmf_session_assimilate_robust the cells still enter these sums
- *   UNWEIGHTED: the Huber weights are not part of the statistics.
+ *   UNWEIGHTED: the Huber weights are not part of the statistics (trmf_session_adapt_series_robust below is the weighted update).
  * trmf_session_series_stats_info: valid = 1 (usable), 0 (absent), -1 (stale); the rows absorbed; gamma.
  *
  * The tables go stale when a row they absorbed may have changed: trmf_session_run, trmf_session_rewind, trmf_session_assimilate /
@@ -432,6 +432,41 @@ typedef struct {
 TRMF_API int32_t trmf_session_series_stats_init(TrmfSession *s, double forget);
 TRMF_API int32_t trmf_session_adapt_series(TrmfSession *s, TrmfAdaptSums *out /* or NULL */, void *Hnew /* or NULL: n x k, row-major */);
 TRMF_API int32_t trmf_session_series_stats_info(TrmfSession *s, int32_t *valid, int32_t *absorbed_rows, double *forget);
+
+/* --- robust online loading updates: Huber-weighted refit of H ---------------------------------------------------------------
+ * trmf_session_adapt_series with Huber weights on the entries it absorbs: the robust form of the loading update, as
+ * trmf_session_assimilate_robust is of the filter.  Sparse storage with missing != 0 only (the form with per-series tables).  For
+ * series j let (S_j, r_j) be the tables, m = rows - absorbed rows, d = gamma^m, om_t = gamma^(rows - 1 - t), E_j the stored entries
+ * of column j not yet absorbed in stored order (a cell stored twice is two observations), tau_j = c scale_j, h^0 = H[j]:
+ *   for s = 1 .. sweeps:   res_e = y_e - w_t . h^{s-1},   u_e = 1 if |res_e| <= tau_j else tau_j / |res_e|          (e in E_j)
+ *                          S^s = d S_j + sum_e (u_e om_t) w_t w_t^T,   r^s = d r_j + sum_e (u_e om_t) y_e w_t
+ *                          h^s = (S^s + lambdaI I)^-1 r^s                                  (Cholesky, as adapt_series)
+ *   commit S^sweeps, r^sweeps, H[j] = h^sweeps; report the u_e of the last sweep
+ * Every sweep restarts from the decayed OLD tables; only the new entries are reweighted: iteratively reweighted least squares on
+ *   J_j(h) = h^T (d S_j + lambdaI I) h - 2 h . (d r_j) + sum_e om_t rho_tau(y_e - w_t . h),   rho_tau(x) = x^2 (|x| <= tau), 2 tau |x| - tau^2
+ * so sum_j J_j never rises from one sweep to the next.  The committed tables and H keep h_j = (S_j + lambdaI I)^-1 r_j: a later
+ * adapt_series or another robust call continues from them unchanged.  The weights are this call's own: residuals against the
+ * loadings with W as it is now, not the filter's weights (per row, against the prior row).  A series with no new entry runs one
+ * sweep (nothing to reweight).  c = +inf is adapt_series: the same operations in the same order, the same bits.
+ *   c, sweeps, scale   as for trmf_session_assimilate_robust (c > 0, +inf allowed; sweeps in 1..64; n positive finite values, or
+ *                      NULL for the square roots of the resident sigma2 table)
+ *   out      NULL, or: the fields of TrmfAdaptSums (the squared errors unweighted); downweighted = entries with u_e < 1 and
+ *            weight_sum = sum u_e, of the last sweep; objective_before / objective_after = sum_j J_j at h^0 / at h^sweeps, in fp64,
+ *            summed in series order
+ *   Hnew     NULL, or n x k reals, row-major
+ *   wptr, wrows, weights   each NULL, or the weights series-major: n + 1 offsets; per new entry its timestamp (row number); the last
+ *            sweep's u_e in the element type.  sum_j |E_j| = out->entries values.
+ * Generations, staleness, blocking, sameness across ranks and calls, and what stays untouched are adapt_series'.  0, or -1 with
+ * trmf_last_error() and H, the tables, the outputs and the session as they were: whatever adapt_series refuses; c not positive,
+ * sweeps outside 1..64, a scale that is not finite and positive, no scale and no resident noise; the full-observation forms (dense
+ * storage, sparse storage with missing == 0), which keep one shared S -- the message says so. */
+typedef struct {
+    uint64_t series, rows, entries, downweighted;
+    double sq_err_before, sq_err_after, max_abs_change, weight_sum, objective_before, objective_after;
+} TrmfRobustAdaptSums;
+TRMF_API int32_t trmf_session_adapt_series_robust(TrmfSession *s, double c, int32_t sweeps, const double *scale /* n, or NULL */,
+                                                  TrmfRobustAdaptSums *out /* or NULL */, void *Hnew /* or NULL */, uint64_t *wptr /* or NULL: n + 1 */,
+                                                  uint32_t *wrows /* or NULL */, void *weights /* or NULL */);
 
 /* --- fixed-interval smoother of the online rows: windowed preconditioned conjugate gradients -----------------------------
  * The filters above fit row i to its own observations and the AR prior of the rows BEFORE it; the AR penalties of the later rows
