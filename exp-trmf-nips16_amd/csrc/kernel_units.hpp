@@ -21,12 +21,13 @@
 //   unit_smooth.hip    smooth_ar_kernel, smooth_apply_kernel, smooth_update_kernel, smooth_finish_kernel: the windowed PCG of trmf_session_smooth
 //   unit_smooth_robust.hip  smooth_robust_part_kernel (4), smooth_robust_fold_kernel (4): the weighted Grams of trmf_session_smooth_robust
 //   unit_adapt_robust.hip   adapt_robust_series_kernel (4), adapt_robust_objective_kernel: trmf_session_adapt_series_robust
+//   unit_slide.hip     csc_slide_count_kernel, csc_slide_kernel, series_downdate_kernel (4): the sliding window of trmf_session_slide
 //
 // A unit defines TRMF_UNIT before including this file; the non-template kernels of the shared headers are compiled by the main
 // unit only (#if !defined(TRMF_UNIT) around them).
 #pragma once
 
-// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online, 10 online loadings, 11 smoother, 12 robust smoother, 13 robust online loadings; the kernels of these families
+// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online, 10 online loadings, 11 smoother, 12 robust smoother, 13 robust online loadings, 14 sliding window; the kernels of these families
 // have their BODIES only where TRMF_UNIT_BODIES is defined -- the main unit sees declarations, so that it neither compiles them
 // nor runs them through the optimiser as `extern template` would (available_externally bodies: 3 of its 3.5 minutes))
 #if defined(TRMF_UNIT) || defined(TRMF_SINGLE_UNIT)
@@ -69,6 +70,9 @@
 #endif
 #if !defined(TRMF_UNIT) || TRMF_UNIT == 13
 #include "adapt_robust_kernels.hpp"     // (includes adapt_kernels.hpp for the shared rank-1 update and factorisation)
+#endif
+#if !defined(TRMF_UNIT) || TRMF_UNIT == 14
+#include "slide_kernels.hpp"            // (includes adapt_kernels.hpp for the shared rank-1 update)
 #endif
 #if !defined(TRMF_UNIT)
 #include "cg_persist_args.hpp"     // the declaration only: the body is unit_persist.hip's business
@@ -204,6 +208,11 @@ namespace trmf {
 #define TRMF_UNIT_ADAPT_ROBUST(X)                                                                                            \
     X void adapt_robust_series_kernel<1>(AdaptRobustArgs); X void adapt_robust_series_kernel<2>(AdaptRobustArgs);            \
     X void adapt_robust_series_kernel<3>(AdaptRobustArgs); X void adapt_robust_series_kernel<4>(AdaptRobustArgs);
+
+// sliding window (slide_kernels.hpp): the downdate of the loading statistics as NT = 1..4 (k <= 64); the compaction kernels are not templates
+#define TRMF_UNIT_SLIDE(X)                                                                                                   \
+    X void series_downdate_kernel<1>(DowndateArgs); X void series_downdate_kernel<2>(DowndateArgs);                          \
+    X void series_downdate_kernel<3>(DowndateArgs); X void series_downdate_kernel<4>(DowndateArgs);
 
 #define TRMF_DEFINE_KERNEL template __global__
 

@@ -430,12 +430,76 @@ struct TrmfSessionImpl : SessionXPhase {
         if ((uint64_t)(T0 + Tn + 1) >= (1ull << 24) || (uint64_t)(T0 + Tn + 1) * KP * sizeof(real) > 0xffffffffull ||
             nnz + Yn->nnz >= (1ull << 32)) { set_error("append_rows: problem would exceed 32-bit device indices"); return kFail; }
         if (Tn <= 0) return 0;
+        return slide(Yn, 0, false, nullptr);       // the growing case of the sliding window: one code path, the same bits
+    }
+
+    // ---- the sliding window (trmf_session_slide; slide_kernels.hpp) ---------------------------------------------------------------
+    // Appends Ynew (as append_rows does; may be absent) and retires the `retire` oldest timestamps in ONE new generation of storage:
+    // the CSR side, a dense Y (and its raw copy under a transform) and W are suffix copies, the CSC side is compacted stably per
+    // column with the block's entries behind the survivors, the held-out set is compacted by the same kernel, and -- downdate -- the
+    // loading statistics lose the retired entries' terms (read from the storage and the W of BEFORE the slide, written to the
+    // inactive generation).  Afterwards the session is the one trmf_session_create would build from the retained entries in their
+    // stored order, W[retire:] + the block's AR roll-out and the current H, Theta, weights and transform.  Failure-atomic like
+    // append_rows: everything is built in locals and committed at the end.  slide_refusal() is the validation, run by the entry
+    // point on the calling thread before any rank's worker starts (a refused call must not break the barrier of a TRMF_DEVICES group).
+    struct SlideResult { uint64_t rows_retired = 0, entries_retired = 0, rows_appended = 0, entries_appended = 0, rows = 0, entries = 0; };
+    std::string slide_refusal(const PyMatrix *Yn, int retire, int downdate) const {
+        if (retire < 0) return "slide: retire must not be negative";
+        if (downdate != 0 && downdate != 1) return "slide: downdate_stats must be 0 or 1";
+        const int64_t Tn = Yn ? (int64_t)Yn->rows : 0;
+        if (Yn) {
+            if ((int)Yn->cols != n) return "slide: column count differs from the session's";
+            if ((Yn->type != TRMF_SPARSE) != dense) return "slide: storage class (sparse/dense) differs from the session's";
+        }
+        if (retire > T) return "slide: cannot retire " + std::to_string(retire) + " rows, the session holds " + std::to_string(T) + " (rows of the block itself cannot be retired)";
+        const int64_t T1 = (int64_t)T + Tn - retire;
+        if (T1 < (int64_t)midx + 1)
+            return "slide: retiring " + std::to_string(retire) + " rows would leave " + std::to_string(T1) + ", fewer than the largest lag + 1 = " + std::to_string(midx + 1);
+        const uint64_t gone = dense ? 0 : host_row_ptr[(size_t)retire] - host_row_ptr[0];
+        if ((uint64_t)(T1 + 1) >= (1ull << 24) || (uint64_t)(T1 + 1) * KP * sizeof(real) > 0xffffffffull || (!dense && nnz - gone + (Yn ? Yn->nnz : 0) >= (1ull << 32)))
+            return "slide: problem would exceed 32-bit device indices";
+        if (downdate) {
+            if (full) return "slide: downdate_stats needs per-series statistics (sparse storage with missing != 0); the full-observation forms share one S";
+            if (!ad_exists || !ad_valid) return "slide: downdate_stats without valid series statistics (trmf_session_series_stats_init)";
+        }
+        return "";
+    }
+    void heldout_geometry(uint64_t m, int *nb, uint64_t *chunk) const {
+        // equal contiguous chunks, a multiple of one workgroup step each: the work of a workgroup does not depend on row lengths
+        *nb = (int)std::max<uint64_t>(1, std::min<uint64_t>(kHoMaxBlocks, (m + 255) / 256));
+        *chunk = ((m + *nb - 1) / *nb + kHoStep - 1) / kHoStep * kHoStep;
+        if (*chunk == 0) *chunk = kHoStep;
+        *nb = (int)std::max<uint64_t>(1, (m + *chunk - 1) / *chunk);
+    }
+    // counts of the columns' survivors -> host (retire > 0; the caller has filled the `o*` fields of the arguments)
+    int slide_count(SlideArgs &sa, DevBuf<uint32_t> &d_kept, std::vector<uint32_t> &kept) {
+        kept.assign((size_t)sa.ncols, 0u);
+        if (sa.ncols <= 0) return 0;
+        if (d_kept.alloc((size_t)sa.ncols, false)) return kFail;
+        sa.kept = d_kept.p;
+        hipLaunchKernelGGL(csc_slide_count_kernel, dim3((sa.ncols + 3) / 4), dim3(256), 0, stream, sa);
+        TRMF_HIP_CHECK(hipGetLastError());
+        // through the library's pinned staging when it is to be had (a copy into pageable memory is staged by the runtime)
+        const size_t bytes = kept.size() * sizeof(uint32_t);
+        std::unique_lock<std::mutex> lease;
+        unsigned char *pin = HostStager::current().staging(bytes, lease);
+        TRMF_HIP_CHECK(hipMemcpyAsync(pin ? (void *)pin : (void *)kept.data(), d_kept.p, bytes, hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (pin) std::memcpy(kept.data(), pin, bytes);
+        return 0;
+    }
+    int slide(const PyMatrix *Yn, int retire, bool downdate, SlideResult *res) {
+        const int Tn = Yn ? (int)Yn->rows : 0, T0 = T, Tk = T0 - retire, T1 = Tk + Tn;
+        SlideResult out{};
+        out.rows = (uint64_t)T0; out.entries = nnz;
+        if (Tn <= 0 && retire == 0) { if (res) *res = out; return 0; }
         FillStreamScope fill(stream);
         TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        const int T1 = T0 + Tn;
-        {   // the grown generation of buffers in ONE slab (the pool returns the previous generation's slab once it is wholly free)
+        const uint64_t nzn = (Yn && !dense) ? Yn->nnz : 0;
+        const uint64_t cut = dense ? 0 : host_row_ptr[(size_t)retire];        // CSR rows are contiguous: the retired entries are a prefix
+        {   // the new generation of buffers in ONE slab (the pool returns the previous generation's slab once it is wholly free)
             const int Tsave = T; const uint64_t nzsave = nnz;
-            T = T1; nnz = dense ? (uint64_t)T1 * n : nnz + Yn->nnz;
+            T = T1; nnz = dense ? (uint64_t)T1 * n : nnz - cut + nzn;
             const size_t fp = footprint_estimate();
             T = Tsave; nnz = nzsave;
             DevicePool::current().reserve(fp);
@@ -444,78 +508,163 @@ struct TrmfSessionImpl : SessionXPhase {
         // the session only after every allocation, copy and kernel of the step has succeeded; a failed call leaves the
         // session exactly as it was.
         std::vector<uint64_t> new_row_ptr, new_col_ptr;
+        std::vector<uint32_t> kept;                   // sparse storage, retire > 0: the survivors of every column
         uint64_t new_nnz = nnz;
         double new_ysq = ysq_acc;
-        DevBuf<uint32_t> ptr2, idx2, cptr2, cidx2; DevBuf<real> val2, cval2, tn2, nt2, raw2, W2;
+        DevBuf<uint32_t> ptr2, idx2, cptr2, cidx2, hrow2, hcol2; DevBuf<real> val2, cval2, tn2, nt2, raw2, W2, hval2;
+        uint64_t ho_m2 = ho_m;
+        const bool ho_slide = ho_set && retire > 0 && ho_m > 0;
+        const bool ad_down = downdate && retire > 0 && retire <= ad_rows;      // (retiring past the absorbed rows leaves the tables stale)
         SyncStreamOnExit drain(stream);
         if (!dense) {
-            const uint64_t nz0 = nnz, nzn = Yn->nnz, nz1 = nz0 + nzn;
-            // CSR: old rows keep their place, the block's rows follow
-            new_row_ptr = host_row_ptr;
-            for (int i = 1; i <= Tn; i++) new_row_ptr.push_back(nz0 + Yn->row_ptr[i]);
+            const uint64_t nz0 = nnz, nzk = nz0 - cut, nz1 = nzk + nzn;
+            // CSR: the retained rows move to the front with their pointers rebased, the block's rows follow
+            new_row_ptr.reserve((size_t)T1 + 1);
+            for (int i = retire; i <= T0; i++) new_row_ptr.push_back(host_row_ptr[(size_t)i] - cut);
+            for (int i = 1; i <= Tn; i++) new_row_ptr.push_back(nzk + Yn->row_ptr[i]);
             if (upload_ptr32(ptr2, (const size_t *)new_row_ptr.data(), (size_t)T1 + 1) || idx2.alloc(nz1, false) || val2.alloc(nz1, false)) return kFail;
-            TRMF_HIP_CHECK(hipMemcpyAsync(idx2.p, Yr_idx.p, nz0 * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-            TRMF_HIP_CHECK(hipMemcpyAsync(val2.p, Yr_val.p, nz0 * sizeof(real), hipMemcpyDeviceToDevice, stream));
-            if (nzn) {
-                TRMF_HIP_CHECK(hipMemcpyAsync(idx2.p + nz0, Yn->col_idx, nzn * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                TRMF_HIP_CHECK(hipMemcpyAsync(val2.p + nz0, Yn->val_t, nzn * sizeof(real), hipMemcpyHostToDevice, stream));
+            if (nzk) {
+                TRMF_HIP_CHECK(hipMemcpyAsync(idx2.p, Yr_idx.p + cut, nzk * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+                TRMF_HIP_CHECK(hipMemcpyAsync(val2.p, Yr_val.p + cut, nzk * sizeof(real), hipMemcpyDeviceToDevice, stream));
             }
-            // CSC: column j = its old entries, then the block's entries of that column (timestamps shifted by T0)
-            new_col_ptr = host_col_ptr;
+            if (nzn) {
+                TRMF_HIP_CHECK(hipMemcpyAsync(idx2.p + nzk, Yn->col_idx, nzn * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+                TRMF_HIP_CHECK(hipMemcpyAsync(val2.p + nzk, Yn->val_t, nzn * sizeof(real), hipMemcpyHostToDevice, stream));
+            }
+            // CSC: column j = its surviving entries in their stored order (timestamps reduced by `retire`), then the block's entries
+            // of that column (timestamps shifted to follow the retained rows)
+            SlideArgs sa{};
+            sa.optr = Yc_ptr.p; sa.oidx = Yc_idx.p; sa.oval = Yc_val.p; sa.ncols = n; sa.retire = (uint32_t)retire; sa.shift = (uint32_t)Tk;
+            DevBuf<uint32_t> d_kept;
+            if (retire > 0) { if (slide_count(sa, d_kept, kept)) return kFail; }
+            else { kept.resize((size_t)n); for (int j = 0; j < n; j++) kept[j] = (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j]); }
+            new_col_ptr.assign((size_t)n + 1, 0);
             std::vector<uint32_t> np32((size_t)n + 1);
-            for (int j = 0; j <= n; j++) { new_col_ptr[j] += Yn->col_ptr[j]; np32[j] = (uint32_t)new_col_ptr[j]; }
+            for (int j = 0; j < n; j++) new_col_ptr[j + 1] = new_col_ptr[j] + kept[j] + (Yn ? (uint64_t)(Yn->col_ptr[j + 1] - Yn->col_ptr[j]) : 0);
+            for (int j = 0; j <= n; j++) np32[j] = (uint32_t)new_col_ptr[j];
+            if (new_col_ptr[n] != nz1) { set_error("slide: the two orientations of Y do not hold the same entries"); return kFail; }
             DevBuf<uint32_t> wptr, widx; DevBuf<real> wval;
             SyncStreamOnExit drain_block(stream);
-            if (cptr2.upload(np32.data(), np32.size()) || cidx2.alloc(nz1, false) || cval2.alloc(nz1, false) ||
-                upload_ptr32(wptr, Yn->col_ptr, (size_t)n + 1) || widx.upload(Yn->row_idx, nzn) || wval.upload((const real *)Yn->val, nzn))
-                return kFail;
-            hipLaunchKernelGGL(csc_append_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, Yc_ptr.p, Yc_idx.p, Yc_val.p, wptr.p, widx.p,
-                               wval.p, cptr2.p, cidx2.p, cval2.p, n, (uint32_t)T0);
+            if (cptr2.upload(np32.data(), np32.size()) || cidx2.alloc(nz1, false) || cval2.alloc(nz1, false)) return kFail;
+            if (Yn && (upload_ptr32(wptr, Yn->col_ptr, (size_t)n + 1) || widx.upload(Yn->row_idx, nzn) || wval.upload((const real *)Yn->val, nzn))) return kFail;
+            if (Yn) { sa.wptr = wptr.p; sa.widx = widx.p; sa.wval = wval.p; }
+            sa.nptr = cptr2.p; sa.nidx = cidx2.p; sa.nval = cval2.p;
+            hipLaunchKernelGGL(csc_slide_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, sa);
             TRMF_HIP_CHECK(hipGetLastError());
             TRMF_HIP_CHECK(hipStreamSynchronize(stream));
             new_nnz = nz1;
             if (device_sum_squares(val2.p, new_nnz, &new_ysq)) return kFail;
         } else {
             std::vector<real> blk;
-            (void)dense_rows_to_rowmajor(Yn, blk);
+            if (Yn) (void)dense_rows_to_rowmajor(Yn, blk);
+            const size_t nk = (size_t)Tk * n;
             if (tn2.alloc((size_t)T1 * n, false) || nt2.alloc((size_t)T1 * n, false)) return kFail;
-            TRMF_HIP_CHECK(hipMemcpyAsync(tn2.p, Yd_tn.p, (size_t)T0 * n * sizeof(real), hipMemcpyDeviceToDevice, stream));
-            TRMF_HIP_CHECK(hipMemcpyAsync(tn2.p + (size_t)T0 * n, blk.data(), blk.size() * sizeof(real), hipMemcpyHostToDevice, stream));
-            if (has_transform) {                        // the block is RAW data: grow the raw copy, re-derive below
+            if (nk) TRMF_HIP_CHECK(hipMemcpyAsync(tn2.p, Yd_tn.p + (size_t)retire * n, nk * sizeof(real), hipMemcpyDeviceToDevice, stream));
+            if (!blk.empty()) TRMF_HIP_CHECK(hipMemcpyAsync(tn2.p + nk, blk.data(), blk.size() * sizeof(real), hipMemcpyHostToDevice, stream));
+            if (has_transform) {                        // the block is RAW data: slide the raw copy, re-derive below
                 if (raw2.alloc((size_t)T1 * n, false)) return kFail;
-                TRMF_HIP_CHECK(hipMemcpyAsync(raw2.p, Yraw.p, (size_t)T0 * n * sizeof(real), hipMemcpyDeviceToDevice, stream));
-                TRMF_HIP_CHECK(hipMemcpyAsync(raw2.p + (size_t)T0 * n, blk.data(), blk.size() * sizeof(real), hipMemcpyHostToDevice, stream));
+                if (nk) TRMF_HIP_CHECK(hipMemcpyAsync(raw2.p, Yraw.p + (size_t)retire * n, nk * sizeof(real), hipMemcpyDeviceToDevice, stream));
+                if (!blk.empty()) TRMF_HIP_CHECK(hipMemcpyAsync(raw2.p + nk, blk.data(), blk.size() * sizeof(real), hipMemcpyHostToDevice, stream));
             }
             launch_transpose(tn2.p, T1, n, nt2.p);
             TRMF_HIP_CHECK(hipGetLastError());
             TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // blk is a local: its copies must have left the host
             new_nnz = (uint64_t)T1 * n;
-            if (device_sum_squares(tn2.p, new_nnz, &new_ysq)) return kFail;    // over the grown matrix, like a fresh session's
+            if (device_sum_squares(tn2.p, new_nnz, &new_ysq)) return kFail;    // over the new matrix, like a fresh session's
         }
-        {   // W: T0 rows kept, Tn rows rolled out by the AR model, one all-zero row at the end
+        if (ad_down) {   // the retired entries' terms leave the tables: old storage, old W, active generation -> the other one
+            std::vector<real> hom;
+            if (ad_gamma != 1.0) {
+                hom.resize((size_t)retire);
+                for (int t = 0; t < retire; t++) hom[t] = -(real)std::pow(ad_gamma, (double)(ad_rows - 1 - t));
+            }
+            DevBuf<uint32_t> d_abs; DevBuf<real> om;
+            if (d_abs.upload(ad_cnt.data(), ad_cnt.size()) || (!hom.empty() && om.upload(hom.data(), hom.size()))) return kFail;
+            DowndateArgs da{Yc_ptr.p, Yc_idx.p, Yc_val.p, d_abs.p, W.p, hom.empty() ? nullptr : om.p, ad_S[ad_cur].p, ad_r[ad_cur].p,
+                            ad_S[1 - ad_cur].p, ad_r[1 - ad_cur].p, (uint32_t)retire, n, k, KP};
+            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(series_downdate_kernel<decltype(N)::value>, dim3(n), dim3(64), 0, stream, da); }))
+                return unsupported_rank();
+            TRMF_HIP_CHECK(hipGetLastError());
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // (d_abs and om are locals)
+        }
+        if (ho_slide) {  // held-out positions in retired rows are dropped, the rest shifted: the COO list as pseudo-columns of kSlideChunk entries
+            const int nch = (int)((ho_m + kSlideChunk - 1) / kSlideChunk);
+            std::vector<uint32_t> cp((size_t)nch + 1), hk, np((size_t)nch + 1, 0u);
+            for (int c = 0; c <= nch; c++) cp[c] = (uint32_t)std::min<uint64_t>((uint64_t)c * kSlideChunk, ho_m);
+            DevBuf<uint32_t> d_cp, d_np, d_kept;
+            SlideArgs sa{};
+            if (d_cp.upload(cp.data(), cp.size())) return kFail;
+            sa.optr = d_cp.p; sa.oidx = ho_row.p; sa.oval = ho_val.p; sa.oaux = ho_col.p; sa.ncols = nch; sa.retire = (uint32_t)retire;
+            if (slide_count(sa, d_kept, hk)) return kFail;
+            for (int c = 0; c < nch; c++) np[c + 1] = np[c] + hk[c];
+            ho_m2 = np[nch];
+            if (d_np.upload(np.data(), np.size()) || hrow2.alloc(ho_m2, false) || hcol2.alloc(ho_m2, false) || hval2.alloc(ho_m2, false)) return kFail;
+            sa.nptr = d_np.p; sa.nidx = hrow2.p; sa.nval = hval2.p; sa.naux = hcol2.p;
+            hipLaunchKernelGGL(csc_slide_kernel, dim3((nch + 3) / 4), dim3(256), 0, stream, sa);
+            TRMF_HIP_CHECK(hipGetLastError());
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // (the pointer arrays are locals)
+        }
+        DevBuf<double> hpart2;
+        int ho_nb2 = ho_nb; uint64_t ho_chunk2 = ho_chunk;
+        if (ho_slide) { heldout_geometry(ho_m2, &ho_nb2, &ho_chunk2); if (hpart2.alloc((size_t)kHoSums * ho_nb2, false)) return kFail; }
+        {   // W: the retained rows, Tn rows rolled out by the AR model, one all-zero row at the end
             if (W2.alloc((size_t)(T1 + 1) * KP)) return kFail;
-            TRMF_HIP_CHECK(hipMemcpyAsync(W2.p, W.p, (size_t)T0 * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-            // rank <= 64: the one-wavefront kernel this path has always used (its digests stay); above: the forecast's roll-out,
-            // which covers every rank (the one-wavefront kernel rolled only the first 64 columns forward)
-            if (k <= kMaxRank) {
-                hipLaunchKernelGGL(latent_forecast_kernel, dim3(1), dim3(64), 0, stream, W2.p, T0, T1, KP, NT, k, lag_set.p, nlag, theta.p);
+            if (Tn > 0 && retire > 0 && Tk < midx && k <= kMaxRank) {
+                // the roll-out reads rows that are being retired: roll out behind the old rows first, then keep the suffix
+                DevBuf<real> Wf;
+                SyncStreamOnExit drain_w(stream);
+                if (Wf.alloc((size_t)(T0 + Tn + 1) * KP)) return kFail;
+                TRMF_HIP_CHECK(hipMemcpyAsync(Wf.p, W.p, (size_t)T0 * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+                hipLaunchKernelGGL(latent_forecast_kernel, dim3(1), dim3(64), 0, stream, Wf.p, T0, T0 + Tn, KP, NT, k, lag_set.p, nlag, theta.p);
                 TRMF_HIP_CHECK(hipGetLastError());
-            } else if (launch_rollout(W.p, T0, Tn, W2.p + (size_t)T0 * KP, nullptr)) return kFail;
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+                TRMF_HIP_CHECK(hipMemcpyAsync(W2.p, Wf.p + (size_t)retire * KP, (size_t)T1 * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+                TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+            } else {
+                if (Tk) TRMF_HIP_CHECK(hipMemcpyAsync(W2.p, W.p + (size_t)retire * KP, (size_t)Tk * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+                // rank <= 64: the one-wavefront kernel this path has always used (its digests stay); above: the forecast's roll-out,
+                // which covers every rank (the one-wavefront kernel rolled only the first 64 columns forward) and reads the OLD rows
+                if (Tn > 0 && k <= kMaxRank) {
+                    hipLaunchKernelGGL(latent_forecast_kernel, dim3(1), dim3(64), 0, stream, W2.p, Tk, T1, KP, NT, k, lag_set.p, nlag, theta.p);
+                    TRMF_HIP_CHECK(hipGetLastError());
+                } else if (Tn > 0 && launch_rollout(W.p, T0, Tn, W2.p + (size_t)Tk * KP, nullptr)) return kFail;
+                TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+            }
         }
         // ---- commit ----
         if (!dense) {
             Yr_ptr.swap(ptr2); Yr_idx.swap(idx2); Yr_val.swap(val2);
             Yc_ptr.swap(cptr2); Yc_idx.swap(cidx2); Yc_val.swap(cval2);
+            if (retire > 0 && ad_exists)            // the absorbed entries stay a prefix of every column: it lost the retired ones
+                for (int j = 0; j < n && (size_t)j < ad_cnt.size(); j++) {
+                    const uint32_t lost = (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j]) - kept[j];
+                    ad_cnt[j] -= std::min(ad_cnt[j], lost);
+                }
             host_row_ptr.swap(new_row_ptr); host_col_ptr.swap(new_col_ptr);
         } else {
             Yd_tn.swap(tn2); Yd_nt.swap(nt2);
             if (has_transform) Yraw.swap(raw2);
         }
         W.swap(W2);
+        if (retire > 0) {
+            if (ad_exists) {
+                if (retire > ad_rows) adapt_stale();    // rows the tables never absorbed are gone: they no longer describe a prefix
+                else if (ad_down) ad_cur = 1 - ad_cur;
+                ad_rows = std::max(0, ad_rows - retire);
+            }
+            if (ho_slide) {
+                ho_row.swap(hrow2); ho_col.swap(hcol2); ho_val.swap(hval2); ho_part.swap(hpart2); ho_pred.release();
+                ho_m = ho_m2; ho_nb = ho_nb2; ho_chunk = ho_chunk2;
+            }
+            markW.release(); markH.release(); markT.release(); mark_iter = -1;     // a mark names rows that have moved
+            snapW.release(); snapH.release(); snapT.release(); snap_iter = -1;
+        }
+        out.rows_retired = (uint64_t)retire; out.entries_retired = dense ? (uint64_t)retire * n : cut;
+        out.rows_appended = (uint64_t)Tn; out.entries_appended = dense ? (uint64_t)Tn * n : nzn;
+        out.rows = (uint64_t)T1; out.entries = new_nnz;
+        if (res) *res = out;
         nnz = new_nnz; ysq_acc = new_ysq;
         T = T1;
-        if (dense && has_transform && apply_series_transform()) return kFail;   // current coefficients over the grown raw matrix
+        if (dense && has_transform && apply_series_transform()) return kFail;   // current coefficients over the new raw matrix
         set_trYTY();
         iter = 0;
         if (gramx_mode != kGramxReplicate && comm->world > 1 && !test_env("TRMF_GRAMX")) { gramx_mode = kGramxMeasure; gramx_calls = 0; }
@@ -910,11 +1059,7 @@ struct TrmfSessionImpl : SessionXPhase {
         FillStreamScope fill(stream);
         const uint64_t m = Yt->nnz;
         if (ho_row.upload(rows.data(), m) || ho_col.upload(Yt->col_idx, m) || ho_val.upload((const real *)Yt->val_t, m)) return kFail;
-        // equal contiguous chunks, a multiple of one workgroup step each: the work of a workgroup does not depend on row lengths
-        ho_nb = (int)std::max<uint64_t>(1, std::min<uint64_t>(kHoMaxBlocks, (m + 255) / 256));
-        ho_chunk = ((m + ho_nb - 1) / ho_nb + kHoStep - 1) / kHoStep * kHoStep;
-        if (ho_chunk == 0) ho_chunk = kHoStep;
-        ho_nb = (int)std::max<uint64_t>(1, (m + ho_chunk - 1) / ho_chunk);
+        heldout_geometry(m, &ho_nb, &ho_chunk);
         if (ho_part.alloc((size_t)kHoSums * ho_nb, false) || ho_sums.alloc(kHoSums, false)) return kFail;
         TRMF_HIP_CHECK(hipStreamSynchronize(stream));
         ho_m = m; ho_set = true;

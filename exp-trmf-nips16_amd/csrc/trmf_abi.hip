@@ -321,6 +321,12 @@ int64_t trmf_device_free_bytes(void) {
     return (int64_t)free_b;
 }
 
+int64_t trmf_device_pool_live_bytes(void) {
+    DeviceGuard guard;
+    if (!guard.ok) return -1;
+    return (int64_t)DevicePool::current().stats().live_bytes;
+}
+
 const char *trmf_last_error(void) {
     static thread_local std::string copy;
     std::lock_guard<std::mutex> lk(g_err_mu);
@@ -370,6 +376,27 @@ int32_t trmf_session_append_rows(TrmfSession *s, const PyMatrix *Ynew) {
     if (!s || !Ynew) { set_error("null session or block"); return kFail; }
     DeviceGuard guard;
     return guard.ok ? HND(s)->all([&](TrmfSessionImpl *t) { return t->append_rows(Ynew); }) : kFail;
+}
+// Every argument is checked here, on the calling thread, before any rank's worker runs (a rejected call must not break the barrier
+// of a TRMF_DEVICES group).
+int32_t trmf_session_slide(TrmfSession *s, const PyMatrix *Ynew, int32_t retire, int32_t downdate_stats, TrmfSlideSums *out) {
+    if (!s) { set_error("null session"); return kFail; }
+    const std::string why = HND(s)->first()->slide_refusal(Ynew, retire, downdate_stats);
+    if (!why.empty()) { set_error(why); return kFail; }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    TrmfSessionImpl::SlideResult res;
+    const int rc = HND(s)->all([&](TrmfSessionImpl *t) {
+        TrmfSessionImpl::SlideResult r;
+        const int c = t->slide(Ynew, retire, downdate_stats != 0, &r);
+        if (c == 0 && t->comm->rank == 0) res = r;
+        return c;
+    });
+    if (rc == 0 && out) {
+        out->rows_retired = res.rows_retired; out->entries_retired = res.entries_retired; out->rows_appended = res.rows_appended;
+        out->entries_appended = res.entries_appended; out->rows = res.rows; out->entries = res.entries;
+    }
+    return rc;
 }
 int32_t trmf_session_rows(TrmfSession *s) { return s ? HND(s)->first()->T : kFail; }
 int32_t trmf_session_set_series_transform(TrmfSession *s, const void *a, const void *b) {

@@ -168,7 +168,7 @@ class Model(object):
 
     # ---- online update ----------------------------------------------------------------------------
     def assimilate(self, Ynew, lambdaI, lambdaAR, missing=True, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0,
-                   smooth_back=0, Yback=None, smooth_robust=False, adapt_robust=False):
+                   smooth_back=0, Yback=None, smooth_robust=False, adapt_robust=False, window=None):
         """A new ``Model`` grown by the ``Ynew.shape[0]`` timestamps of ``Ynew`` (raw values; a transform of this model is
         applied first): H, the lag weights and the rows this model has stay as they are, every new row of W is solved from its
         own observations and the AR prior of the rows before it (``trmf.online.filter_rows``; the host form of
@@ -189,8 +189,15 @@ class Model(object):
         ``adapt_robust=True`` (needs both ``robust_c`` and ``adapt``): the statistics absorb the block with Huber weights of their
         own (``trmf.online.SeriesStats.absorb_robust`` with the same ``robust_c``, ``scale`` and ``robust_sweeps``; the host form
         of ``Session.update(adapt_robust=True)``) and ``adapt_weights`` of the new model are its weights; without the flag the
-        cells enter unweighted, as before."""
+        cells enter unweighted, as before.
+        ``window=N`` (the host form of ``Session.update(window=N)``): the new model keeps the last N rows only -- the oldest
+        ``max(0, m + Tn - N)`` rows of W are dropped after the update, and series statistics drop their absorbed rows by as many
+        (their tables keep the retired rows as exponentially forgotten history; a model holds no training matrix to downdate
+        from).  An N smaller than the block + ``smooth_back`` + the largest lag + 1 is refused."""
         from .online import filter_rows, robust_filter_rows, smooth_rows, robust_smooth_rows
+        if window is not None:
+            from .session import check_window
+            window = check_window(window, Ynew.shape[0], int(smooth_back), int(self.lag_set.max()) if len(self.lag_set) else 0)
         if adapt_robust and (robust_c is None or not adapt):
             raise ValueError('assimilate: adapt_robust=True needs both robust_c and adapt (it refits the loadings with the Huber threshold of '
                              'the robust filter)')
@@ -232,13 +239,14 @@ class Model(object):
         if smooth_back > 0:
             first = max(self.m - smooth_back, int(self.lag_set.max()) if len(self.lag_set) else 0)
             tail = Yback[smooth_back - (self.m - first):] if first < self.m else Yback[:0]
-            window = smat.vstack([smat.csr_matrix(tail), smat.csr_matrix(Ynew)]).tocsr() if smat.issparse(Ynew) else np.vstack([np.asarray(tail), np.asarray(Ynew)])
+            span = smat.vstack([smat.csr_matrix(tail), smat.csr_matrix(Ynew)]).tocsr() if smat.issparse(Ynew) else np.vstack([np.asarray(tail), np.asarray(Ynew)])
             if smooth_robust:
-                grown, weights = robust_smooth_rows(grown, self.H, self.lag_set, self.lag_val, window, first, lambdaI, lambdaAR, missing,
+                grown, weights = robust_smooth_rows(grown, self.H, self.lag_set, self.lag_val, span, first, lambdaI, lambdaAR, missing,
                                                     scale, robust_c, robust_sweeps)
             else:
-                grown = smooth_rows(grown, self.H, self.lag_set, self.lag_val, window, first, lambdaI, lambdaAR, missing)
-        out = Model.from_arrays(grown, self.H.copy(), self.lag_val.copy(), self.lag_set.copy(), transform=self.transform)
+                grown = smooth_rows(grown, self.H, self.lag_set, self.lag_val, span, first, lambdaI, lambdaAR, missing)
+        retire = max(0, grown.shape[0] - window) if window is not None else 0
+        out = Model.from_arrays(np.ascontiguousarray(grown[retire:]), self.H.copy(), self.lag_val.copy(), self.lag_set.copy(), transform=self.transform)
         stats = getattr(self, 'series_stats', None)
         if adapt:
             import copy
@@ -254,6 +262,8 @@ class Model(object):
             else:
                 stats = copy.deepcopy(stats).absorb(grown, Ynew)
                 out.H[:] = stats.solve(lambdaI)
+            if retire:
+                stats.rows -= min(retire, stats.rows)          # (the tables keep the retired rows: forgotten history)
             out.series_stats = stats
         if weights is not None:
             out.robust_weights = weights

@@ -407,6 +407,22 @@ def robust_window_objective(W, H, lag_set, lag_val, Yrows, first_row, lambdaI, l
     return fit + 0.5 * (float(lambdaI) * ridge + float(lambdaAR) * ar)
 
 
+# ---- the sliding window (trmf_session_slide) ------------------------------------------------------------------------------------
+def slide_entries(rows, cols, vals, retire):
+    """What a stored list of entries becomes when the ``retire`` oldest rows leave: the entries with ``rows >= retire`` in their
+    STORED order (a stable filter -- the lists need not be sorted and a cell may be stored twice), row numbers reduced by
+    ``retire``.  Applied to the (row index, column index, value) arrays of either orientation of a session's Y it gives the arrays
+    of the session after ``slide``.  Returns ``(rows, cols, vals)`` as new arrays."""
+    rows, cols, vals = np.asarray(rows), np.asarray(cols), np.asarray(vals)
+    retire = int(retire)
+    if retire < 0:
+        raise ValueError('slide_entries: retire must not be negative, not {}'.format(retire))
+    if not (rows.shape == cols.shape == vals.shape and rows.ndim == 1):
+        raise ValueError('slide_entries: rows, cols and vals must be one-dimensional arrays of one length')
+    keep = rows >= retire
+    return rows[keep] - rows.dtype.type(retire), cols[keep].copy(), vals[keep].copy()
+
+
 # ---- online loading updates: the rows of H refitted from new rows (trmf_session_series_stats_init / _adapt_series) ---------------
 def _series_entries(Y, missing):
     """Per series the (timestamps, values) of its observations in stored order.  Sparse ``Y``: the stored entries of the column
@@ -522,6 +538,43 @@ class SeriesStats(object):
                     self.S[j] += np.outer(aw, Wn[t])
                 self.r[j] += aw * y[e]
         self.rows = T
+        return self
+
+    def retire(self, W, Y, count, downdate=True):
+        """The sliding-window form (``trmf_session_slide``): the ``count`` oldest of the absorbed rows leave.  ``W`` (``self.rows``
+        x k or longer) and ``Y`` (at least ``count`` rows) are the factor and the observations of BEFORE the retirement, row 0 the
+        oldest.  With ``downdate`` every retired entry's term is subtracted, ::
+
+            S_j <- S_j - om_t w_t w_t^T,   r_j <- r_j - om_t y_tj w_t,   om_t = forget^(rows - 1 - t),   t < count
+
+        one rank-1 update per entry in stored order (the absorb step with the sign of the weight flipped), in the dtype of ``W``:
+        the tables then describe the retained rows alone.  Without it the tables keep the retired rows as exponentially forgotten
+        history (recursive least squares as usually run, the natural choice for ``forget < 1``).  Either way ``self.rows`` drops by
+        ``count``, so that the next ``absorb`` takes the rows after the retained ones."""
+        W = np.asarray(W)
+        count = int(count)
+        if count < 0 or count > self.rows:
+            raise ValueError('SeriesStats.retire: count {} outside 0..{} (the absorbed rows)'.format(count, self.rows))
+        if W.shape[1] != self.k or W.dtype != self.dtype or W.shape[0] < count:
+            raise ValueError('SeriesStats.retire: W is {} {}, at least {} rows of {} columns of {} were expected'.format(W.shape, W.dtype, count, self.k, self.dtype))
+        if Y.shape[0] < count or Y.shape[1] != self.n:
+            raise ValueError('SeriesStats.retire: Y is {}, at least {} rows of {} series were expected'.format(Y.shape, count, self.n))
+        if downdate and count:
+            dt = self.dtype
+            om = (-(self.forget ** (self.rows - 1 - np.arange(count, dtype=np.float64)))).astype(dt)
+            if not self.missing:
+                for t in range(count):
+                    self.S[0] += np.outer(om[t] * W[t], W[t])
+            for j, (rows, y) in enumerate(_series_entries(Y, self.missing)):
+                y = np.asarray(y, dtype=dt)
+                for e, t in enumerate(rows):
+                    if t >= count:
+                        continue
+                    aw = om[t] * W[t]
+                    if self.missing:
+                        self.S[j] += np.outer(aw, W[t])
+                    self.r[j] += aw * y[e]
+        self.rows -= count
         return self
 
     def solve(self, lambdaI):

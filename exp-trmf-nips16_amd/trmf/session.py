@@ -94,6 +94,14 @@ class TrmfAdaptSums(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TrmfSlideSums(ctypes.Structure):
+    _fields_ = [('rows_retired', c_uint64), ('entries_retired', c_uint64), ('rows_appended', c_uint64), ('entries_appended', c_uint64),
+                ('rows', c_uint64), ('entries', c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class TrmfRobustAdaptSums(ctypes.Structure):
     """Sums of a robust online loading update (include/trmf_abi.h): those of ``TrmfAdaptSums``, the number of down-weighted
     entries and the sum of the weights of the last sweep, the Huber objective ``sum_j J_j`` before / after."""
@@ -210,6 +218,9 @@ def bind(lib):
         lib.trmf_session_adapt_series_robust.argtypes = [c_void_p, c_double, c_int32, c_void_p, POINTER(TrmfRobustAdaptSums), c_void_p, c_void_p,
                                                          c_void_p, c_void_p]
         lib.trmf_session_adapt_series_robust.restype = c_int32
+    if hasattr(lib, 'trmf_session_slide'):            # (absent from libraries built before the sliding window)
+        lib.trmf_session_slide.argtypes = [c_void_p, P, c_int32, c_int32, POINTER(TrmfSlideSums)]; lib.trmf_session_slide.restype = c_int32
+        lib.trmf_device_pool_live_bytes.restype = ctypes.c_int64
     if hasattr(lib, 'trmf_session_fit_noise'):        # (absent from libraries built before the forecast uncertainty)
         lib.trmf_session_fit_noise.argtypes = [c_void_p, POINTER(TrmfNoiseStats)]; lib.trmf_session_fit_noise.restype = c_int32
         lib.trmf_session_noise.argtypes = [c_void_p, c_void_p, c_void_p]; lib.trmf_session_noise.restype = c_int32
@@ -249,6 +260,27 @@ def _stored_per_row(pm):
     if pm.type != PyMatrix.SPARSE:
         return None
     return np.diff(np.ctypeslib.as_array(pm.row_ptr, shape=(int(pm.rows) + 1,)).astype(np.int64))
+
+
+def check_retire(retire):
+    """The front end's argument check of ``slide``: ``retire`` as an int that is not negative."""
+    if isinstance(retire, bool) or not isinstance(retire, (int, np.integer)):
+        raise TypeError('retire must be an integer, not {!r}'.format(retire))
+    if retire < 0:
+        raise ValueError('retire must not be negative, not {}'.format(retire))
+    return int(retire)
+
+
+def check_window(window, block_rows, smooth_back, reach):
+    """The front end's argument check of ``update(window=N)``: N holds at least the block, the rows smoothed back and the largest
+    lag + 1."""
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)):
+        raise TypeError('window must be an integer, not {!r}'.format(window))
+    need = int(block_rows) + int(smooth_back) + int(reach) + 1
+    if window < need:
+        raise ValueError('update: window={} is smaller than the block ({}) + smooth_back ({}) + the largest lag ({}) + 1 = {}'.format(
+            window, block_rows, smooth_back, reach, need))
+    return int(window)
 
 
 def check_lag_penalty(lambdaLagL1, lag_refit=False):
@@ -325,6 +357,49 @@ class Session(object):
         if self._stored is not None:
             self._stored = np.concatenate([self._stored, _stored_per_row(block)])
         return self
+
+    def slide(self, Ynew=None, retire=0, downdate_stats=False):
+        """The sliding window: append the timestamps of ``Ynew`` (as ``append_rows`` does; ``None``: nothing) and retire the
+        ``retire`` oldest rows of the resident problem, in one pass on the device.  Afterwards the session is the one a fresh
+        ``Session`` would be on the retained entries in their stored order (``trmf.online.slide_entries``), ``W[retire:]`` followed
+        by the AR roll-out of the block, and the current H, lag weights and transform; row numbers of every later call count from
+        the new first row.  Held-out positions in retired rows are dropped, the others move up; the mark is invalidated.  Series
+        statistics: their absorbed rows drop by ``retire``; with ``downdate_stats`` the retired entries' terms are also subtracted
+        from ``S_j`` and ``r_j`` (``trmf.SeriesStats.retire``; sparse storage with ``missing`` only) so that the next
+        ``adapt_series`` fits the retained rows alone, without it they stay as exponentially forgotten history.  ``self.model``
+        is replaced by a host model of ``rows()`` timestamps (W shifted; H, lag weights, lag set and transform carried over).
+        Returns ``{'rows_retired', 'entries_retired', 'rows_appended', 'entries_appended', 'rows', 'entries'}``.  A refused call
+        (negative ``retire``, more than the rows held before the call, fewer than the largest lag + 1 rows left, whatever
+        ``append_rows`` refuses, ``downdate_stats`` without valid per-series statistics) raises and leaves the session as it was."""
+        retire = check_retire(retire)
+        if not hasattr(self.lib, 'trmf_session_slide'):
+            raise RuntimeError('slide: the loaded library was built before the sliding window')
+        block = None
+        if Ynew is not None:
+            block = Ynew if isinstance(Ynew, PyMatrix) else PyMatrix(Ynew, dtype=self.model.W.dtype)
+        before = self.rows()
+        sums = TrmfSlideSums()
+        self._check(self.lib.trmf_session_slide(self.handle, byref(block) if block is not None else None, retire, 1 if downdate_stats else 0,
+                                                byref(sums)), 'trmf_session_slide')
+        if self._stored is not None:
+            self._stored = np.concatenate([self._stored[retire:]] + ([_stored_per_row(block)] if block is not None else []))
+        if retire and getattr(self, '_heldout_rows', None) is not None:
+            self._heldout_rows = self._heldout_rows[self._heldout_rows >= retire] - retire
+            self._heldout_nnz = int(self._heldout_rows.size)
+        old = self.model
+        moved = np.zeros((self.rows(), old.k), dtype=old.W.dtype, order='C')
+        kept = old.W[retire:min(before, old.m)]
+        moved[:len(kept)] = kept
+        self.model = type(old).from_arrays(moved, old.H.copy(), old.lag_val.copy(), old.lag_set.copy(), transform=old.transform)
+        return sums.as_dict()
+
+    def retire_rows(self, count, downdate_stats=False):
+        """``slide`` without a block: retire the ``count`` oldest rows."""
+        return self.slide(None, count, downdate_stats)
+
+    def pool_live_bytes(self):
+        """Bytes of device memory that live buffers of this process hold in the library's pool right now."""
+        return int(self.lib.trmf_device_pool_live_bytes())
 
     def assimilate(self, first_row, return_latent=False):
         """Online update on the device: rows ``first_row .. rows()-1`` of W are re-solved in ascending order from their own
@@ -506,7 +581,7 @@ class Session(object):
         return {'valid': v.value == 1, 'stale': v.value == -1, 'absorbed_rows': int(rows.value), 'forget': float(g.value)}
 
     def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0, smooth_back=0, smooth_robust=False,
-               adapt_robust=False):
+               adapt_robust=False, window=None, downdate_stats=False):
         """Absorb the new timestamps ``Ynew`` (as for ``append_rows``): append them, assimilate the new block, run ``iters``
         ALS iterations if asked for.  ``self.model`` is replaced by a host model of ``rows()`` timestamps (H, lag weights, lag
         set and transform carried over; its arrays are filled by the next ``download()``).  Returns the sums of ``assimilate``;
@@ -520,7 +595,10 @@ class Session(object):
         ``robust_c`` and ``smooth_back > 0`` is refused.  ``smooth_back`` with ``adapt`` is refused: the rows before the block are the
         ones the series statistics have absorbed.  Under ``robust_c`` the loading update of ``adapt`` still takes every cell
         unweighted unless ``adapt_robust=True`` is passed: the block's loading update is then ``adapt_series_robust`` with the same
-        ``robust_c``, ``scale`` and ``robust_sweeps``.  ``adapt_robust=True`` without both ``robust_c`` and ``adapt`` is refused."""
+        ``robust_c``, ``scale`` and ``robust_sweeps``.  ``adapt_robust=True`` without both ``robust_c`` and ``adapt`` is refused.  With ``window=N`` the session is a
+        sliding window of at most N rows: the append becomes ``slide(Ynew, max(0, rows() + Tn - N), downdate_stats)`` and every later
+        step runs on the shifted row numbers; an N smaller than the block + ``smooth_back`` + the largest lag + 1 is refused before the
+        session is touched.  Without ``window`` the session grows as before."""
         smooth_back = int(smooth_back)
         if smooth_back < 0:
             raise ValueError('update: smooth_back must not be negative, not {}'.format(smooth_back))
@@ -536,6 +614,13 @@ class Session(object):
         if smooth_back > 0 and adapt:
             raise ValueError('update: smooth_back together with adapt is refused: the rows before the block are the ones the series statistics have absorbed: smoothing them makes the statistics stale')
         before = self.rows()
+        retire = 0
+        if window is not None:
+            block = Ynew if isinstance(Ynew, PyMatrix) else PyMatrix(Ynew, dtype=self.model.W.dtype)
+            Ynew = block
+            retire = max(0, before + int(block.rows) - check_window(window, int(block.rows), smooth_back, self._reach()))
+        elif downdate_stats:
+            raise ValueError('update: downdate_stats needs window')
         if adapt:
             info = self.series_stats_info()
             if info['stale']:       # before anything is appended: a refused update leaves the session as it was
@@ -543,11 +628,15 @@ class Session(object):
                                    'transform since they were built); initialise them again (init_series_stats)')
             if not info['valid']:
                 self.init_series_stats(forget)
-        self.append_rows(Ynew)
-        old = self.model
-        grown = np.zeros((self.rows(), old.k), dtype=old.W.dtype, order='C')
-        grown[:min(before, old.m)] = old.W[:before]
-        self.model = type(old).from_arrays(grown, old.H.copy(), old.lag_val.copy(), old.lag_set.copy(), transform=old.transform)
+        if window is not None:
+            self.slide(Ynew, retire, downdate_stats)
+            before -= retire                                 # the block's first row, counted from the new first row
+        else:
+            self.append_rows(Ynew)
+            old = self.model
+            grown = np.zeros((self.rows(), old.k), dtype=old.W.dtype, order='C')
+            grown[:min(before, old.m)] = old.W[:before]
+            self.model = type(old).from_arrays(grown, old.H.copy(), old.lag_val.copy(), old.lag_set.copy(), transform=old.transform)
         sums = self.assimilate(before) if robust_c is None else self.assimilate_robust(before, robust_c, robust_sweeps, scale)
         if smooth_back > 0:
             first = max(before - smooth_back, self._reach())
@@ -609,7 +698,7 @@ class Session(object):
         zeros included, are the cells to score, in the scale the session trains on.  ``None`` drops the set."""
         if Ytest is None:
             self._check(self.lib.trmf_session_set_heldout(self.handle, None), 'trmf_session_set_heldout')
-            self._heldout_nnz = None
+            self._heldout_nnz = self._heldout_rows = None
             return self
         if isinstance(Ytest, PyMatrix):
             pyT = Ytest
@@ -619,6 +708,7 @@ class Session(object):
             raise TypeError('set_heldout: a scipy.sparse matrix is required (its stored entries are the held-out cells)')
         self._check(self.lib.trmf_session_set_heldout(self.handle, byref(pyT)), 'trmf_session_set_heldout')
         self._heldout_nnz = int(pyT.nnz)
+        self._heldout_rows = np.repeat(np.arange(int(pyT.rows), dtype=np.int64), _stored_per_row(pyT))     # (slide drops the retired rows' cells)
         return self
 
     def eval_heldout_sums(self, predictions=False):

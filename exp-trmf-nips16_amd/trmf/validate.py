@@ -35,7 +35,7 @@ def _as_training_matrix(block, missing):
     return smat.csr_matrix(block) if missing else block
 
 
-def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag=None, assimilate=False, robust=None, adapt=None, smooth_back=0):
+def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag=None, assimilate=False, robust=None, adapt=None, smooth_back=0, window=None):
     """Yield the trained model of every window from one resident session.  With a transform (dense Y, full
     observation) the session holds the RAW matrix and applies each window's refitted coefficients on the device."""
     from .session import Session
@@ -50,7 +50,7 @@ def _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing,
             _ensure_noise(sess)
         for prev_cut, cut in zip(cuts[:-1], cuts[1:]):
             if assimilate:      # online: the new rows are filtered in, nothing is retrained
-                sess.update(_as_training_matrix(Y[prev_cut:cut], missing), **dict(robust or {}, **dict(adapt or {}, **({'smooth_back': smooth_back} if smooth_back else {}))))
+                sess.update(_as_training_matrix(Y[prev_cut:cut], missing), **dict(robust or {}, **dict(adapt or {}, **dict({'smooth_back': smooth_back} if smooth_back else {}, **({'window': window} if window is not None else {})))))
                 yield sess.download()
                 continue
             # host-side model of the new size: same warm start the device applies, same RNG consumption as the
@@ -137,7 +137,7 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
                      max_iter=20, missing=True, threshold=0, transform=None, threads=16, verbose=0, seed=0,
                      resident=True, forecast_on_device=False, lambdaLagL1=0.0, lag_refit=False, update='retrain', interval_level=None,
                      robust_c=None, robust_sweeps=4, adapt_series=False, forget=1.0, smooth_back=0, smooth_robust=False,
-                     adapt_robust=False):
+                     adapt_robust=False, window=None):
     """``interval_level`` (e.g. 0.9; needs ``forecast_on_device=True``): every window also fits the noise of its trained model and
     scores the predictive distribution of its forecast on the device; the result is ``(Metrics, IntervalMetrics)``, the ``Metrics``
     being exactly those of the call without it.
@@ -158,6 +158,9 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
     ``adapt_robust=True`` (needs both ``robust_c`` and ``adapt_series``): the loadings are refitted by ``Session.adapt_series_robust``
     with the same ``robust_c`` and ``robust_sweeps``, so that a spiked cell is kept out of H as it is kept out of W; without it the
     loading update takes every cell unweighted.
+    ``window=N`` (with ``update='assimilate'`` only; not with ``forecast_on_device``): the session is a sliding window -- every
+    absorbed block retires the oldest rows beyond N (``Session.update(window=N)``) instead of growing the resident problem; the
+    default is the expanding window.
     ``lambdaLagL1`` / ``lag_refit``: sparse lag weights (``Session.set_lag_penalty``) on every path.
     ``forecast_on_device=True`` keeps the forecasts and their scoring on the device as well (one session, no download and no
     host model per window); it needs the resident path and a dense ``Y``, and says so where that does not hold."""
@@ -202,6 +205,13 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
             raise ValueError('smooth_back together with adapt_series is refused: the rows before the block are the ones the series statistics have absorbed: smoothing them makes the statistics stale')
     if smooth_robust:
         robust['smooth_robust'] = True      # (Session.update's keyword)
+    if window is not None:
+        if not online:
+            raise ValueError("window: a sliding window retires rows absorbed online (update='assimilate'); retraining uses the growing prefix")
+        if forecast_on_device:
+            raise ValueError('window: not together with forecast_on_device (its loop addresses rows of the growing prefix)')
+        from .session import check_window
+        window = check_window(window, window_size, smooth_back, max(lag_set) if len(lag_set) else 0)
     if online:
         if transform is not None:
             raise ValueError("update='assimilate': a per-window transform rescales the whole history, which an online update does not revisit")
@@ -226,7 +236,7 @@ def rolling_validate(Y, lag_set, k=40, window_size=24, nr_windows=7, lambdaI=0.5
                                         interval_level, robust, adapt, smooth_back)
     # resident: a NumPy Y, and a transform only where the device can apply it (dense full-observation training)
     if resident and isinstance(Y, np.ndarray) and (transform is None or (not missing and Y.dtype in (np.float32, np.float64))):
-        models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag, online, robust, adapt, smooth_back)
+        models = _train_windows_resident(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, verbose, lag, online, robust, adapt, smooth_back, window)
     else:
         models = _train_windows_fresh(Y, lag_set, k, cuts, seed, hyper, max_iter, missing, transform, threads, verbose, lag)
     forecasts = np.zeros((horizon, n), dtype=Y.dtype, order='C')

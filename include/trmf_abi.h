@@ -144,6 +144,9 @@ TRMF_API int32_t trmf_device_count(void);
 TRMF_API int32_t trmf_set_device(int32_t device);
 /* Free bytes of HBM on the selected device right now (-1 if no device): sizing aid, and what the leak test reads. */
 TRMF_API int64_t trmf_device_free_bytes(void);
+/* Bytes of the selected device's pool that live buffers of this process hold right now (-1 if no device): what a session that is
+ * meant to stay the same size -- a sliding window -- is checked against. */
+TRMF_API int64_t trmf_device_pool_live_bytes(void);
 /* Last error text of section-2 calls (static storage, never NULL). */
 TRMF_API const char *trmf_last_error(void);
 
@@ -198,6 +201,38 @@ TRMF_API int32_t trmf_session_set_timing(TrmfSession *s, int32_t period);
  * restarts at 1 like a fresh c_trmf_train call (period_* gating, trmf.cpp:647).  Blocking.  With a communicator
  * active every rank must call it with the same block. */
 TRMF_API int32_t trmf_session_append_rows(TrmfSession *s, const PyMatrix *Ynew);
+/* The sliding window: append Ynew (as trmf_session_append_rows does, with the same validation; NULL = nothing to append) AND
+ * retire the `retire` oldest timestamps, in one new generation of storage (the data is passed over once, on the device; only the
+ * block crosses PCIe).  retire == 0 with a block IS trmf_session_append_rows (one code path, the same bits).
+ *
+ * Contract: afterwards the session is the one trmf_session_create would build from
+ *   - the retained entries in their STORED order, timestamps reduced by `retire`, followed (per row / per column) by the block's
+ *     (the input need not be a canonical CSR/CSC pair: the column compaction on the device is stable),
+ *   - W[retire:] followed by the AR roll-out of the block,
+ *   - the current H, lag weights, lambdas, lag penalty and series transform (the raw matrix slides, the current coefficients
+ *     are re-applied, sum y^2 is recomputed as a fresh session computes it),
+ * and every later call -- run, assimilate*, smooth*, forecast*, objective, download -- returns the bits it returns on that fresh
+ * session.  The iteration counter restarts, as after append_rows.  Blocking; with a communicator active every rank makes the
+ * same call.  Failure-atomic: a refused or failed call leaves the session exactly as it was.
+ *
+ * Refused (trmf_last_error(); the session stays usable): retire < 0; retire larger than the rows held before the call (rows of
+ * the block itself cannot be retired); fewer than (largest lag + 1) rows left after the append; everything append_rows refuses,
+ * the 32-bit index limits applied to the sizes AFTER the slide; downdate_stats not 0 or 1; downdate_stats == 1 without valid
+ * series statistics or on a full-observation form (dense storage, sparse storage with missing == 0: one shared S).
+ *
+ * Other resident state.  The mark is invalidated when rows are retired.  Noise tables, forecast scores and interval scores are
+ * per series / per latent dimension and stay.  Held-out positions in retired rows are dropped, the others move up by `retire`
+ * (trmf_session_eval_heldout then returns the sums of a fresh trmf_session_set_heldout of the shifted set).  Series statistics
+ * (trmf_session_series_stats_init): absorbed_rows and the per-series absorbed counts drop by what was retired, so the entries
+ * not yet absorbed remain the tail of every column.  downdate_stats == 1 (sparse storage, missing != 0) also subtracts every
+ * retired entry's om_t w_t w_t^T and om_t y w_t, om_t = forget^(absorbed_rows - 1 - t), from S_j and r_j in stored order -- the
+ * tables then describe the retained rows only (a rectangular window); H is not refitted, the next adapt_series does that.
+ * downdate_stats == 0 leaves the tables as they are: the retired rows stay in them as exponentially forgotten history, which is
+ * recursive least squares as usually run and the natural choice for forget < 1.  Retiring rows the tables have not absorbed
+ * yet makes them stale; stale tables stay stale. */
+typedef struct { uint64_t rows_retired, entries_retired, rows_appended, entries_appended, rows, entries; } TrmfSlideSums;
+TRMF_API int32_t trmf_session_slide(TrmfSession *s, const PyMatrix *Ynew /* or NULL */, int32_t retire, int32_t downdate_stats,
+                                    TrmfSlideSums *out /* or NULL */);
 /* Train on a[i] * y + b[i] of series (column) i instead of the raw dense Y the session holds (missing == 0 only):
  * the per-window NormalizedTransform of the reference's rolling_validate(transform=True) (python/trmf/trmf.py:82-96,
  * 237-249, 253-257), which rescales every entry of the growing prefix.  The session keeps the raw matrix (rows passed
@@ -209,7 +244,7 @@ TRMF_API int32_t trmf_session_append_rows(TrmfSession *s, const PyMatrix *Ynew);
 TRMF_API int32_t trmf_session_set_series_transform(TrmfSession *s, const void *a /* n */, const void *b /* n */);
 /* Checkpoint of the session's (W, H, lag_val, iteration counter) ON THE DEVICE, and the way back to it: after rewind the
  * session continues exactly as it did after mark (the solver is deterministic).  One mark per session (a new one replaces the
- * old); append_rows invalidates it.  Both block.  No reference counterpart (bench.py repeats its timed window with these). */
+ * old); append_rows and slide invalidate it.  Both block.  No reference counterpart (bench.py repeats its timed window with these). */
 TRMF_API int32_t trmf_session_mark(TrmfSession *s);
 TRMF_API int32_t trmf_session_rewind(TrmfSession *s);
 /* Number of timestamps currently held by the session (rows of W). */
