@@ -189,9 +189,10 @@ struct TrmfSessionImpl : SessionXPhase {
         t_upload_s = now_s() - tu0;
 
         if (xstate.alloc(1) || log.alloc(kLogCap)) return kFail;
-        if (full && (Bf.alloc((size_t)n * KP) || GSf.alloc((size_t)k * k) || Uf.alloc((size_t)k * k) || GSx.alloc((size_t)k * k + kHvGramPad) ||
+        if (full && (GSf.alloc((size_t)k * k) || Uf.alloc((size_t)k * k) || GSx.alloc((size_t)k * k + kHvGramPad) ||
                      sgram_part.alloc((size_t)kSmallGramBlocks * k * k)))
             return kFail;
+        if (alloc_series_scratch()) return kFail;
         if (comm->world > 1 && count_ranks_per_device()) return kFail;
         if (alloc_time_scratch()) return kFail;
 
@@ -225,8 +226,12 @@ struct TrmfSessionImpl : SessionXPhase {
         return autotune();
     }
 
+    // What is sized by the number of series n alone: called by create() and again by change_series().  (gemm_part, gen_scratch, the
+    // F-row partition and the split rows depend on n too: alloc_time_scratch() derives them.)
+    int alloc_series_scratch() { return full && Bf.alloc((size_t)n * KP) ? kFail : 0; }
+
     // Everything whose size depends on the number of timestamps T (and the row partitions): called by create()
-    // and again by append_rows().
+    // and again by append_rows() and change_series().
     int alloc_time_scratch() {
         const size_t NV = (size_t)T * KP;
         if (full && dense && gemm_part.alloc((size_t)kGemmChunks * (size_t)std::max(T, n) * KP)) return kFail;
@@ -669,6 +674,343 @@ struct TrmfSessionImpl : SessionXPhase {
         iter = 0;
         if (gramx_mode != kGramxReplicate && comm->world > 1 && !test_env("TRMF_GRAMX")) { gramx_mode = kGramxMeasure; gramx_calls = 0; }
         if (alloc_time_scratch()) return kFail;
+        TRMF_HIP_CHECK(hipDeviceSynchronize());
+        return autotune();
+    }
+    // ---- series churn (trmf_session_change_series; churn_kernels.hpp) ---------------------------------------------------------------
+    // Retires the series with keep[j] == 0 and adds the m series of Ynew (rows() x m; may be absent) in ONE new generation of
+    // storage: kept series keep their relative order and are renumbered densely from 0, the new ones follow.  The CSR side is
+    // compacted stably per row with the block's entries behind the survivors (csr_churn_kernel), the CSC side is whole-column
+    // copies (csc_gather_kernel) with the block's columns behind them, a dense Y -- or its raw copy under a transform -- is
+    // gathered by columns (dense_churn_kernel) and by rows (row_gather_kernel), H, the transform coefficients and the per-series
+    // loading statistics are row gathers, the held-out set is compacted by csr_churn_kernel over pseudo-rows.  fit: the new rows of H
+    // are the ridge of adapt_series' init pass run over the new columns only (the same kernels: adapt_series_kernel / adapt_part_kernel,
+    // or the full-observation forms with their one shared S), forget = the tables' gamma when they are carried, 1 otherwise.
+    // Afterwards the session is the one trmf_session_create would build from the churned entries in their stored order, the current
+    // W and lag weights and H = [H[keep]; H_new].  Failure-atomic like slide: everything is built in locals and committed at the end.
+    // churn_refusal() is the validation, run by the entry point on the calling thread before any rank's worker starts.  A pivot of
+    // the fit that is not positive and finite is not a failure of this rank's task (res->bad_series, nothing is committed).
+    struct ChurnResult {
+        uint64_t series_before = 0, series_retired = 0, series_added = 0, series = 0, entries_retired = 0, entries_added = 0, entries = 0, heldout_dropped = 0;
+        int fitted = 0, stats_carried = 0, bad_series = -1;
+        double sq_err_new = 0;
+    };
+    bool churn_carries_stats(int m, int fit) const { return ad_exists && ad_valid && ad_rows == T && !full && (m == 0 || fit); }
+    std::string churn_refusal(const uint8_t *keep, const PyMatrix *Yn, int fit, const void *Hnew, const real *tra, const real *trb) const {
+        if (fit != 0 && fit != 1) return "change_series: fit must be 0 or 1";
+        const int64_t m = Yn ? (int64_t)Yn->cols : 0;
+        int64_t nk = n;
+        uint64_t nzk = dense ? 0 : nnz;
+        if (keep) {
+            nk = 0; nzk = 0;
+            for (int j = 0; j < n; j++)
+                if (keep[j]) { nk++; if (!dense) nzk += host_col_ptr[j + 1] - host_col_ptr[j]; }
+        }
+        if (Yn) {
+            if ((Yn->type != TRMF_SPARSE) != dense) return "change_series: storage class (sparse/dense) differs from the session's";
+            if ((int64_t)Yn->rows != (int64_t)T)
+                return "change_series: the block has " + std::to_string((long long)Yn->rows) + " rows, the session holds " + std::to_string(T) + " (new series cover every timestamp held)";
+        }
+        if (nk + m == 0) return "change_series: no series would be left (keep is all zero and there is no block)";
+        if (fit && Hnew) return "change_series: fit together with Hnew (the fit computes the new loadings)";
+        if (fit && m > 0 && k > kMaxRank)
+            return "change_series: the cold-start fit covers the register-tiled ranks 1..64, this session has rank " + std::to_string(k) + " (fit = 0 works at every rank)";
+        if (!has_transform && (tra || trb)) return "change_series: transform coefficients given, but no series transform is set";
+        if (has_transform && m > 0) {
+            if (!tra || !trb) return "change_series: a series transform is set: the new series need both tr_a_new and tr_b_new";
+            for (int64_t j = 0; j < m; j++) {
+                if (!std::isfinite((double)tra[j]) || !std::isfinite((double)trb[j])) return "change_series: a transform coefficient of new series " + std::to_string((long long)j) + " is not finite";
+                if (tra[j] == real(0)) return "change_series: tr_a_new of new series " + std::to_string((long long)j) + " is zero (the transform could not be undone)";
+            }
+        }
+        const uint64_t n1 = (uint64_t)(nk + m);
+        if (n1 + 1 >= (1ull << 24) || (n1 + 1) * KP * sizeof(real) > 0xffffffffull) return "change_series: problem would exceed 32-bit device indices";
+        if (!dense && Yn) {
+            if ((uint64_t)Yn->row_ptr[(size_t)T] != Yn->nnz || (uint64_t)Yn->col_ptr[(size_t)m] != Yn->nnz)
+                return "change_series: the two orientations of the block hold different entry counts";
+            if (nzk + Yn->nnz >= (1ull << 32)) return "change_series: problem would exceed 32-bit device indices";
+            for (uint64_t e = 0; e < Yn->nnz; e++)
+                if ((int64_t)Yn->col_idx[e] >= m || (int64_t)Yn->row_idx[e] >= (int64_t)T) return "change_series: a block entry lies outside rows() x m";
+        }
+        return "";
+    }
+    // counts of the rows' survivors -> host (the caller has filled the `o*` fields and the remap of the arguments)
+    int churn_count(ChurnArgs &ca, DevBuf<uint32_t> &d_kept, std::vector<uint32_t> &kept) {
+        kept.assign((size_t)ca.nrows, 0u);
+        if (ca.nrows <= 0) return 0;
+        if (d_kept.alloc((size_t)ca.nrows, false)) return kFail;
+        ca.kept = d_kept.p;
+        hipLaunchKernelGGL(csr_churn_count_kernel, dim3((ca.nrows + 3) / 4), dim3(256), 0, stream, ca);
+        TRMF_HIP_CHECK(hipGetLastError());
+        const size_t bytes = kept.size() * sizeof(uint32_t);
+        std::unique_lock<std::mutex> lease;
+        unsigned char *pin = HostStager::current().staging(bytes, lease);
+        TRMF_HIP_CHECK(hipMemcpyAsync(pin ? (void *)pin : (void *)kept.data(), d_kept.p, bytes, hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (pin) std::memcpy(kept.data(), pin, bytes);
+        return 0;
+    }
+    int launch_row_gather(const real *src, const uint32_t *list, int nrows, size_t rowlen, real *dst) {
+        if (nrows <= 0 || rowlen == 0) return 0;
+        hipLaunchKernelGGL(row_gather_kernel, dim3((unsigned)std::min(4096, (nrows + 3) / 4)), dim3(256), 0, stream, src, list, nrows, rowlen, dst);
+        TRMF_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    int change_series(const uint8_t *keep, const PyMatrix *Yn, bool fit, const real *Hnew, const real *tra, const real *trb, ChurnResult *res) {
+        const int n0 = n, m = Yn ? (int)Yn->cols : 0;
+        ChurnResult out{};
+        out.series_before = out.series = (uint64_t)n0; out.entries = nnz;
+        if (!keep && m == 0) { if (res) *res = out; return 0; }
+        if (sync()) return kFail;
+        FillStreamScope fill(stream);
+        std::vector<uint32_t> remap((size_t)n0), list;
+        list.reserve((size_t)n0);
+        for (int j = 0; j < n0; j++) {
+            if (!keep || keep[j]) { remap[j] = (uint32_t)list.size(); list.push_back((uint32_t)j); }
+            else remap[j] = kChurnGone;
+        }
+        const int nk = (int)list.size(), n1 = nk + m;
+        const bool all_kept = nk == n0;
+        const bool do_fit = fit && m > 0, carry = churn_carries_stats(m, fit ? 1 : 0);
+        const uint64_t nzn = (Yn && !dense) ? Yn->nnz : 0;
+        uint64_t nzk = 0;
+        if (!dense) for (int q = 0; q < nk; q++) nzk += host_col_ptr[list[q] + 1] - host_col_ptr[list[q]];
+        const uint64_t new_nnz = dense ? (uint64_t)T * n1 : nzk + nzn;
+        {   // the new generation of buffers in ONE slab (the pool returns the previous generation's slab once it is wholly free)
+            const uint64_t nzsave = nnz;
+            n = n1; nnz = new_nnz;
+            const size_t fp = footprint_estimate();
+            n = n0; nnz = nzsave;
+            DevicePool::current().reserve(fp);
+        }
+        const size_t PK = adapt_packed(k);
+        std::vector<uint64_t> new_row_ptr, new_col_ptr;
+        double new_ysq = ysq_acc;
+        DevBuf<uint32_t> d_remap, d_list, ptr2, idx2, cptr2, cidx2, hrow2, hcol2, wptr, widx;
+        DevBuf<real> val2, cval2, tn2, nt2, raw2, H2, a2, b2, S2, r2, S3, r3, hval2, wval, blk_d, blk_tr, blk_nt, Hn, Hraw, Hpad, chg, om, slab, U, Sfull, rfull;
+        DevBuf<uint32_t> d_first, d_items;
+        DevBuf<int> flag;
+        DevBuf<double> errs, hpart2, trp;
+        uint64_t ho_m2 = ho_m;
+        const bool ho_churn = ho_set && !all_kept && ho_m > 0;
+        SyncStreamOnExit drain(stream);
+        if (d_remap.upload(remap.data(), remap.size()) || d_list.upload(list.data(), list.size())) return kFail;
+        const real *fit_blk = nullptr;              // dense storage: the block T x m row-major in the scale the session trains on
+        if (!dense) {
+            // CSC: the kept columns in order, each as stored, then the block's columns as delivered
+            new_col_ptr.assign((size_t)n1 + 1, 0);
+            for (int q = 0; q < nk; q++) new_col_ptr[q + 1] = new_col_ptr[q] + (host_col_ptr[list[q] + 1] - host_col_ptr[list[q]]);
+            for (int j = 0; j < m; j++) new_col_ptr[nk + j + 1] = new_col_ptr[nk + j] + (uint64_t)(Yn->col_ptr[j + 1] - Yn->col_ptr[j]);
+            std::vector<uint32_t> np32((size_t)n1 + 1);
+            for (int j = 0; j <= n1; j++) np32[j] = (uint32_t)new_col_ptr[j];
+            if (cptr2.upload(np32.data(), np32.size()) || cidx2.alloc(new_nnz, false) || cval2.alloc(new_nnz, false)) return kFail;
+            if (nk > 0) {
+                CscGatherArgs ga{Yc_ptr.p, Yc_idx.p, Yc_val.p, d_list.p, cptr2.p, cidx2.p, cval2.p, nk};
+                hipLaunchKernelGGL(csc_gather_kernel, dim3((nk + 3) / 4), dim3(256), 0, stream, ga);
+                TRMF_HIP_CHECK(hipGetLastError());
+            }
+            if (nzn) {
+                TRMF_HIP_CHECK(hipMemcpyAsync(cidx2.p + nzk, Yn->row_idx, nzn * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+                TRMF_HIP_CHECK(hipMemcpyAsync(cval2.p + nzk, Yn->val, nzn * sizeof(real), hipMemcpyHostToDevice, stream));
+            }
+            // CSR: every row = its entries of kept series in stored order, renumbered, then the block's entries of that row
+            ChurnArgs ca{};
+            ca.optr = Yr_ptr.p; ca.oidx = Yr_idx.p; ca.oval = Yr_val.p; ca.nrows = T; ca.shift = (uint32_t)nk;
+            ca.remap = all_kept ? nullptr : d_remap.p;
+            std::vector<uint32_t> kept;
+            DevBuf<uint32_t> d_kept;
+            if (!all_kept) { if (churn_count(ca, d_kept, kept)) return kFail; }
+            else { kept.resize((size_t)T); for (int i = 0; i < T; i++) kept[i] = (uint32_t)(host_row_ptr[i + 1] - host_row_ptr[i]); }
+            new_row_ptr.assign((size_t)T + 1, 0);
+            for (int i = 0; i < T; i++) new_row_ptr[i + 1] = new_row_ptr[i] + kept[i] + (m > 0 ? (uint64_t)(Yn->row_ptr[i + 1] - Yn->row_ptr[i]) : 0);
+            if (new_row_ptr[T] != new_nnz) { set_error("change_series: the two orientations of Y do not hold the same entries"); return kFail; }
+            if (upload_ptr32(ptr2, (const size_t *)new_row_ptr.data(), (size_t)T + 1) || idx2.alloc(new_nnz, false) || val2.alloc(new_nnz, false)) return kFail;
+            if (m > 0) {
+                if (upload_ptr32(wptr, Yn->row_ptr, (size_t)T + 1) || widx.upload(Yn->col_idx, nzn) || wval.upload((const real *)Yn->val_t, nzn)) return kFail;
+                ca.wptr = wptr.p; ca.widx = widx.p; ca.wval = wval.p;
+            }
+            ca.nptr = ptr2.p; ca.nidx = idx2.p; ca.nval = val2.p;
+            hipLaunchKernelGGL(csr_churn_kernel, dim3((T + 3) / 4), dim3(256), 0, stream, ca);
+            TRMF_HIP_CHECK(hipGetLastError());
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+            if (device_sum_squares(val2.p, new_nnz, &new_ysq)) return kFail;
+        } else {
+            std::vector<real> blk;
+            if (m > 0) { (void)dense_rows_to_rowmajor(Yn, blk); if (blk_d.upload(blk.data(), blk.size())) return kFail; }
+            const size_t N1 = (size_t)T * n1;
+            if (tn2.alloc(N1, false) || nt2.alloc(N1, false) || (has_transform && raw2.alloc(N1, false))) return kFail;
+            // the block is RAW data: under a transform the raw copy is churned and both orientations are re-derived after the commit
+            DenseChurnArgs da{has_transform ? Yraw.p : Yd_tn.p, d_list.p, m > 0 ? blk_d.p : nullptr, has_transform ? raw2.p : tn2.p, T, n0, nk, m};
+            hipLaunchKernelGGL(dense_churn_kernel, dim3((n1 + 255) / 256, (T + kChurnBand - 1) / kChurnBand), dim3(256), 0, stream, da);
+            TRMF_HIP_CHECK(hipGetLastError());
+            fit_blk = blk_d.p;
+            if (has_transform) {
+                if (a2.alloc((size_t)n1, false) || b2.alloc((size_t)n1, false)) return kFail;
+                if (launch_row_gather(tr_a.p, d_list.p, nk, 1, a2.p) || launch_row_gather(tr_b.p, d_list.p, nk, 1, b2.p)) return kFail;
+                if (m > 0) {
+                    TRMF_HIP_CHECK(hipMemcpyAsync(a2.p + nk, tra, (size_t)m * sizeof(real), hipMemcpyHostToDevice, stream));
+                    TRMF_HIP_CHECK(hipMemcpyAsync(b2.p + nk, trb, (size_t)m * sizeof(real), hipMemcpyHostToDevice, stream));
+                    if (do_fit || k <= kMaxRank) {        // the block in the trained scale, for the fit and the error sum (the bits apply_series_transform gives)
+                        if (blk_tr.alloc(blk.size(), false) || trp.alloc(1024)) return kFail;
+                        hipLaunchKernelGGL(affine_columns_kernel, dim3(1024), dim3(256), 0, stream, blk_d.p, (size_t)T, m, a2.p + nk, b2.p + nk, blk_tr.p, trp.p);
+                        TRMF_HIP_CHECK(hipGetLastError());
+                        fit_blk = blk_tr.p;
+                    }
+                }
+            } else {
+                // the n x T orientation: row copies of the kept series, the block transposed behind them
+                if (launch_row_gather(Yd_nt.p, d_list.p, nk, (size_t)T, nt2.p)) return kFail;
+                if (m > 0) launch_transpose(blk_d.p, T, m, nt2.p + (size_t)nk * T);
+                TRMF_HIP_CHECK(hipGetLastError());
+            }
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // blk is a local: its copy must have left the host
+            if (!has_transform && device_sum_squares(tn2.p, new_nnz, &new_ysq)) return kFail;    // over the new matrix, like a fresh session's
+        }
+        // H: the kept rows gathered, the new rows zero until the fit / the caller's values arrive (the pads and the extra row stay zero)
+        if (H2.alloc((size_t)(n1 + 1) * KP)) return kFail;
+        if (launch_row_gather(H.p, d_list.p, nk, (size_t)KP, H2.p)) return kFail;
+        real *Hnew_rows = H2.p + (size_t)nk * KP;
+        if (m > 0 && !do_fit && Hnew) {
+            if (Hraw.upload(Hnew, (size_t)m * k) || Hpad.alloc((size_t)(m + 1) * KP, false)) return kFail;
+            const size_t N = (size_t)(m + 1) * KP;
+            hipLaunchKernelGGL(factor_pad_kernel, dim3((unsigned)std::min<size_t>(4096, (N + 255) / 256)), dim3(256), 0, stream, Hraw.p, (size_t)m, k, KP, NT, Hpad.p);
+            TRMF_HIP_CHECK(hipGetLastError());
+            TRMF_HIP_CHECK(hipMemcpyAsync(Hnew_rows, Hpad.p, (size_t)m * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        }
+        // the loading statistics that are carried: the kept series' tables gathered (the new series' tables are the fit's output)
+        if (carry) {
+            if (S2.alloc((size_t)n1 * PK, false) || r2.alloc((size_t)n1 * k, false) || S3.alloc((size_t)n1 * PK, false) || r3.alloc((size_t)n1 * k, false)) return kFail;
+            if (launch_row_gather(ad_S[ad_cur].p, d_list.p, nk, PK, S2.p) || launch_row_gather(ad_r[ad_cur].p, d_list.p, nk, (size_t)k, r2.p)) return kFail;
+        }
+        if (do_fit) {    // the cold-start fit: adapt_series' init pass over the new columns, W as it is
+            const double gam = carry ? ad_gamma : 1.0;
+            std::vector<real> hom;
+            if (gam != 1.0) {
+                hom.resize((size_t)T);
+                for (int t = 0; t < T; t++) hom[t] = (real)std::pow(gam, (double)(T - 1 - t));
+            }
+            if (Hn.alloc((size_t)m * KP) || chg.alloc(m, false) || flag.alloc(1, false) || (!hom.empty() && om.upload(hom.data(), hom.size()))) return kFail;
+            TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
+            const real *omp = hom.empty() ? nullptr : om.p;
+            if (!full) {
+                // long columns are cut into items by the rule of the init pass on the churned problem (the bits of a fresh init)
+                std::vector<uint32_t> hfirst((size_t)m + 1), hitems;
+                uint64_t chunk = std::max<uint64_t>(kAdaptChunk, (new_nnz + kAdaptMaxItems - 1) / kAdaptMaxItems);
+                if (const char *e = test_env("TRMF_ADAPT_CHUNK")) chunk = (uint64_t)std::max(1, atoi(e));
+                for (int j = 0; j < m; j++) {
+                    hfirst[j] = (uint32_t)(hitems.size() / 2);
+                    const uint64_t c0 = new_col_ptr[nk + j], c1 = new_col_ptr[nk + j + 1];
+                    if (c1 - c0 > chunk)
+                        for (uint64_t b = c0; b < c1; b += chunk) { hitems.push_back((uint32_t)b); hitems.push_back((uint32_t)std::min<uint64_t>(b + chunk, c1)); }
+                }
+                hfirst[m] = (uint32_t)(hitems.size() / 2);
+                const uint32_t nitems = (uint32_t)(hitems.size() / 2);
+                if (nitems && (d_first.upload(hfirst.data(), hfirst.size()) || d_items.upload(hitems.data(), hitems.size()) ||
+                               slab.alloc((size_t)nitems * adapt_part_reals(k), false))) return kFail;
+                if (!carry && (Sfull.alloc((size_t)m * PK, false) || rfull.alloc((size_t)m * k, false))) return kFail;
+                AdaptArgs a{cptr2.p + nk, cidx2.p, cval2.p, cptr2.p + nk, W.p, omp, nullptr, nullptr, carry ? S2.p + (size_t)nk * PK : Sfull.p,
+                            carry ? r2.p + (size_t)nk * k : rfull.p, nitems ? d_first.p : nullptr, nitems ? d_items.p : nullptr, nitems ? slab.p : nullptr,
+                            Hnew_rows, Hn.p, chg.p, flag.p, real(1), (real)lambdaI, 0, m, k, KP};
+                if (!with_nt(NT, [&](auto N) {
+                        if (nitems) hipLaunchKernelGGL(adapt_part_kernel<decltype(N)::value>, dim3(nitems), dim3(64), 0, stream, a);
+                        hipLaunchKernelGGL(adapt_series_kernel<decltype(N)::value>, dim3(m), dim3(64), 0, stream, a);
+                    })) return unsupported_rank();
+            } else {
+                if (Sfull.alloc(PK, false) || rfull.alloc((size_t)m * k, false) || U.alloc((size_t)k * k, false)) return kFail;
+                if (dense) {      // the m x T orientation of the block in the trained scale
+                    if (blk_nt.alloc((size_t)T * m, false)) return kFail;
+                    launch_transpose(fit_blk, T, m, blk_nt.p);
+                }
+                AdaptFullArgs a{dense ? nullptr : cptr2.p + nk, dense ? nullptr : cidx2.p, dense ? nullptr : cval2.p, dense ? nullptr : cptr2.p + nk,
+                                dense ? blk_nt.p : nullptr, W.p, omp, nullptr, nullptr, Sfull.p, rfull.p, U.p, Hnew_rows, Hn.p, chg.p, real(1), 0, T, m, k, KP, NT};
+                hipLaunchKernelGGL(adapt_full_gram_kernel, dim3((unsigned)((PK + 255) / 256)), dim3(256), 0, stream, a);
+                hipLaunchKernelGGL(adapt_full_rhs_kernel, dim3((m + 3) / 4), dim3(256), 0, stream, a);
+                AssimFactorArgs fa{Sfull.p, (size_t)0, 1, U.p, flag.p, (real)lambdaI, 0, 1, k};       // the one shared system: "series 0" names it
+                if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3(1), dim3(256), 0, stream, fa); }))
+                    return unsupported_rank();
+                hipLaunchKernelGGL(adapt_full_subst_kernel, dim3((m + 3) / 4), dim3(256), 0, stream, a);
+            }
+            TRMF_HIP_CHECK(hipGetLastError());
+            int bad = kAdaptNoBadSeries;
+            TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+            if (bad != kAdaptNoBadSeries) { out.bad_series = bad; if (res) *res = out; return 0; }
+            TRMF_HIP_CHECK(hipMemcpyAsync(Hnew_rows, Hn.p, (size_t)m * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
+        }
+        if (m > 0 && k <= kMaxRank) {   // the new series' squared error with their new loadings (assim_err_kernel's reading of an entry), row order
+            if (errs.alloc((size_t)2 * T, false)) return kFail;
+            AssimErrArgs ea{dense ? nullptr : wptr.p, dense ? nullptr : widx.p, dense ? nullptr : wval.p, dense ? fit_blk : nullptr, Hnew_rows,
+                            W.p, W.p, 0, 0, errs.p, 0, T, m, KP, dense ? 1 : 0};
+            hipLaunchKernelGGL(assim_err_kernel, dim3(T), dim3(256), 0, stream, ea);
+            TRMF_HIP_CHECK(hipGetLastError());
+            std::vector<double> herr((size_t)2 * T);
+            TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, herr.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+            for (int i = 0; i < T; i++) out.sq_err_new += herr[2 * i];
+        }
+        if (ho_churn) {  // held-out positions in retired series are dropped, the rest renumbered: the COO list as pseudo-rows of kSlideChunk entries
+            const int nch = (int)((ho_m + kSlideChunk - 1) / kSlideChunk);
+            std::vector<uint32_t> cp((size_t)nch + 1), hk, np((size_t)nch + 1, 0u);
+            for (int c = 0; c <= nch; c++) cp[c] = (uint32_t)std::min<uint64_t>((uint64_t)c * kSlideChunk, ho_m);
+            DevBuf<uint32_t> d_cp, d_np, d_kept;
+            ChurnArgs ha{};
+            if (d_cp.upload(cp.data(), cp.size())) return kFail;
+            ha.optr = d_cp.p; ha.oidx = ho_col.p; ha.oval = ho_val.p; ha.oaux = ho_row.p; ha.remap = d_remap.p; ha.nrows = nch;
+            if (churn_count(ha, d_kept, hk)) return kFail;
+            for (int c = 0; c < nch; c++) np[c + 1] = np[c] + hk[c];
+            ho_m2 = np[nch];
+            if (d_np.upload(np.data(), np.size()) || hrow2.alloc(ho_m2, false) || hcol2.alloc(ho_m2, false) || hval2.alloc(ho_m2, false)) return kFail;
+            ha.nptr = d_np.p; ha.nidx = hcol2.p; ha.nval = hval2.p; ha.naux = hrow2.p;
+            hipLaunchKernelGGL(csr_churn_kernel, dim3((nch + 3) / 4), dim3(256), 0, stream, ha);
+            TRMF_HIP_CHECK(hipGetLastError());
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // (the pointer arrays are locals)
+        }
+        int ho_nb2 = ho_nb; uint64_t ho_chunk2 = ho_chunk;
+        if (ho_churn) { heldout_geometry(ho_m2, &ho_nb2, &ho_chunk2); if (hpart2.alloc((size_t)kHoSums * ho_nb2, false)) return kFail; }
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        // ---- commit ----
+        out.series_retired = (uint64_t)(n0 - nk); out.series_added = (uint64_t)m; out.series = (uint64_t)n1;
+        out.entries_retired = dense ? (uint64_t)T * (n0 - nk) : nnz - nzk; out.entries_added = dense ? (uint64_t)T * m : nzn; out.entries = new_nnz;
+        out.heldout_dropped = ho_churn ? ho_m - ho_m2 : 0;
+        out.fitted = do_fit ? 1 : 0; out.stats_carried = carry ? 1 : 0;
+        if (!dense) {
+            Yr_ptr.swap(ptr2); Yr_idx.swap(idx2); Yr_val.swap(val2);
+            Yc_ptr.swap(cptr2); Yc_idx.swap(cidx2); Yc_val.swap(cval2);
+        } else {
+            Yd_tn.swap(tn2); Yd_nt.swap(nt2);
+            if (has_transform) { Yraw.swap(raw2); tr_a.swap(a2); tr_b.swap(b2); }
+        }
+        H.swap(H2);
+        if (ad_exists) {
+            if (carry) {
+                ad_S[ad_cur].swap(S2); ad_r[ad_cur].swap(r2); ad_S[1 - ad_cur].swap(S3); ad_r[1 - ad_cur].swap(r3);
+                std::vector<uint32_t> cnt((size_t)n1);
+                for (int j = 0; j < n1; j++) cnt[j] = (uint32_t)(new_col_ptr[j + 1] - new_col_ptr[j]);
+                ad_cnt.swap(cnt);
+            } else {                                  // the tables describe another set of series: stale, and their memory goes back
+                for (int q = 0; q < 2; q++) { ad_S[q].release(); ad_r[q].release(); }
+                ad_cnt.clear();
+                adapt_stale();
+            }
+        }
+        if (ho_churn) {
+            ho_row.swap(hrow2); ho_col.swap(hcol2); ho_val.swap(hval2); ho_part.swap(hpart2); ho_pred.release();
+            ho_m = ho_m2; ho_nb = ho_nb2; ho_chunk = ho_chunk2;
+        }
+        for (int q = 0; q < 2; q++) { fc_table[q].release(); fc_prev[q].release(); iv_table[q].release(); }      // per-series sums of another set of series
+        fc_cur = 0; fc_rows = 0; iv_cur = 0; iv_rows = 0;
+        nz_sigma2.release(); nz_q.release(); nz_set = false;
+        markW.release(); markH.release(); markT.release(); mark_iter = -1;         // a mark names series that have moved
+        snapW.release(); snapH.release(); snapT.release(); snap_iter = -1;
+        if (!dense) { host_row_ptr.swap(new_row_ptr); host_col_ptr.swap(new_col_ptr); }
+        if (res) *res = out;
+        n = n1; nnz = new_nnz; ysq_acc = new_ysq;
+        if (dense && has_transform && apply_series_transform()) return kFail;     // current coefficients over the new raw matrix
+        set_trYTY();
+        iter = 0;
+        if (gramx_mode != kGramxReplicate && comm->world > 1 && !test_env("TRMF_GRAMX")) { gramx_mode = kGramxMeasure; gramx_calls = 0; }
+        if (fs_mode != kShardOff && comm->world > 1 && !test_env("TRMF_FSHARD")) { fs_mode = kShardMeasure; fs_calls = 0; }
+        if (alloc_series_scratch() || alloc_time_scratch()) return kFail;
         TRMF_HIP_CHECK(hipDeviceSynchronize());
         return autotune();
     }
@@ -1835,7 +2177,7 @@ struct TrmfSessionImpl : SessionXPhase {
         const double gam = init ? forget : ad_gamma;
         const int row0 = init ? 0 : ad_rows, m = T - row0;
         const size_t PK = adapt_packed(k), nS = full ? PK : (size_t)n * PK, nR = (size_t)n * k;
-        if (init && !ad_exists) {
+        if (init && (!ad_exists || ad_S[0].n != nS || ad_r[0].n != nR)) {      // (change_series releases stale tables: the series count moved)
             if (ad_S[0].alloc(nS, false) || ad_S[1].alloc(nS, false) || ad_r[0].alloc(nR, false) || ad_r[1].alloc(nR, false)) {
                 for (int q = 0; q < 2; q++) { ad_S[q].release(); ad_r[q].release(); }
                 res->no_memory = 1;

@@ -202,7 +202,7 @@ struct SessionState {
 
     // ---- held-out positions (trmf_session_set_heldout / _eval_heldout; heldout_kernels.hpp) -------------------------------------
     // COO in the caller's CSR order, resident until replaced; append_rows leaves it alone, slide drops the positions in retired
-    // rows and shifts the rest (csc_slide_kernel).
+    // rows and shifts the rest (csc_slide_kernel), change_series drops those in retired series and renumbers the rest (csr_churn_kernel).
     bool ho_set = false;
     uint64_t ho_m = 0, ho_chunk = kHoStep;
     int ho_nb = 1;                            // workgroups of one evaluation: kHoSums partials each in ho_part
@@ -233,7 +233,8 @@ struct SessionState {
     // rank.  Two generations: a call reads ad_cur and writes the other, and ad_cur moves only once the flag has been read.  ad_cnt:
     // sparse storage, the stored entries of each column already absorbed (append_rows puts new entries behind them).  Stale once
     // a row they absorbed may have changed (adapt_stale(): run, rewind, assimilate below ad_rows, a new series transform) or rows
-    // they never absorbed have been retired (slide past ad_rows).
+    // they never absorbed have been retired (slide past ad_rows).  change_series carries them -- kept series gathered, new series from
+    // its fit -- when they are valid, per series and have absorbed every row; otherwise it releases them and leaves them stale.
     DevBuf<real> ad_S[2], ad_r[2];
     std::vector<uint32_t> ad_cnt;
     int ad_cur = 0, ad_rows = 0;

@@ -398,6 +398,43 @@ int32_t trmf_session_slide(TrmfSession *s, const PyMatrix *Ynew, int32_t retire,
     }
     return rc;
 }
+// Series churn: validated here like slide; a pivot of the cold-start fit that is not positive is found by every rank alike and
+// reported here, not by a failing worker task.
+int32_t trmf_session_change_series(TrmfSession *s, const uint8_t *keep, const PyMatrix *Ynew, int32_t fit, const void *Hnew, const void *tr_a_new,
+                                   const void *tr_b_new, TrmfChurnSums *out) {
+    if (!s) { set_error("null session"); return kFail; }
+    const std::string why = HND(s)->first()->churn_refusal(keep, Ynew, fit, Hnew, (const real *)tr_a_new, (const real *)tr_b_new);
+    if (!why.empty()) { set_error(why); return kFail; }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    const bool grouped = HND(s)->group != nullptr;
+    std::vector<TrmfSessionImpl::ChurnResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
+    if (HND(s)->all([&](TrmfSessionImpl *t) {
+            return t->change_series(keep, Ynew, fit != 0, (const real *)Hnew, (const real *)tr_a_new, (const real *)tr_b_new, &res[grouped ? t->comm->rank : 0]);
+        })) return kFail;
+    for (const auto &r : res)
+        if (r.bad_series >= 0) {
+            const TrmfSessionImpl *f = HND(s)->first();
+            set_error((f->full ? std::string("change_series: the new series' shared system") : "change_series: new series " + std::to_string(r.bad_series)) +
+                      ": a pivot of S + lambdaI I is not positive and finite (lambdaI == 0 and a new series with fewer independent rows than the "
+                      "rank?); nothing was changed");
+            return kFail;
+        }
+    if (out) {
+        const auto &r = res[0];
+        out->series_before = r.series_before; out->series_retired = r.series_retired; out->series_added = r.series_added; out->series = r.series;
+        out->entries_retired = r.entries_retired; out->entries_added = r.entries_added; out->entries = r.entries;
+        out->heldout_dropped = r.heldout_dropped; out->fitted = r.fitted; out->stats_carried = r.stats_carried; out->sq_err_new = r.sq_err_new;
+    }
+    return 0;
+}
+int32_t trmf_session_row_entries(TrmfSession *s, uint64_t *per_row) {
+    if (!s || !per_row) { set_error("null argument"); return kFail; }
+    const TrmfSessionImpl *f = HND(s)->first();
+    if (f->dense) { set_error("row_entries: dense storage holds every cell"); return kFail; }
+    for (int i = 0; i < f->T; i++) per_row[i] = f->host_row_ptr[(size_t)i + 1] - f->host_row_ptr[(size_t)i];
+    return 0;
+}
 int32_t trmf_session_rows(TrmfSession *s) { return s ? HND(s)->first()->T : kFail; }
 int32_t trmf_session_set_series_transform(TrmfSession *s, const void *a, const void *b) {
     if (!s) { set_error("null session"); return kFail; }

@@ -8,6 +8,7 @@ the fixed-interval smoother adds ``smooth_rows``, ``window_objective`` (and ``Se
 the robust smoother adds ``robust_smooth_rows``, ``robust_window_objective`` (and ``Session.smooth_robust``, ``smooth_robust=True``);
 robust online loading updates add ``robust_series_objective`` (and ``SeriesStats.absorb_robust``, ``Session.adapt_series_robust``, ``adapt_robust=True``);
 the sliding window adds ``slide_entries`` (and ``SeriesStats.retire``, ``Session.slide``, ``Session.retire_rows``, ``Session.update(window=)``);
+series churn adds ``churn_entries`` (and ``Session.change_series``, ``Session.add_series``, ``Session.retire_series``, ``Model.add_series``, ``Model.retire_series``);
 forecast uncertainty adds ``fit_noise``, ``impulse_response``, ``forecast_std`` and ``IntervalMetrics`` (and ``Model.fit_noise``,
 ``Model.forecast_std``, ``Session.forecast_dist``).
 """
@@ -15,8 +16,8 @@ from .trmf import Model, Metrics
 from .trmf import train, fit, rolling_validate, grid_search
 from .impute import ImputeMetrics, impute, grid_impute
 from .online import (filter_rows, robust_filter_rows, series_ridge, SeriesStats, smooth_rows, window_objective, robust_smooth_rows,
-                     robust_window_objective, robust_series_objective, slide_entries)
+                     robust_window_objective, robust_series_objective, slide_entries, churn_entries)
 from .uncertainty import IntervalMetrics, fit_noise, forecast_std, impulse_response
 
-__all__ = ['Model', 'Metrics', 'train', 'fit', 'rolling_validate', 'grid_search', 'ImputeMetrics', 'impute', 'grid_impute', 'filter_rows', 'robust_filter_rows', 'series_ridge', 'SeriesStats', 'smooth_rows', 'window_objective', 'robust_smooth_rows', 'robust_window_objective', 'robust_series_objective', 'slide_entries',
+__all__ = ['Model', 'Metrics', 'train', 'fit', 'rolling_validate', 'grid_search', 'ImputeMetrics', 'impute', 'grid_impute', 'filter_rows', 'robust_filter_rows', 'series_ridge', 'SeriesStats', 'smooth_rows', 'window_objective', 'robust_smooth_rows', 'robust_window_objective', 'robust_series_objective', 'slide_entries', 'churn_entries',
            'fit_noise', 'impulse_response', 'forecast_std', 'IntervalMetrics']

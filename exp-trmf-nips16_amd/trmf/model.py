@@ -282,6 +282,47 @@ class Model(object):
         self.series_stats = SeriesStats(self.W, Y, forget, missing)
         return self
 
+    # ---- series churn ------------------------------------------------------------------------------
+    def _transform_of(self, a, b):
+        import copy
+        tr = copy.copy(self.transform)
+        tr.a, tr.b = a, b
+        return tr
+
+    def retire_series(self, which):
+        """A new ``Model`` without the series ``which`` (a list of indices or a mask of ``n`` flags): the kept rows of H in their
+        order, W, the lag weights and the lag set as they are, the transform's coefficients gathered (the host form of
+        ``Session.retire_series``).  Series statistics and a fitted noise are not carried."""
+        from .session import check_keep
+        keep = check_keep(which, self.n, retire=True)
+        if not keep.any():
+            raise ValueError('retire_series: no series would be left')
+        tr = None if self.transform is None else self._transform_of(np.asarray(self.transform.a)[:, keep], np.asarray(self.transform.b)[:, keep])
+        return Model.from_arrays(self.W.copy(), np.ascontiguousarray(self.H[keep]), self.lag_val.copy(), self.lag_set.copy(), transform=tr)
+
+    def add_series(self, Ynew, lambdaI, missing=True, forget=1.0, transform_new=None):
+        """A new ``Model`` grown by the ``Ynew.shape[1]`` series of ``Ynew`` (``m`` rows: the new series over every timestamp of
+        this model; raw values): their loadings are the cold-start ridge ``trmf.series_ridge(W, Ynew, lambdaI, forget, missing)``
+        with W as it is, appended behind the rows of H (the host form of ``Session.add_series``).  A model with a transform needs
+        ``transform_new`` (an object with ``a``, ``b`` of the new series, e.g. ``NormalizedTransform(Ynew)``), which is applied to
+        ``Ynew`` first and appended to the model's."""
+        from .online import series_ridge
+        if Ynew.shape[0] != self.m:
+            raise ValueError('add_series: Ynew has {} rows, the model {}'.format(Ynew.shape[0], self.m))
+        tr = None
+        if self.transform is not None:
+            if transform_new is None:
+                raise ValueError('add_series: this model has a series transform: the new series need transform_new')
+            if smat.issparse(Ynew):
+                raise ValueError('add_series: a series transform needs dense rows')
+            Ynew = transform_new.preprocess(np.asarray(Ynew)).astype(self.W.dtype)
+            tr = self._transform_of(np.concatenate([np.asarray(self.transform.a), np.asarray(transform_new.a)], axis=1),
+                                    np.concatenate([np.asarray(self.transform.b), np.asarray(transform_new.b)], axis=1))
+        elif transform_new is not None:
+            raise ValueError('add_series: transform_new given, but this model has no series transform')
+        Hn = series_ridge(self.W, Ynew, lambdaI, forget, missing)
+        return Model.from_arrays(self.W.copy(), np.ascontiguousarray(np.vstack([self.H, Hn])), self.lag_val.copy(), self.lag_set.copy(), transform=tr)
+
     # ---- construction ------------------------------------------------------------------------------
     @staticmethod
     def syn_gen(m, n, k, lag_set, seed=None, noise=0.01, dtype=np.float32):

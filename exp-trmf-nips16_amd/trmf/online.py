@@ -423,6 +423,47 @@ def slide_entries(rows, cols, vals, retire):
     return rows[keep] - rows.dtype.type(retire), cols[keep].copy(), vals[keep].copy()
 
 
+# ---- series churn (trmf_session_change_series) -----------------------------------------------------------------------------------
+def churn_entries(rows, cols, vals, keep, n, block=None, major='row'):
+    """What a stored list of entries becomes when series leave and a block of new series joins: the stored-order rule of
+    ``trmf_session_change_series``.  ``keep`` is a mask of ``n`` flags (``None``: every series stays); the kept series keep their
+    relative order and are renumbered densely from 0.  The entries of kept series survive in their STORED order with the new
+    numbers (a stable filter -- the lists need not be sorted and a cell may be stored twice).  ``block = (rows, cols, vals)``
+    holds the entries of the new series, numbered from 0 within the block, in the stored order of the same orientation: they
+    get the numbers ``n_kept + cols`` and are merged stably behind the survivors of the same ``major`` index -- ``major='row'``
+    (the CSR arrays: every row is its survivors, then the block's entries of that row) or ``major='col'`` (the CSC arrays: the
+    kept columns in order, each as stored, then the block's columns as delivered).  Without a block the survivors are returned
+    as filtered, whatever their order.  Returns ``(rows, cols, vals)`` as new arrays."""
+    rows, cols, vals = np.asarray(rows), np.asarray(cols), np.asarray(vals)
+    n = int(n)
+    if not (rows.shape == cols.shape == vals.shape and rows.ndim == 1):
+        raise ValueError('churn_entries: rows, cols and vals must be one-dimensional arrays of one length')
+    if major not in ('row', 'col'):
+        raise ValueError("churn_entries: major must be 'row' or 'col', not {!r}".format(major))
+    if keep is None:
+        keep = np.ones(n, dtype=bool)
+    keep = np.asarray(keep)
+    if keep.shape != (n,):
+        raise ValueError('churn_entries: keep must hold {} flags, not {}'.format(n, keep.shape))
+    keep = keep.astype(bool)
+    if cols.size and (cols.min() < 0 or cols.max() >= n):
+        raise ValueError('churn_entries: a column index lies outside 0..{}'.format(n - 1))
+    remap = np.cumsum(keep) - 1
+    stay = keep[cols] if cols.size else np.zeros(0, dtype=bool)
+    r, c, v = rows[stay].copy(), remap[cols[stay]].astype(cols.dtype), vals[stay].copy()
+    if block is None:
+        return r, c, v
+    br, bc, bv = (np.asarray(a) for a in block)
+    if not (br.shape == bc.shape == bv.shape and br.ndim == 1):
+        raise ValueError('churn_entries: the block must be three one-dimensional arrays of one length')
+    if bc.size and bc.min() < 0:
+        raise ValueError('churn_entries: a column index of the block is negative')
+    nk = int(np.count_nonzero(keep))
+    r = np.concatenate([r, br.astype(r.dtype)]); c = np.concatenate([c, (bc + nk).astype(c.dtype)]); v = np.concatenate([v, bv.astype(v.dtype)])
+    order = np.argsort(r if major == 'row' else c, kind='stable')
+    return r[order], c[order], v[order]
+
+
 # ---- online loading updates: the rows of H refitted from new rows (trmf_session_series_stats_init / _adapt_series) ---------------
 def _series_entries(Y, missing):
     """Per series the (timestamps, values) of its observations in stored order.  Sparse ``Y``: the stored entries of the column

@@ -102,6 +102,17 @@ class TrmfSlideSums(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class TrmfChurnSums(ctypes.Structure):
+    _fields_ = [('series_before', c_uint64), ('series_retired', c_uint64), ('series_added', c_uint64), ('series', c_uint64),
+                ('entries_retired', c_uint64), ('entries_added', c_uint64), ('entries', c_uint64), ('heldout_dropped', c_uint64),
+                ('fitted', c_int32), ('stats_carried', c_int32), ('sq_err_new', c_double)]
+
+    def as_dict(self):
+        out = {name: int(getattr(self, name)) for name, _ in self._fields_[:8]}
+        out.update(fitted=bool(self.fitted), stats_carried=bool(self.stats_carried), sq_err_new=float(self.sq_err_new))
+        return out
+
+
 class TrmfRobustAdaptSums(ctypes.Structure):
     """Sums of a robust online loading update (include/trmf_abi.h): those of ``TrmfAdaptSums``, the number of down-weighted
     entries and the sum of the weights of the last sweep, the Huber objective ``sum_j J_j`` before / after."""
@@ -221,6 +232,10 @@ def bind(lib):
     if hasattr(lib, 'trmf_session_slide'):            # (absent from libraries built before the sliding window)
         lib.trmf_session_slide.argtypes = [c_void_p, P, c_int32, c_int32, POINTER(TrmfSlideSums)]; lib.trmf_session_slide.restype = c_int32
         lib.trmf_device_pool_live_bytes.restype = ctypes.c_int64
+    if hasattr(lib, 'trmf_session_change_series'):    # (absent from libraries built before series churn)
+        lib.trmf_session_change_series.argtypes = [c_void_p, c_void_p, P, c_int32, c_void_p, c_void_p, c_void_p, POINTER(TrmfChurnSums)]
+        lib.trmf_session_change_series.restype = c_int32
+        lib.trmf_session_row_entries.argtypes = [c_void_p, c_void_p]; lib.trmf_session_row_entries.restype = c_int32
     if hasattr(lib, 'trmf_session_fit_noise'):        # (absent from libraries built before the forecast uncertainty)
         lib.trmf_session_fit_noise.argtypes = [c_void_p, POINTER(TrmfNoiseStats)]; lib.trmf_session_fit_noise.restype = c_int32
         lib.trmf_session_noise.argtypes = [c_void_p, c_void_p, c_void_p]; lib.trmf_session_noise.restype = c_int32
@@ -269,6 +284,32 @@ def check_retire(retire):
     if retire < 0:
         raise ValueError('retire must not be negative, not {}'.format(retire))
     return int(retire)
+
+
+def check_keep(keep, n, retire=False):
+    """The front end's argument check of ``change_series``: ``keep`` as a boolean mask of ``n`` flags (``None``: all set).  A mask is
+    an array of ``n`` booleans; with ``retire`` the argument names the series that LEAVE instead -- such a mask, or a list of distinct
+    indices in ``0..n-1`` -- and the complement is returned."""
+    n = int(n)
+    if keep is None:
+        return np.ones(n, dtype=bool)
+    a = np.asarray(keep)
+    if a.dtype == bool:
+        if a.shape != (n,):
+            raise ValueError('a mask of {} flags was expected, not one of shape {}'.format(n, a.shape))
+        return ~a if retire else a.copy()
+    if not retire:
+        raise TypeError('keep must be a boolean mask of {} flags, not {!r}'.format(n, a.dtype))
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise TypeError('which must be a boolean mask or a list of integer indices, not {!r}'.format(keep))
+    a = a.astype(np.int64)
+    if a.size and (a.min() < 0 or a.max() >= n):
+        raise ValueError('a series index lies outside 0..{}'.format(n - 1))
+    if np.unique(a).size != a.size:
+        raise ValueError('a series index is listed twice')
+    mask = np.ones(n, dtype=bool)
+    mask[a] = False
+    return mask
 
 
 def check_window(window, block_rows, smooth_back, reach):
@@ -384,6 +425,8 @@ class Session(object):
         if self._stored is not None:
             self._stored = np.concatenate([self._stored[retire:]] + ([_stored_per_row(block)] if block is not None else []))
         if retire and getattr(self, '_heldout_rows', None) is not None:
+            if getattr(self, '_heldout_cols', None) is not None:
+                self._heldout_cols = self._heldout_cols[self._heldout_rows >= retire]
             self._heldout_rows = self._heldout_rows[self._heldout_rows >= retire] - retire
             self._heldout_nnz = int(self._heldout_rows.size)
         old = self.model
@@ -396,6 +439,83 @@ class Session(object):
     def retire_rows(self, count, downdate_stats=False):
         """``slide`` without a block: retire the ``count`` oldest rows."""
         return self.slide(None, count, downdate_stats)
+
+    def change_series(self, keep=None, Ynew=None, fit=True, H=None, transform_new=None):
+        """Series churn on the device: retire the series whose flag in ``keep`` (a boolean mask of n flags; ``None``: keep all) is
+        unset and add the series of ``Ynew`` (``rows()`` x m, the new series over every timestamp held, same storage class as the
+        session's Y, raw values; ``None``: nothing).  Kept series keep their order and are renumbered densely from 0, the new ones
+        follow.  Afterwards the session is the one a fresh ``Session`` would be on the churned entries in their stored order
+        (``trmf.churn_entries``), the current W and lag weights and ``H = [H[keep]; H_new]``.  ``fit`` (ranks up to 64): the new
+        loadings are the cold-start ridge ``trmf.series_ridge(W, Ynew, lambdaI, forget, missing)`` computed on the device, ``forget``
+        that of the series statistics when they are carried (valid, per series, every row absorbed) and 1 otherwise; without it
+        -- or with ``H`` given, which takes the fit's place -- they are ``H`` (m x k) or zeros.  ``transform_new`` (``a``, ``b`` of the new series): needed iff a series transform is
+        set.  Held-out positions of retired series are dropped; the forecast and interval scores are reset; a fitted noise is
+        invalidated (``fit_noise`` again); the mark is released.  ``self.model`` is replaced by a host model of the new series
+        count (H rows gathered, new rows zero until ``download()``).  Returns the sums as a dict.  A refused call raises and leaves
+        the session as it was."""
+        n = self.model.n
+        mask = None if keep is None else check_keep(keep, n)
+        if not hasattr(self.lib, 'trmf_session_change_series'):
+            raise RuntimeError('change_series: the loaded library was built before series churn')
+        dt = self.model.W.dtype
+        block = None
+        if Ynew is not None:
+            block = Ynew if isinstance(Ynew, PyMatrix) else PyMatrix(Ynew, dtype=dt)
+        m = int(block.cols) if block is not None else 0
+        fit = bool(fit) and block is not None and H is None
+        Hn = None
+        if H is not None:
+            Hn = np.ascontiguousarray(np.asarray(H))
+            if Hn.dtype != dt or Hn.shape != (m, self.model.k):
+                raise ValueError('change_series: H is {} {}, {} x {} of {} was expected'.format(Hn.shape, Hn.dtype, m, self.model.k, dt))
+        ta = tb = None
+        if transform_new is not None:
+            ta = np.ascontiguousarray(np.asarray(transform_new.a).ravel())
+            tb = np.ascontiguousarray(np.asarray(transform_new.b, dtype=dt).ravel())
+            if ta.dtype != dt or ta.shape != (m,) or tb.shape != (m,):
+                raise ValueError('change_series: transform_new must hold {} coefficients of {}'.format(m, dt))
+        flags = None if mask is None else np.ascontiguousarray(mask.astype(np.uint8))
+        sums = TrmfChurnSums()
+        self._check(self.lib.trmf_session_change_series(
+            self.handle, flags.ctypes.data if flags is not None else None, byref(block) if block is not None else None, 1 if fit else 0,
+            Hn.ctypes.data if Hn is not None else None, ta.ctypes.data if ta is not None else None, tb.ctypes.data if tb is not None else None,
+            byref(sums)), 'trmf_session_change_series')
+        if mask is None and block is None:
+            return sums.as_dict()
+        if mask is None:
+            mask = np.ones(n, dtype=bool)
+        if self._stored is not None:       # sparse storage: the survivors of a row are known to the library
+            per_row = np.zeros(self.rows(), dtype=np.uint64)
+            self._check(self.lib.trmf_session_row_entries(self.handle, per_row.ctypes.data), 'trmf_session_row_entries')
+            self._stored = per_row.astype(np.int64)
+        if getattr(self, '_heldout_cols', None) is not None and not mask.all():
+            stay = mask[self._heldout_cols]
+            self._heldout_rows = self._heldout_rows[stay]
+            self._heldout_cols = (np.cumsum(mask) - 1)[self._heldout_cols[stay]]
+            self._heldout_nnz = int(self._heldout_rows.size)
+        old = self.model
+        Hhost = np.zeros((int(sums.series), old.k), dtype=dt, order='C')
+        Hhost[:int(mask.sum())] = old.H[mask]
+        if Hn is not None:
+            Hhost[int(mask.sum()):] = Hn
+        tr = old.transform
+        if tr is not None:
+            import copy
+            tr = copy.copy(tr)
+            a_old, b_old = np.asarray(old.transform.a), np.asarray(old.transform.b)
+            tr.a = np.concatenate([a_old[:, mask]] + ([np.asarray(transform_new.a).reshape(1, -1)] if m else []), axis=1)
+            tr.b = np.concatenate([b_old[:, mask]] + ([np.asarray(transform_new.b).reshape(1, -1)] if m else []), axis=1)
+        self.model = type(old).from_arrays(old.W.copy(), Hhost, old.lag_val.copy(), old.lag_set.copy(), transform=tr)
+        self.model.pyW.type, self.model.pyH.type = old.pyW.type, old.pyH.type      # (a (rows, 1) array is both memory orders: keep the tag)
+        return sums.as_dict()
+
+    def add_series(self, Ynew, fit=True, H=None, transform_new=None):
+        """``change_series`` that only adds: the series of ``Ynew`` join behind the resident ones."""
+        return self.change_series(None, Ynew, fit, H, transform_new)
+
+    def retire_series(self, which):
+        """``change_series`` that only retires: ``which`` is a list of series indices or a boolean mask of the series that leave."""
+        return self.change_series(check_keep(which, self.model.n, retire=True))
 
     def pool_live_bytes(self):
         """Bytes of device memory that live buffers of this process hold in the library's pool right now."""
@@ -698,7 +818,7 @@ class Session(object):
         zeros included, are the cells to score, in the scale the session trains on.  ``None`` drops the set."""
         if Ytest is None:
             self._check(self.lib.trmf_session_set_heldout(self.handle, None), 'trmf_session_set_heldout')
-            self._heldout_nnz = self._heldout_rows = None
+            self._heldout_nnz = self._heldout_rows = self._heldout_cols = None
             return self
         if isinstance(Ytest, PyMatrix):
             pyT = Ytest
@@ -709,6 +829,7 @@ class Session(object):
         self._check(self.lib.trmf_session_set_heldout(self.handle, byref(pyT)), 'trmf_session_set_heldout')
         self._heldout_nnz = int(pyT.nnz)
         self._heldout_rows = np.repeat(np.arange(int(pyT.rows), dtype=np.int64), _stored_per_row(pyT))     # (slide drops the retired rows' cells)
+        self._heldout_cols = np.ctypeslib.as_array(pyT.col_idx, shape=(int(pyT.nnz),)).astype(np.int64) if pyT.nnz else np.zeros(0, np.int64)     # (change_series drops the retired series' cells)
         return self
 
     def eval_heldout_sums(self, predictions=False):

@@ -233,6 +233,66 @@ TRMF_API int32_t trmf_session_append_rows(TrmfSession *s, const PyMatrix *Ynew);
 typedef struct { uint64_t rows_retired, entries_retired, rows_appended, entries_appended, rows, entries; } TrmfSlideSums;
 TRMF_API int32_t trmf_session_slide(TrmfSession *s, const PyMatrix *Ynew /* or NULL */, int32_t retire, int32_t downdate_stats,
                                     TrmfSlideSums *out /* or NULL */);
+/* Series churn: retire series (columns of Y, rows of H) of a resident session and add a block of new ones, in one new generation of
+ * storage; only the block crosses PCIe.  keep: n flags (non-zero: the series stays), NULL keeps all.  Ynew: rows() x m, the m new
+ * series over ALL timestamps the session holds, same storage class as the session's Y (raw data under a series transform), NULL:
+ * nothing to add.  Kept series keep their relative order and are renumbered densely from 0; the m new series follow them.
+ *
+ * Contract: afterwards the session is the one trmf_session_create would build from
+ *   - the churned entries in their STORED order in both orientations: every CSR row = its entries of kept series with the series
+ *     renumbered, then the block's entries of that row at series + n_kept; the CSC = the kept columns in order, each as stored,
+ *     then the block's columns as delivered (the input need not be a canonical CSR/CSC pair: the compactions are stable).  Dense
+ *     storage: both orientations (and the raw copy under a transform) hold the kept columns followed by the block,
+ *   - the current W and lag weights, lambdas, lag penalty,
+ *   - H = [H[keep]; H_new], the transform coefficients [a[keep]; tr_a_new], [b[keep]; tr_b_new],
+ * and every later call returns the bits it returns on that fresh session.  The iteration counter restarts, as after append_rows
+ * and slide.  Everything sized by the number of series is re-derived the way trmf_session_create derives it (F-row partition, split
+ * rows, scratch, the measure-once decisions).  Blocking; with a communicator active every rank makes the same call.  Failure-atomic:
+ * a refused or failed call leaves the session exactly as it was.
+ *
+ * H_new.  fit == 1 (ranks 1..64): every new series' loadings are fitted on the device from the resident W over all rows() rows,
+ *   h_j = (S_j + lambdaI I)^-1 r_j,   S_j = sum_t om_t w_t w_t^T,   r_j = sum_t om_t y_tj w_t,   om_t = forget^(rows - 1 - t)
+ * by the kernels of trmf_session_series_stats_init / _adapt_series run over the new columns (sums in stored order in the element
+ * type, the same Cholesky and substitutions): sparse storage with missing != 0 sums over the stored entries of column j, the
+ * full-observation forms (sparse with missing == 0, dense) over every timestamp with one shared S.  forget is the series
+ * statistics' when they are carried (below), 1 otherwise.  A new series without entries gets h = 0 exactly when lambdaI > 0; with
+ * lambdaI == 0 a system that is not positive definite is refused, the message names the new series.  fit == 0: Hnew (m x k,
+ * row-major) or, NULL, zeros.
+ *
+ * Other resident state.  Series statistics: when they are valid, have absorbed every row (absorbed_rows == rows()), are per series
+ * (sparse storage with missing != 0) and the call fits (or adds nothing), the kept series' tables are gathered and the new series'
+ * tables are the ones the fit built, so a later adapt_series goes on from them; in every other case existing statistics become
+ * stale.  Held-out positions in retired series are dropped, the others renumbered.  The forecast and interval score tables are
+ * reset (rows_scored 0).  A fitted or set noise is invalidated: trmf_session_fit_noise / _set_noise must be called again.  The mark
+ * is released.  W, the lag weights and the iteration log stay.
+ *
+ * out: series_before / series_retired / series_added / series and entries_retired / entries_added / entries count series and
+ * stored entries (dense: cells); heldout_dropped the held-out positions lost; fitted / stats_carried say what the call did;
+ * sq_err_new = sum over the new series' stored entries of (y - w_t . h_j)^2 with the new loadings, in fp64 (ranks 1..64, else 0).
+ *
+ * Refused (trmf_last_error(); the session stays usable): keep all zero with no block; a block whose row count differs from rows();
+ * a storage class that differs from the session's; fit together with Hnew; fit with a block at rank above 64 (fit == 0 works at
+ * every rank); a series transform set without both tr_a_new and tr_b_new, coefficients given without a transform, a coefficient that
+ * is not finite, a zero in tr_a_new (y -> a y + b is undone by dividing by a; b may be zero: a centred series); a block entry
+ * outside rows() x m; sizes beyond the 32-bit device indices; a block whose two orientations hold different entry counts.
+ * keep == NULL with Ynew == NULL is a no-op that returns 0. */
+typedef struct {
+    uint64_t series_before, series_retired, series_added, series;
+    uint64_t entries_retired, entries_added, entries;
+    uint64_t heldout_dropped;
+    int32_t  fitted;        /* the new series' loadings were fitted by the call */
+    int32_t  stats_carried; /* the loading statistics are still valid */
+    double   sq_err_new;    /* fp64: sum over the new series' stored entries of (y - w_t.h_j)^2, with the new loadings */
+} TrmfChurnSums;
+TRMF_API int32_t trmf_session_change_series(TrmfSession *s, const uint8_t *keep /* n flags, or NULL: keep all */,
+                                            const PyMatrix *Ynew /* rows() x m, same storage class, or NULL */,
+                                            int32_t fit /* 1: fit the new loadings on the device */,
+                                            const void *Hnew /* m x k row-major, or NULL (fit == 0: NULL means zeros) */,
+                                            const void *tr_a_new, const void *tr_b_new /* m each: needed iff a series transform is set */,
+                                            TrmfChurnSums *out /* or NULL */);
+/* Stored entries per timestamp of a sparse session's Y right now (rows() values; what sizes the per-entry weights of the robust
+ * calls after series have been retired).  -1 for dense storage. */
+TRMF_API int32_t trmf_session_row_entries(TrmfSession *s, uint64_t *per_row /* rows() */);
 /* Train on a[i] * y + b[i] of series (column) i instead of the raw dense Y the session holds (missing == 0 only):
  * the per-window NormalizedTransform of the reference's rolling_validate(transform=True) (python/trmf/trmf.py:82-96,
  * 237-249, 253-257), which rescales every entry of the growing prefix.  The session keeps the raw matrix (rows passed
