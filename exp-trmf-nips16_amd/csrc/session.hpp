@@ -1,7 +1,8 @@
 // session.hpp -- host side of the MI355X TRMF solver: set-up of the HBM-resident problem (asynchronous, one synchronisation),
-// growth by appended rows, the measure-once decisions, the outer ALS loop (trmf.cpp:599-694) as asynchronous kernel launches
-// on one HIP stream, recovery from a timed-out persistent kernel, statistics.  State and the phases live in the layers below
-// (session_state.hpp lists them).
+// the measure-once decisions, the outer ALS loop (trmf.cpp:599-694) as asynchronous kernel launches on one HIP stream, recovery
+// from a timed-out persistent kernel, statistics, held-out evaluation, forecasts and their noise model.  State and the phases live
+// in the layers below, the calls that change a resident session between runs (growth by appended rows, the sliding window, series
+// churn, the online solves) in the layer above, session_online.hpp (session_state.hpp lists all of them).
 //
 // With several ranks (one process per GPU) the nnz-heavy kernels (F-solve, X-side Gram, loss) run on this rank's contiguous row
 // block; the CG runs replicated or sharded over time (DESIGN.md "Multi-GPU").
@@ -13,8 +14,8 @@ extern "C" char **environ;      // (the TRMF_* environment is part of the key of
 
 namespace trmf {
 
-struct TrmfSessionImpl : SessionXPhase {
-    ~TrmfSessionImpl() {
+struct SessionCore : SessionXPhase {
+    ~SessionCore() {
         // nothing of this session may still be running when its buffers go back to the pool and its stream to the cache
         if (stream) (void)hipStreamSynchronize(stream);
         if (side) (void)hipStreamSynchronize(side);
@@ -421,598 +422,12 @@ struct TrmfSessionImpl : SessionXPhase {
         return 0;
     }
 
-    // ---- append new timestamps (trmf_session_append_rows; the rolling-window caller trmf.py:303-329) ---------------
-    // Ynew: Tn x n block of NEW timestamps, same storage class as the session's Y.  Only that block (plus, for a
-    // sparse Y, one 4-byte pointer per item) crosses PCIe: the CSR gains rows at its end, the CSC -- whose columns
-    // each gain entries at their tails -- is rebuilt on the device from the old CSC and the block's CSC, a dense Y's
-    // n x T copy is re-strided on the device, and W is extended by the AR recursion with the current Theta
-    // (Model.latent_forecast, trmf.py:170-181, the reference's warm start :237-246).  H and Theta are kept.
-    // The iteration counter restarts (a new train() call in the reference, trmf.cpp:647).
-    int append_rows(const PyMatrix *Yn) {
-        const int Tn = (int)Yn->rows, T0 = T;
-        if ((int)Yn->cols != n) { set_error("append_rows: column count differs from the session's"); return kFail; }
-        if ((Yn->type != TRMF_SPARSE) != dense) { set_error("append_rows: storage class (sparse/dense) differs from the session's"); return kFail; }
-        if ((uint64_t)(T0 + Tn + 1) >= (1ull << 24) || (uint64_t)(T0 + Tn + 1) * KP * sizeof(real) > 0xffffffffull ||
-            nnz + Yn->nnz >= (1ull << 32)) { set_error("append_rows: problem would exceed 32-bit device indices"); return kFail; }
-        if (Tn <= 0) return 0;
-        return slide(Yn, 0, false, nullptr);       // the growing case of the sliding window: one code path, the same bits
-    }
-
-    // ---- the sliding window (trmf_session_slide; slide_kernels.hpp) ---------------------------------------------------------------
-    // Appends Ynew (as append_rows does; may be absent) and retires the `retire` oldest timestamps in ONE new generation of storage:
-    // the CSR side, a dense Y (and its raw copy under a transform) and W are suffix copies, the CSC side is compacted stably per
-    // column with the block's entries behind the survivors, the held-out set is compacted by the same kernel, and -- downdate -- the
-    // loading statistics lose the retired entries' terms (read from the storage and the W of BEFORE the slide, written to the
-    // inactive generation).  Afterwards the session is the one trmf_session_create would build from the retained entries in their
-    // stored order, W[retire:] + the block's AR roll-out and the current H, Theta, weights and transform.  Failure-atomic like
-    // append_rows: everything is built in locals and committed at the end.  slide_refusal() is the validation, run by the entry
-    // point on the calling thread before any rank's worker starts (a refused call must not break the barrier of a TRMF_DEVICES group).
-    struct SlideResult { uint64_t rows_retired = 0, entries_retired = 0, rows_appended = 0, entries_appended = 0, rows = 0, entries = 0; };
-    std::string slide_refusal(const PyMatrix *Yn, int retire, int downdate) const {
-        if (retire < 0) return "slide: retire must not be negative";
-        if (downdate != 0 && downdate != 1) return "slide: downdate_stats must be 0 or 1";
-        const int64_t Tn = Yn ? (int64_t)Yn->rows : 0;
-        if (Yn) {
-            if ((int)Yn->cols != n) return "slide: column count differs from the session's";
-            if ((Yn->type != TRMF_SPARSE) != dense) return "slide: storage class (sparse/dense) differs from the session's";
-        }
-        if (retire > T) return "slide: cannot retire " + std::to_string(retire) + " rows, the session holds " + std::to_string(T) + " (rows of the block itself cannot be retired)";
-        const int64_t T1 = (int64_t)T + Tn - retire;
-        if (T1 < (int64_t)midx + 1)
-            return "slide: retiring " + std::to_string(retire) + " rows would leave " + std::to_string(T1) + ", fewer than the largest lag + 1 = " + std::to_string(midx + 1);
-        const uint64_t gone = dense ? 0 : host_row_ptr[(size_t)retire] - host_row_ptr[0];
-        if ((uint64_t)(T1 + 1) >= (1ull << 24) || (uint64_t)(T1 + 1) * KP * sizeof(real) > 0xffffffffull || (!dense && nnz - gone + (Yn ? Yn->nnz : 0) >= (1ull << 32)))
-            return "slide: problem would exceed 32-bit device indices";
-        if (downdate) {
-            if (full) return "slide: downdate_stats needs per-series statistics (sparse storage with missing != 0); the full-observation forms share one S";
-            if (!ad_exists || !ad_valid) return "slide: downdate_stats without valid series statistics (trmf_session_series_stats_init)";
-        }
-        return "";
-    }
     void heldout_geometry(uint64_t m, int *nb, uint64_t *chunk) const {
         // equal contiguous chunks, a multiple of one workgroup step each: the work of a workgroup does not depend on row lengths
         *nb = (int)std::max<uint64_t>(1, std::min<uint64_t>(kHoMaxBlocks, (m + 255) / 256));
         *chunk = ((m + *nb - 1) / *nb + kHoStep - 1) / kHoStep * kHoStep;
         if (*chunk == 0) *chunk = kHoStep;
         *nb = (int)std::max<uint64_t>(1, (m + *chunk - 1) / *chunk);
-    }
-    // counts of the columns' survivors -> host (retire > 0; the caller has filled the `o*` fields of the arguments)
-    int slide_count(SlideArgs &sa, DevBuf<uint32_t> &d_kept, std::vector<uint32_t> &kept) {
-        kept.assign((size_t)sa.ncols, 0u);
-        if (sa.ncols <= 0) return 0;
-        if (d_kept.alloc((size_t)sa.ncols, false)) return kFail;
-        sa.kept = d_kept.p;
-        hipLaunchKernelGGL(csc_slide_count_kernel, dim3((sa.ncols + 3) / 4), dim3(256), 0, stream, sa);
-        TRMF_HIP_CHECK(hipGetLastError());
-        // through the library's pinned staging when it is to be had (a copy into pageable memory is staged by the runtime)
-        const size_t bytes = kept.size() * sizeof(uint32_t);
-        std::unique_lock<std::mutex> lease;
-        unsigned char *pin = HostStager::current().staging(bytes, lease);
-        TRMF_HIP_CHECK(hipMemcpyAsync(pin ? (void *)pin : (void *)kept.data(), d_kept.p, bytes, hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        if (pin) std::memcpy(kept.data(), pin, bytes);
-        return 0;
-    }
-    int slide(const PyMatrix *Yn, int retire, bool downdate, SlideResult *res) {
-        const int Tn = Yn ? (int)Yn->rows : 0, T0 = T, Tk = T0 - retire, T1 = Tk + Tn;
-        SlideResult out{};
-        out.rows = (uint64_t)T0; out.entries = nnz;
-        if (Tn <= 0 && retire == 0) { if (res) *res = out; return 0; }
-        FillStreamScope fill(stream);
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        const uint64_t nzn = (Yn && !dense) ? Yn->nnz : 0;
-        const uint64_t cut = dense ? 0 : host_row_ptr[(size_t)retire];        // CSR rows are contiguous: the retired entries are a prefix
-        {   // the new generation of buffers in ONE slab (the pool returns the previous generation's slab once it is wholly free)
-            const int Tsave = T; const uint64_t nzsave = nnz;
-            T = T1; nnz = dense ? (uint64_t)T1 * n : nnz - cut + nzn;
-            const size_t fp = footprint_estimate();
-            T = Tsave; nnz = nzsave;
-            DevicePool::current().reserve(fp);
-        }
-        // Failure-atomic: everything new is built in locals (device buffers, host pointer arrays, sums) and swapped into
-        // the session only after every allocation, copy and kernel of the step has succeeded; a failed call leaves the
-        // session exactly as it was.
-        std::vector<uint64_t> new_row_ptr, new_col_ptr;
-        std::vector<uint32_t> kept;                   // sparse storage, retire > 0: the survivors of every column
-        uint64_t new_nnz = nnz;
-        double new_ysq = ysq_acc;
-        DevBuf<uint32_t> ptr2, idx2, cptr2, cidx2, hrow2, hcol2; DevBuf<real> val2, cval2, tn2, nt2, raw2, W2, hval2;
-        uint64_t ho_m2 = ho_m;
-        const bool ho_slide = ho_set && retire > 0 && ho_m > 0;
-        const bool ad_down = downdate && retire > 0 && retire <= ad_rows;      // (retiring past the absorbed rows leaves the tables stale)
-        SyncStreamOnExit drain(stream);
-        if (!dense) {
-            const uint64_t nz0 = nnz, nzk = nz0 - cut, nz1 = nzk + nzn;
-            // CSR: the retained rows move to the front with their pointers rebased, the block's rows follow
-            new_row_ptr.reserve((size_t)T1 + 1);
-            for (int i = retire; i <= T0; i++) new_row_ptr.push_back(host_row_ptr[(size_t)i] - cut);
-            for (int i = 1; i <= Tn; i++) new_row_ptr.push_back(nzk + Yn->row_ptr[i]);
-            if (upload_ptr32(ptr2, (const size_t *)new_row_ptr.data(), (size_t)T1 + 1) || idx2.alloc(nz1, false) || val2.alloc(nz1, false)) return kFail;
-            if (nzk) {
-                TRMF_HIP_CHECK(hipMemcpyAsync(idx2.p, Yr_idx.p + cut, nzk * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-                TRMF_HIP_CHECK(hipMemcpyAsync(val2.p, Yr_val.p + cut, nzk * sizeof(real), hipMemcpyDeviceToDevice, stream));
-            }
-            if (nzn) {
-                TRMF_HIP_CHECK(hipMemcpyAsync(idx2.p + nzk, Yn->col_idx, nzn * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                TRMF_HIP_CHECK(hipMemcpyAsync(val2.p + nzk, Yn->val_t, nzn * sizeof(real), hipMemcpyHostToDevice, stream));
-            }
-            // CSC: column j = its surviving entries in their stored order (timestamps reduced by `retire`), then the block's entries
-            // of that column (timestamps shifted to follow the retained rows)
-            SlideArgs sa{};
-            sa.optr = Yc_ptr.p; sa.oidx = Yc_idx.p; sa.oval = Yc_val.p; sa.ncols = n; sa.retire = (uint32_t)retire; sa.shift = (uint32_t)Tk;
-            DevBuf<uint32_t> d_kept;
-            if (retire > 0) { if (slide_count(sa, d_kept, kept)) return kFail; }
-            else { kept.resize((size_t)n); for (int j = 0; j < n; j++) kept[j] = (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j]); }
-            new_col_ptr.assign((size_t)n + 1, 0);
-            std::vector<uint32_t> np32((size_t)n + 1);
-            for (int j = 0; j < n; j++) new_col_ptr[j + 1] = new_col_ptr[j] + kept[j] + (Yn ? (uint64_t)(Yn->col_ptr[j + 1] - Yn->col_ptr[j]) : 0);
-            for (int j = 0; j <= n; j++) np32[j] = (uint32_t)new_col_ptr[j];
-            if (new_col_ptr[n] != nz1) { set_error("slide: the two orientations of Y do not hold the same entries"); return kFail; }
-            DevBuf<uint32_t> wptr, widx; DevBuf<real> wval;
-            SyncStreamOnExit drain_block(stream);
-            if (cptr2.upload(np32.data(), np32.size()) || cidx2.alloc(nz1, false) || cval2.alloc(nz1, false)) return kFail;
-            if (Yn && (upload_ptr32(wptr, Yn->col_ptr, (size_t)n + 1) || widx.upload(Yn->row_idx, nzn) || wval.upload((const real *)Yn->val, nzn))) return kFail;
-            if (Yn) { sa.wptr = wptr.p; sa.widx = widx.p; sa.wval = wval.p; }
-            sa.nptr = cptr2.p; sa.nidx = cidx2.p; sa.nval = cval2.p;
-            hipLaunchKernelGGL(csc_slide_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, sa);
-            TRMF_HIP_CHECK(hipGetLastError());
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-            new_nnz = nz1;
-            if (device_sum_squares(val2.p, new_nnz, &new_ysq)) return kFail;
-        } else {
-            std::vector<real> blk;
-            if (Yn) (void)dense_rows_to_rowmajor(Yn, blk);
-            const size_t nk = (size_t)Tk * n;
-            if (tn2.alloc((size_t)T1 * n, false) || nt2.alloc((size_t)T1 * n, false)) return kFail;
-            if (nk) TRMF_HIP_CHECK(hipMemcpyAsync(tn2.p, Yd_tn.p + (size_t)retire * n, nk * sizeof(real), hipMemcpyDeviceToDevice, stream));
-            if (!blk.empty()) TRMF_HIP_CHECK(hipMemcpyAsync(tn2.p + nk, blk.data(), blk.size() * sizeof(real), hipMemcpyHostToDevice, stream));
-            if (has_transform) {                        // the block is RAW data: slide the raw copy, re-derive below
-                if (raw2.alloc((size_t)T1 * n, false)) return kFail;
-                if (nk) TRMF_HIP_CHECK(hipMemcpyAsync(raw2.p, Yraw.p + (size_t)retire * n, nk * sizeof(real), hipMemcpyDeviceToDevice, stream));
-                if (!blk.empty()) TRMF_HIP_CHECK(hipMemcpyAsync(raw2.p + nk, blk.data(), blk.size() * sizeof(real), hipMemcpyHostToDevice, stream));
-            }
-            launch_transpose(tn2.p, T1, n, nt2.p);
-            TRMF_HIP_CHECK(hipGetLastError());
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // blk is a local: its copies must have left the host
-            new_nnz = (uint64_t)T1 * n;
-            if (device_sum_squares(tn2.p, new_nnz, &new_ysq)) return kFail;    // over the new matrix, like a fresh session's
-        }
-        if (ad_down) {   // the retired entries' terms leave the tables: old storage, old W, active generation -> the other one
-            std::vector<real> hom;
-            if (ad_gamma != 1.0) {
-                hom.resize((size_t)retire);
-                for (int t = 0; t < retire; t++) hom[t] = -(real)std::pow(ad_gamma, (double)(ad_rows - 1 - t));
-            }
-            DevBuf<uint32_t> d_abs; DevBuf<real> om;
-            if (d_abs.upload(ad_cnt.data(), ad_cnt.size()) || (!hom.empty() && om.upload(hom.data(), hom.size()))) return kFail;
-            DowndateArgs da{Yc_ptr.p, Yc_idx.p, Yc_val.p, d_abs.p, W.p, hom.empty() ? nullptr : om.p, ad_S[ad_cur].p, ad_r[ad_cur].p,
-                            ad_S[1 - ad_cur].p, ad_r[1 - ad_cur].p, (uint32_t)retire, n, k, KP};
-            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(series_downdate_kernel<decltype(N)::value>, dim3(n), dim3(64), 0, stream, da); }))
-                return unsupported_rank();
-            TRMF_HIP_CHECK(hipGetLastError());
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // (d_abs and om are locals)
-        }
-        if (ho_slide) {  // held-out positions in retired rows are dropped, the rest shifted: the COO list as pseudo-columns of kSlideChunk entries
-            const int nch = (int)((ho_m + kSlideChunk - 1) / kSlideChunk);
-            std::vector<uint32_t> cp((size_t)nch + 1), hk, np((size_t)nch + 1, 0u);
-            for (int c = 0; c <= nch; c++) cp[c] = (uint32_t)std::min<uint64_t>((uint64_t)c * kSlideChunk, ho_m);
-            DevBuf<uint32_t> d_cp, d_np, d_kept;
-            SlideArgs sa{};
-            if (d_cp.upload(cp.data(), cp.size())) return kFail;
-            sa.optr = d_cp.p; sa.oidx = ho_row.p; sa.oval = ho_val.p; sa.oaux = ho_col.p; sa.ncols = nch; sa.retire = (uint32_t)retire;
-            if (slide_count(sa, d_kept, hk)) return kFail;
-            for (int c = 0; c < nch; c++) np[c + 1] = np[c] + hk[c];
-            ho_m2 = np[nch];
-            if (d_np.upload(np.data(), np.size()) || hrow2.alloc(ho_m2, false) || hcol2.alloc(ho_m2, false) || hval2.alloc(ho_m2, false)) return kFail;
-            sa.nptr = d_np.p; sa.nidx = hrow2.p; sa.nval = hval2.p; sa.naux = hcol2.p;
-            hipLaunchKernelGGL(csc_slide_kernel, dim3((nch + 3) / 4), dim3(256), 0, stream, sa);
-            TRMF_HIP_CHECK(hipGetLastError());
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // (the pointer arrays are locals)
-        }
-        DevBuf<double> hpart2;
-        int ho_nb2 = ho_nb; uint64_t ho_chunk2 = ho_chunk;
-        if (ho_slide) { heldout_geometry(ho_m2, &ho_nb2, &ho_chunk2); if (hpart2.alloc((size_t)kHoSums * ho_nb2, false)) return kFail; }
-        {   // W: the retained rows, Tn rows rolled out by the AR model, one all-zero row at the end
-            if (W2.alloc((size_t)(T1 + 1) * KP)) return kFail;
-            if (Tn > 0 && retire > 0 && Tk < midx && k <= kMaxRank) {
-                // the roll-out reads rows that are being retired: roll out behind the old rows first, then keep the suffix
-                DevBuf<real> Wf;
-                SyncStreamOnExit drain_w(stream);
-                if (Wf.alloc((size_t)(T0 + Tn + 1) * KP)) return kFail;
-                TRMF_HIP_CHECK(hipMemcpyAsync(Wf.p, W.p, (size_t)T0 * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-                hipLaunchKernelGGL(latent_forecast_kernel, dim3(1), dim3(64), 0, stream, Wf.p, T0, T0 + Tn, KP, NT, k, lag_set.p, nlag, theta.p);
-                TRMF_HIP_CHECK(hipGetLastError());
-                TRMF_HIP_CHECK(hipMemcpyAsync(W2.p, Wf.p + (size_t)retire * KP, (size_t)T1 * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-                TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-            } else {
-                if (Tk) TRMF_HIP_CHECK(hipMemcpyAsync(W2.p, W.p + (size_t)retire * KP, (size_t)Tk * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-                // rank <= 64: the one-wavefront kernel this path has always used (its digests stay); above: the forecast's roll-out,
-                // which covers every rank (the one-wavefront kernel rolled only the first 64 columns forward) and reads the OLD rows
-                if (Tn > 0 && k <= kMaxRank) {
-                    hipLaunchKernelGGL(latent_forecast_kernel, dim3(1), dim3(64), 0, stream, W2.p, Tk, T1, KP, NT, k, lag_set.p, nlag, theta.p);
-                    TRMF_HIP_CHECK(hipGetLastError());
-                } else if (Tn > 0 && launch_rollout(W.p, T0, Tn, W2.p + (size_t)Tk * KP, nullptr)) return kFail;
-                TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-            }
-        }
-        // ---- commit ----
-        if (!dense) {
-            Yr_ptr.swap(ptr2); Yr_idx.swap(idx2); Yr_val.swap(val2);
-            Yc_ptr.swap(cptr2); Yc_idx.swap(cidx2); Yc_val.swap(cval2);
-            if (retire > 0 && ad_exists)            // the absorbed entries stay a prefix of every column: it lost the retired ones
-                for (int j = 0; j < n && (size_t)j < ad_cnt.size(); j++) {
-                    const uint32_t lost = (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j]) - kept[j];
-                    ad_cnt[j] -= std::min(ad_cnt[j], lost);
-                }
-            host_row_ptr.swap(new_row_ptr); host_col_ptr.swap(new_col_ptr);
-        } else {
-            Yd_tn.swap(tn2); Yd_nt.swap(nt2);
-            if (has_transform) Yraw.swap(raw2);
-        }
-        W.swap(W2);
-        if (retire > 0) {
-            if (ad_exists) {
-                if (retire > ad_rows) adapt_stale();    // rows the tables never absorbed are gone: they no longer describe a prefix
-                else if (ad_down) ad_cur = 1 - ad_cur;
-                ad_rows = std::max(0, ad_rows - retire);
-            }
-            if (ho_slide) {
-                ho_row.swap(hrow2); ho_col.swap(hcol2); ho_val.swap(hval2); ho_part.swap(hpart2); ho_pred.release();
-                ho_m = ho_m2; ho_nb = ho_nb2; ho_chunk = ho_chunk2;
-            }
-            markW.release(); markH.release(); markT.release(); mark_iter = -1;     // a mark names rows that have moved
-            snapW.release(); snapH.release(); snapT.release(); snap_iter = -1;
-        }
-        out.rows_retired = (uint64_t)retire; out.entries_retired = dense ? (uint64_t)retire * n : cut;
-        out.rows_appended = (uint64_t)Tn; out.entries_appended = dense ? (uint64_t)Tn * n : nzn;
-        out.rows = (uint64_t)T1; out.entries = new_nnz;
-        if (res) *res = out;
-        nnz = new_nnz; ysq_acc = new_ysq;
-        T = T1;
-        if (dense && has_transform && apply_series_transform()) return kFail;   // current coefficients over the new raw matrix
-        set_trYTY();
-        iter = 0;
-        if (gramx_mode != kGramxReplicate && comm->world > 1 && !test_env("TRMF_GRAMX")) { gramx_mode = kGramxMeasure; gramx_calls = 0; }
-        if (alloc_time_scratch()) return kFail;
-        TRMF_HIP_CHECK(hipDeviceSynchronize());
-        return autotune();
-    }
-    // ---- series churn (trmf_session_change_series; churn_kernels.hpp) ---------------------------------------------------------------
-    // Retires the series with keep[j] == 0 and adds the m series of Ynew (rows() x m; may be absent) in ONE new generation of
-    // storage: kept series keep their relative order and are renumbered densely from 0, the new ones follow.  The CSR side is
-    // compacted stably per row with the block's entries behind the survivors (csr_churn_kernel), the CSC side is whole-column
-    // copies (csc_gather_kernel) with the block's columns behind them, a dense Y -- or its raw copy under a transform -- is
-    // gathered by columns (dense_churn_kernel) and by rows (row_gather_kernel), H, the transform coefficients and the per-series
-    // loading statistics are row gathers, the held-out set is compacted by csr_churn_kernel over pseudo-rows.  fit: the new rows of H
-    // are the ridge of adapt_series' init pass run over the new columns only (the same kernels: adapt_series_kernel / adapt_part_kernel,
-    // or the full-observation forms with their one shared S), forget = the tables' gamma when they are carried, 1 otherwise.
-    // Afterwards the session is the one trmf_session_create would build from the churned entries in their stored order, the current
-    // W and lag weights and H = [H[keep]; H_new].  Failure-atomic like slide: everything is built in locals and committed at the end.
-    // churn_refusal() is the validation, run by the entry point on the calling thread before any rank's worker starts.  A pivot of
-    // the fit that is not positive and finite is not a failure of this rank's task (res->bad_series, nothing is committed).
-    struct ChurnResult {
-        uint64_t series_before = 0, series_retired = 0, series_added = 0, series = 0, entries_retired = 0, entries_added = 0, entries = 0, heldout_dropped = 0;
-        int fitted = 0, stats_carried = 0, bad_series = -1;
-        double sq_err_new = 0;
-    };
-    bool churn_carries_stats(int m, int fit) const { return ad_exists && ad_valid && ad_rows == T && !full && (m == 0 || fit); }
-    std::string churn_refusal(const uint8_t *keep, const PyMatrix *Yn, int fit, const void *Hnew, const real *tra, const real *trb) const {
-        if (fit != 0 && fit != 1) return "change_series: fit must be 0 or 1";
-        const int64_t m = Yn ? (int64_t)Yn->cols : 0;
-        int64_t nk = n;
-        uint64_t nzk = dense ? 0 : nnz;
-        if (keep) {
-            nk = 0; nzk = 0;
-            for (int j = 0; j < n; j++)
-                if (keep[j]) { nk++; if (!dense) nzk += host_col_ptr[j + 1] - host_col_ptr[j]; }
-        }
-        if (Yn) {
-            if ((Yn->type != TRMF_SPARSE) != dense) return "change_series: storage class (sparse/dense) differs from the session's";
-            if ((int64_t)Yn->rows != (int64_t)T)
-                return "change_series: the block has " + std::to_string((long long)Yn->rows) + " rows, the session holds " + std::to_string(T) + " (new series cover every timestamp held)";
-        }
-        if (nk + m == 0) return "change_series: no series would be left (keep is all zero and there is no block)";
-        if (fit && Hnew) return "change_series: fit together with Hnew (the fit computes the new loadings)";
-        if (fit && m > 0 && k > kMaxRank)
-            return "change_series: the cold-start fit covers the register-tiled ranks 1..64, this session has rank " + std::to_string(k) + " (fit = 0 works at every rank)";
-        if (!has_transform && (tra || trb)) return "change_series: transform coefficients given, but no series transform is set";
-        if (has_transform && m > 0) {
-            if (!tra || !trb) return "change_series: a series transform is set: the new series need both tr_a_new and tr_b_new";
-            for (int64_t j = 0; j < m; j++) {
-                if (!std::isfinite((double)tra[j]) || !std::isfinite((double)trb[j])) return "change_series: a transform coefficient of new series " + std::to_string((long long)j) + " is not finite";
-                if (tra[j] == real(0)) return "change_series: tr_a_new of new series " + std::to_string((long long)j) + " is zero (the transform could not be undone)";
-            }
-        }
-        const uint64_t n1 = (uint64_t)(nk + m);
-        if (n1 + 1 >= (1ull << 24) || (n1 + 1) * KP * sizeof(real) > 0xffffffffull) return "change_series: problem would exceed 32-bit device indices";
-        if (!dense && Yn) {
-            if ((uint64_t)Yn->row_ptr[(size_t)T] != Yn->nnz || (uint64_t)Yn->col_ptr[(size_t)m] != Yn->nnz)
-                return "change_series: the two orientations of the block hold different entry counts";
-            if (nzk + Yn->nnz >= (1ull << 32)) return "change_series: problem would exceed 32-bit device indices";
-            for (uint64_t e = 0; e < Yn->nnz; e++)
-                if ((int64_t)Yn->col_idx[e] >= m || (int64_t)Yn->row_idx[e] >= (int64_t)T) return "change_series: a block entry lies outside rows() x m";
-        }
-        return "";
-    }
-    // counts of the rows' survivors -> host (the caller has filled the `o*` fields and the remap of the arguments)
-    int churn_count(ChurnArgs &ca, DevBuf<uint32_t> &d_kept, std::vector<uint32_t> &kept) {
-        kept.assign((size_t)ca.nrows, 0u);
-        if (ca.nrows <= 0) return 0;
-        if (d_kept.alloc((size_t)ca.nrows, false)) return kFail;
-        ca.kept = d_kept.p;
-        hipLaunchKernelGGL(csr_churn_count_kernel, dim3((ca.nrows + 3) / 4), dim3(256), 0, stream, ca);
-        TRMF_HIP_CHECK(hipGetLastError());
-        const size_t bytes = kept.size() * sizeof(uint32_t);
-        std::unique_lock<std::mutex> lease;
-        unsigned char *pin = HostStager::current().staging(bytes, lease);
-        TRMF_HIP_CHECK(hipMemcpyAsync(pin ? (void *)pin : (void *)kept.data(), d_kept.p, bytes, hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        if (pin) std::memcpy(kept.data(), pin, bytes);
-        return 0;
-    }
-    int launch_row_gather(const real *src, const uint32_t *list, int nrows, size_t rowlen, real *dst) {
-        if (nrows <= 0 || rowlen == 0) return 0;
-        hipLaunchKernelGGL(row_gather_kernel, dim3((unsigned)std::min(4096, (nrows + 3) / 4)), dim3(256), 0, stream, src, list, nrows, rowlen, dst);
-        TRMF_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    int change_series(const uint8_t *keep, const PyMatrix *Yn, bool fit, const real *Hnew, const real *tra, const real *trb, ChurnResult *res) {
-        const int n0 = n, m = Yn ? (int)Yn->cols : 0;
-        ChurnResult out{};
-        out.series_before = out.series = (uint64_t)n0; out.entries = nnz;
-        if (!keep && m == 0) { if (res) *res = out; return 0; }
-        if (sync()) return kFail;
-        FillStreamScope fill(stream);
-        std::vector<uint32_t> remap((size_t)n0), list;
-        list.reserve((size_t)n0);
-        for (int j = 0; j < n0; j++) {
-            if (!keep || keep[j]) { remap[j] = (uint32_t)list.size(); list.push_back((uint32_t)j); }
-            else remap[j] = kChurnGone;
-        }
-        const int nk = (int)list.size(), n1 = nk + m;
-        const bool all_kept = nk == n0;
-        const bool do_fit = fit && m > 0, carry = churn_carries_stats(m, fit ? 1 : 0);
-        const uint64_t nzn = (Yn && !dense) ? Yn->nnz : 0;
-        uint64_t nzk = 0;
-        if (!dense) for (int q = 0; q < nk; q++) nzk += host_col_ptr[list[q] + 1] - host_col_ptr[list[q]];
-        const uint64_t new_nnz = dense ? (uint64_t)T * n1 : nzk + nzn;
-        {   // the new generation of buffers in ONE slab (the pool returns the previous generation's slab once it is wholly free)
-            const uint64_t nzsave = nnz;
-            n = n1; nnz = new_nnz;
-            const size_t fp = footprint_estimate();
-            n = n0; nnz = nzsave;
-            DevicePool::current().reserve(fp);
-        }
-        const size_t PK = adapt_packed(k);
-        std::vector<uint64_t> new_row_ptr, new_col_ptr;
-        double new_ysq = ysq_acc;
-        DevBuf<uint32_t> d_remap, d_list, ptr2, idx2, cptr2, cidx2, hrow2, hcol2, wptr, widx;
-        DevBuf<real> val2, cval2, tn2, nt2, raw2, H2, a2, b2, S2, r2, S3, r3, hval2, wval, blk_d, blk_tr, blk_nt, Hn, Hraw, Hpad, chg, om, slab, U, Sfull, rfull;
-        DevBuf<uint32_t> d_first, d_items;
-        DevBuf<int> flag;
-        DevBuf<double> errs, hpart2, trp;
-        uint64_t ho_m2 = ho_m;
-        const bool ho_churn = ho_set && !all_kept && ho_m > 0;
-        SyncStreamOnExit drain(stream);
-        if (d_remap.upload(remap.data(), remap.size()) || d_list.upload(list.data(), list.size())) return kFail;
-        const real *fit_blk = nullptr;              // dense storage: the block T x m row-major in the scale the session trains on
-        if (!dense) {
-            // CSC: the kept columns in order, each as stored, then the block's columns as delivered
-            new_col_ptr.assign((size_t)n1 + 1, 0);
-            for (int q = 0; q < nk; q++) new_col_ptr[q + 1] = new_col_ptr[q] + (host_col_ptr[list[q] + 1] - host_col_ptr[list[q]]);
-            for (int j = 0; j < m; j++) new_col_ptr[nk + j + 1] = new_col_ptr[nk + j] + (uint64_t)(Yn->col_ptr[j + 1] - Yn->col_ptr[j]);
-            std::vector<uint32_t> np32((size_t)n1 + 1);
-            for (int j = 0; j <= n1; j++) np32[j] = (uint32_t)new_col_ptr[j];
-            if (cptr2.upload(np32.data(), np32.size()) || cidx2.alloc(new_nnz, false) || cval2.alloc(new_nnz, false)) return kFail;
-            if (nk > 0) {
-                CscGatherArgs ga{Yc_ptr.p, Yc_idx.p, Yc_val.p, d_list.p, cptr2.p, cidx2.p, cval2.p, nk};
-                hipLaunchKernelGGL(csc_gather_kernel, dim3((nk + 3) / 4), dim3(256), 0, stream, ga);
-                TRMF_HIP_CHECK(hipGetLastError());
-            }
-            if (nzn) {
-                TRMF_HIP_CHECK(hipMemcpyAsync(cidx2.p + nzk, Yn->row_idx, nzn * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                TRMF_HIP_CHECK(hipMemcpyAsync(cval2.p + nzk, Yn->val, nzn * sizeof(real), hipMemcpyHostToDevice, stream));
-            }
-            // CSR: every row = its entries of kept series in stored order, renumbered, then the block's entries of that row
-            ChurnArgs ca{};
-            ca.optr = Yr_ptr.p; ca.oidx = Yr_idx.p; ca.oval = Yr_val.p; ca.nrows = T; ca.shift = (uint32_t)nk;
-            ca.remap = all_kept ? nullptr : d_remap.p;
-            std::vector<uint32_t> kept;
-            DevBuf<uint32_t> d_kept;
-            if (!all_kept) { if (churn_count(ca, d_kept, kept)) return kFail; }
-            else { kept.resize((size_t)T); for (int i = 0; i < T; i++) kept[i] = (uint32_t)(host_row_ptr[i + 1] - host_row_ptr[i]); }
-            new_row_ptr.assign((size_t)T + 1, 0);
-            for (int i = 0; i < T; i++) new_row_ptr[i + 1] = new_row_ptr[i] + kept[i] + (m > 0 ? (uint64_t)(Yn->row_ptr[i + 1] - Yn->row_ptr[i]) : 0);
-            if (new_row_ptr[T] != new_nnz) { set_error("change_series: the two orientations of Y do not hold the same entries"); return kFail; }
-            if (upload_ptr32(ptr2, (const size_t *)new_row_ptr.data(), (size_t)T + 1) || idx2.alloc(new_nnz, false) || val2.alloc(new_nnz, false)) return kFail;
-            if (m > 0) {
-                if (upload_ptr32(wptr, Yn->row_ptr, (size_t)T + 1) || widx.upload(Yn->col_idx, nzn) || wval.upload((const real *)Yn->val_t, nzn)) return kFail;
-                ca.wptr = wptr.p; ca.widx = widx.p; ca.wval = wval.p;
-            }
-            ca.nptr = ptr2.p; ca.nidx = idx2.p; ca.nval = val2.p;
-            hipLaunchKernelGGL(csr_churn_kernel, dim3((T + 3) / 4), dim3(256), 0, stream, ca);
-            TRMF_HIP_CHECK(hipGetLastError());
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-            if (device_sum_squares(val2.p, new_nnz, &new_ysq)) return kFail;
-        } else {
-            std::vector<real> blk;
-            if (m > 0) { (void)dense_rows_to_rowmajor(Yn, blk); if (blk_d.upload(blk.data(), blk.size())) return kFail; }
-            const size_t N1 = (size_t)T * n1;
-            if (tn2.alloc(N1, false) || nt2.alloc(N1, false) || (has_transform && raw2.alloc(N1, false))) return kFail;
-            // the block is RAW data: under a transform the raw copy is churned and both orientations are re-derived after the commit
-            DenseChurnArgs da{has_transform ? Yraw.p : Yd_tn.p, d_list.p, m > 0 ? blk_d.p : nullptr, has_transform ? raw2.p : tn2.p, T, n0, nk, m};
-            hipLaunchKernelGGL(dense_churn_kernel, dim3((n1 + 255) / 256, (T + kChurnBand - 1) / kChurnBand), dim3(256), 0, stream, da);
-            TRMF_HIP_CHECK(hipGetLastError());
-            fit_blk = blk_d.p;
-            if (has_transform) {
-                if (a2.alloc((size_t)n1, false) || b2.alloc((size_t)n1, false)) return kFail;
-                if (launch_row_gather(tr_a.p, d_list.p, nk, 1, a2.p) || launch_row_gather(tr_b.p, d_list.p, nk, 1, b2.p)) return kFail;
-                if (m > 0) {
-                    TRMF_HIP_CHECK(hipMemcpyAsync(a2.p + nk, tra, (size_t)m * sizeof(real), hipMemcpyHostToDevice, stream));
-                    TRMF_HIP_CHECK(hipMemcpyAsync(b2.p + nk, trb, (size_t)m * sizeof(real), hipMemcpyHostToDevice, stream));
-                    if (do_fit || k <= kMaxRank) {        // the block in the trained scale, for the fit and the error sum (the bits apply_series_transform gives)
-                        if (blk_tr.alloc(blk.size(), false) || trp.alloc(1024)) return kFail;
-                        hipLaunchKernelGGL(affine_columns_kernel, dim3(1024), dim3(256), 0, stream, blk_d.p, (size_t)T, m, a2.p + nk, b2.p + nk, blk_tr.p, trp.p);
-                        TRMF_HIP_CHECK(hipGetLastError());
-                        fit_blk = blk_tr.p;
-                    }
-                }
-            } else {
-                // the n x T orientation: row copies of the kept series, the block transposed behind them
-                if (launch_row_gather(Yd_nt.p, d_list.p, nk, (size_t)T, nt2.p)) return kFail;
-                if (m > 0) launch_transpose(blk_d.p, T, m, nt2.p + (size_t)nk * T);
-                TRMF_HIP_CHECK(hipGetLastError());
-            }
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // blk is a local: its copy must have left the host
-            if (!has_transform && device_sum_squares(tn2.p, new_nnz, &new_ysq)) return kFail;    // over the new matrix, like a fresh session's
-        }
-        // H: the kept rows gathered, the new rows zero until the fit / the caller's values arrive (the pads and the extra row stay zero)
-        if (H2.alloc((size_t)(n1 + 1) * KP)) return kFail;
-        if (launch_row_gather(H.p, d_list.p, nk, (size_t)KP, H2.p)) return kFail;
-        real *Hnew_rows = H2.p + (size_t)nk * KP;
-        if (m > 0 && !do_fit && Hnew) {
-            if (Hraw.upload(Hnew, (size_t)m * k) || Hpad.alloc((size_t)(m + 1) * KP, false)) return kFail;
-            const size_t N = (size_t)(m + 1) * KP;
-            hipLaunchKernelGGL(factor_pad_kernel, dim3((unsigned)std::min<size_t>(4096, (N + 255) / 256)), dim3(256), 0, stream, Hraw.p, (size_t)m, k, KP, NT, Hpad.p);
-            TRMF_HIP_CHECK(hipGetLastError());
-            TRMF_HIP_CHECK(hipMemcpyAsync(Hnew_rows, Hpad.p, (size_t)m * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-        }
-        // the loading statistics that are carried: the kept series' tables gathered (the new series' tables are the fit's output)
-        if (carry) {
-            if (S2.alloc((size_t)n1 * PK, false) || r2.alloc((size_t)n1 * k, false) || S3.alloc((size_t)n1 * PK, false) || r3.alloc((size_t)n1 * k, false)) return kFail;
-            if (launch_row_gather(ad_S[ad_cur].p, d_list.p, nk, PK, S2.p) || launch_row_gather(ad_r[ad_cur].p, d_list.p, nk, (size_t)k, r2.p)) return kFail;
-        }
-        if (do_fit) {    // the cold-start fit: adapt_series' init pass over the new columns, W as it is
-            const double gam = carry ? ad_gamma : 1.0;
-            std::vector<real> hom;
-            if (gam != 1.0) {
-                hom.resize((size_t)T);
-                for (int t = 0; t < T; t++) hom[t] = (real)std::pow(gam, (double)(T - 1 - t));
-            }
-            if (Hn.alloc((size_t)m * KP) || chg.alloc(m, false) || flag.alloc(1, false) || (!hom.empty() && om.upload(hom.data(), hom.size()))) return kFail;
-            TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
-            const real *omp = hom.empty() ? nullptr : om.p;
-            if (!full) {
-                // long columns are cut into items by the rule of the init pass on the churned problem (the bits of a fresh init)
-                std::vector<uint32_t> hfirst((size_t)m + 1), hitems;
-                uint64_t chunk = std::max<uint64_t>(kAdaptChunk, (new_nnz + kAdaptMaxItems - 1) / kAdaptMaxItems);
-                if (const char *e = test_env("TRMF_ADAPT_CHUNK")) chunk = (uint64_t)std::max(1, atoi(e));
-                for (int j = 0; j < m; j++) {
-                    hfirst[j] = (uint32_t)(hitems.size() / 2);
-                    const uint64_t c0 = new_col_ptr[nk + j], c1 = new_col_ptr[nk + j + 1];
-                    if (c1 - c0 > chunk)
-                        for (uint64_t b = c0; b < c1; b += chunk) { hitems.push_back((uint32_t)b); hitems.push_back((uint32_t)std::min<uint64_t>(b + chunk, c1)); }
-                }
-                hfirst[m] = (uint32_t)(hitems.size() / 2);
-                const uint32_t nitems = (uint32_t)(hitems.size() / 2);
-                if (nitems && (d_first.upload(hfirst.data(), hfirst.size()) || d_items.upload(hitems.data(), hitems.size()) ||
-                               slab.alloc((size_t)nitems * adapt_part_reals(k), false))) return kFail;
-                if (!carry && (Sfull.alloc((size_t)m * PK, false) || rfull.alloc((size_t)m * k, false))) return kFail;
-                AdaptArgs a{cptr2.p + nk, cidx2.p, cval2.p, cptr2.p + nk, W.p, omp, nullptr, nullptr, carry ? S2.p + (size_t)nk * PK : Sfull.p,
-                            carry ? r2.p + (size_t)nk * k : rfull.p, nitems ? d_first.p : nullptr, nitems ? d_items.p : nullptr, nitems ? slab.p : nullptr,
-                            Hnew_rows, Hn.p, chg.p, flag.p, real(1), (real)lambdaI, 0, m, k, KP};
-                if (!with_nt(NT, [&](auto N) {
-                        if (nitems) hipLaunchKernelGGL(adapt_part_kernel<decltype(N)::value>, dim3(nitems), dim3(64), 0, stream, a);
-                        hipLaunchKernelGGL(adapt_series_kernel<decltype(N)::value>, dim3(m), dim3(64), 0, stream, a);
-                    })) return unsupported_rank();
-            } else {
-                if (Sfull.alloc(PK, false) || rfull.alloc((size_t)m * k, false) || U.alloc((size_t)k * k, false)) return kFail;
-                if (dense) {      // the m x T orientation of the block in the trained scale
-                    if (blk_nt.alloc((size_t)T * m, false)) return kFail;
-                    launch_transpose(fit_blk, T, m, blk_nt.p);
-                }
-                AdaptFullArgs a{dense ? nullptr : cptr2.p + nk, dense ? nullptr : cidx2.p, dense ? nullptr : cval2.p, dense ? nullptr : cptr2.p + nk,
-                                dense ? blk_nt.p : nullptr, W.p, omp, nullptr, nullptr, Sfull.p, rfull.p, U.p, Hnew_rows, Hn.p, chg.p, real(1), 0, T, m, k, KP, NT};
-                hipLaunchKernelGGL(adapt_full_gram_kernel, dim3((unsigned)((PK + 255) / 256)), dim3(256), 0, stream, a);
-                hipLaunchKernelGGL(adapt_full_rhs_kernel, dim3((m + 3) / 4), dim3(256), 0, stream, a);
-                AssimFactorArgs fa{Sfull.p, (size_t)0, 1, U.p, flag.p, (real)lambdaI, 0, 1, k};       // the one shared system: "series 0" names it
-                if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3(1), dim3(256), 0, stream, fa); }))
-                    return unsupported_rank();
-                hipLaunchKernelGGL(adapt_full_subst_kernel, dim3((m + 3) / 4), dim3(256), 0, stream, a);
-            }
-            TRMF_HIP_CHECK(hipGetLastError());
-            int bad = kAdaptNoBadSeries;
-            TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-            if (bad != kAdaptNoBadSeries) { out.bad_series = bad; if (res) *res = out; return 0; }
-            TRMF_HIP_CHECK(hipMemcpyAsync(Hnew_rows, Hn.p, (size_t)m * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-        }
-        if (m > 0 && k <= kMaxRank) {   // the new series' squared error with their new loadings (assim_err_kernel's reading of an entry), row order
-            if (errs.alloc((size_t)2 * T, false)) return kFail;
-            AssimErrArgs ea{dense ? nullptr : wptr.p, dense ? nullptr : widx.p, dense ? nullptr : wval.p, dense ? fit_blk : nullptr, Hnew_rows,
-                            W.p, W.p, 0, 0, errs.p, 0, T, m, KP, dense ? 1 : 0};
-            hipLaunchKernelGGL(assim_err_kernel, dim3(T), dim3(256), 0, stream, ea);
-            TRMF_HIP_CHECK(hipGetLastError());
-            std::vector<double> herr((size_t)2 * T);
-            TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, herr.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-            for (int i = 0; i < T; i++) out.sq_err_new += herr[2 * i];
-        }
-        if (ho_churn) {  // held-out positions in retired series are dropped, the rest renumbered: the COO list as pseudo-rows of kSlideChunk entries
-            const int nch = (int)((ho_m + kSlideChunk - 1) / kSlideChunk);
-            std::vector<uint32_t> cp((size_t)nch + 1), hk, np((size_t)nch + 1, 0u);
-            for (int c = 0; c <= nch; c++) cp[c] = (uint32_t)std::min<uint64_t>((uint64_t)c * kSlideChunk, ho_m);
-            DevBuf<uint32_t> d_cp, d_np, d_kept;
-            ChurnArgs ha{};
-            if (d_cp.upload(cp.data(), cp.size())) return kFail;
-            ha.optr = d_cp.p; ha.oidx = ho_col.p; ha.oval = ho_val.p; ha.oaux = ho_row.p; ha.remap = d_remap.p; ha.nrows = nch;
-            if (churn_count(ha, d_kept, hk)) return kFail;
-            for (int c = 0; c < nch; c++) np[c + 1] = np[c] + hk[c];
-            ho_m2 = np[nch];
-            if (d_np.upload(np.data(), np.size()) || hrow2.alloc(ho_m2, false) || hcol2.alloc(ho_m2, false) || hval2.alloc(ho_m2, false)) return kFail;
-            ha.nptr = d_np.p; ha.nidx = hcol2.p; ha.nval = hval2.p; ha.naux = hrow2.p;
-            hipLaunchKernelGGL(csr_churn_kernel, dim3((nch + 3) / 4), dim3(256), 0, stream, ha);
-            TRMF_HIP_CHECK(hipGetLastError());
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // (the pointer arrays are locals)
-        }
-        int ho_nb2 = ho_nb; uint64_t ho_chunk2 = ho_chunk;
-        if (ho_churn) { heldout_geometry(ho_m2, &ho_nb2, &ho_chunk2); if (hpart2.alloc((size_t)kHoSums * ho_nb2, false)) return kFail; }
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        // ---- commit ----
-        out.series_retired = (uint64_t)(n0 - nk); out.series_added = (uint64_t)m; out.series = (uint64_t)n1;
-        out.entries_retired = dense ? (uint64_t)T * (n0 - nk) : nnz - nzk; out.entries_added = dense ? (uint64_t)T * m : nzn; out.entries = new_nnz;
-        out.heldout_dropped = ho_churn ? ho_m - ho_m2 : 0;
-        out.fitted = do_fit ? 1 : 0; out.stats_carried = carry ? 1 : 0;
-        if (!dense) {
-            Yr_ptr.swap(ptr2); Yr_idx.swap(idx2); Yr_val.swap(val2);
-            Yc_ptr.swap(cptr2); Yc_idx.swap(cidx2); Yc_val.swap(cval2);
-        } else {
-            Yd_tn.swap(tn2); Yd_nt.swap(nt2);
-            if (has_transform) { Yraw.swap(raw2); tr_a.swap(a2); tr_b.swap(b2); }
-        }
-        H.swap(H2);
-        if (ad_exists) {
-            if (carry) {
-                ad_S[ad_cur].swap(S2); ad_r[ad_cur].swap(r2); ad_S[1 - ad_cur].swap(S3); ad_r[1 - ad_cur].swap(r3);
-                std::vector<uint32_t> cnt((size_t)n1);
-                for (int j = 0; j < n1; j++) cnt[j] = (uint32_t)(new_col_ptr[j + 1] - new_col_ptr[j]);
-                ad_cnt.swap(cnt);
-            } else {                                  // the tables describe another set of series: stale, and their memory goes back
-                for (int q = 0; q < 2; q++) { ad_S[q].release(); ad_r[q].release(); }
-                ad_cnt.clear();
-                adapt_stale();
-            }
-        }
-        if (ho_churn) {
-            ho_row.swap(hrow2); ho_col.swap(hcol2); ho_val.swap(hval2); ho_part.swap(hpart2); ho_pred.release();
-            ho_m = ho_m2; ho_nb = ho_nb2; ho_chunk = ho_chunk2;
-        }
-        for (int q = 0; q < 2; q++) { fc_table[q].release(); fc_prev[q].release(); iv_table[q].release(); }      // per-series sums of another set of series
-        fc_cur = 0; fc_rows = 0; iv_cur = 0; iv_rows = 0;
-        nz_sigma2.release(); nz_q.release(); nz_set = false;
-        markW.release(); markH.release(); markT.release(); mark_iter = -1;         // a mark names series that have moved
-        snapW.release(); snapH.release(); snapT.release(); snap_iter = -1;
-        if (!dense) { host_row_ptr.swap(new_row_ptr); host_col_ptr.swap(new_col_ptr); }
-        if (res) *res = out;
-        n = n1; nnz = new_nnz; ysq_acc = new_ysq;
-        if (dense && has_transform && apply_series_transform()) return kFail;     // current coefficients over the new raw matrix
-        set_trYTY();
-        iter = 0;
-        if (gramx_mode != kGramxReplicate && comm->world > 1 && !test_env("TRMF_GRAMX")) { gramx_mode = kGramxMeasure; gramx_calls = 0; }
-        if (fs_mode != kShardOff && comm->world > 1 && !test_env("TRMF_FSHARD")) { fs_mode = kShardMeasure; fs_calls = 0; }
-        if (alloc_series_scratch() || alloc_time_scratch()) return kFail;
-        TRMF_HIP_CHECK(hipDeviceSynchronize());
-        return autotune();
     }
     bool decisions_pending() const {
         if (comm->world <= 1 || full) return false;
@@ -1703,671 +1118,6 @@ struct TrmfSessionImpl : SessionXPhase {
         TRMF_HIP_CHECK(hipStreamSynchronize(stream));
         for (int q = 0; q < 2; q++) iv_table[q].release();      // the next scored call starts from zeroed ones
         iv_cur = 0; iv_rows = 0;
-        return 0;
-    }
-    // ---- online updates (trmf_session_assimilate; online_kernels.hpp) ---------------------------------------------------------
-    // Rows [first_row, T) of W re-solved in ascending order with H and Theta fixed (the caller has validated first_row, the lag set
-    // and the rank).  Stage A rebuilds the Gram cache rows and right-hand sides of the range with the X phase's own builders -- every
-    // X phase rebuilds the rows it reads before it reads them (xsolve: gram_x / xprepare_full), so nothing relies on their old
-    // contents -- stage B factors all rows in parallel, stage C is the serial chain.  Everything lands in scratch; W changes by ONE
-    // device copy after the flag has been read.  No collective: every rank holds the whole Y and W and computes the same bits.
-    // A pivot that is not positive and finite is not a failure of this rank's task (res->bad_row names the row, nothing is
-    // committed): the entry point reports it on the calling thread, so the barrier of a TRMF_DEVICES group stays whole.
-    struct AssimResult {
-        uint64_t rows = 0, entries = 0;
-        double sq_err_before = 0, sq_err_after = 0;
-        int bad_row = -1;
-    };
-    int assimilate(int first_row, AssimResult *res, real *Wout) {
-        *res = AssimResult{};
-        if (sync()) return kFail;
-        const int nr = T - first_row;
-        if (nr <= 0) return 0;
-        FillStreamScope fill(stream);
-        int chunk = kAssimChunk;
-        if (const char *e = test_env("TRMF_ASSIM_CHUNK")) chunk = std::max(1, atoi(e));      // tests: several passes on a small shape
-        chunk = std::min(chunk, nr);
-        DevBuf<real> Wn, flat, U;
-        DevBuf<int> flag;
-        DevBuf<double> errs;
-        SyncStreamOnExit drain(stream);
-        if (Wn.alloc((size_t)nr * KP) || (Wout && flat.alloc((size_t)nr * k, false)) || U.alloc((size_t)chunk * k * k, false) ||
-            flag.alloc(1, false) || errs.alloc((size_t)2 * nr, false)) return kFail;
-        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
-        // stage A
-        if (full) {
-            if (y_times_factor(false, H.p, Bv.p, dense ? 0u : (uint32_t)first_row, (uint32_t)T)) return kFail;        // rows of Y H
-            if (small_gram(H.p, n, real(0), GSx.p, stream)) return kFail;                                             // H^T H
-        } else if (launch_gram_x_rows((uint32_t)first_row, (uint32_t)T)) return kFail;
-        TRMF_HIP_CHECK(hipGetLastError());
-        // stages B and C, a chunk of rows at a time
-        const real lamAR = (real)lambdaAR, lam = (real)lambdaI + lamAR;
-        int reach = 0;
-        if (midx > 0 && assim_chain_lds_bytes(k, nlag, midx) <= kLdsMax && !test_env("TRMF_FORECAST_GLOBAL")) reach = midx;
-        const size_t lds = assim_chain_lds_bytes(k, nlag, reach);
-        if (allow_dyn_lds(assim_chain_kernel, lds, "online update")) return kFail;
-        for (int r0 = first_row; r0 < T; r0 += chunk) {
-            const int rows = std::min(chunk, T - r0);
-            AssimFactorArgs fa{Gmat(), full ? (size_t)0 : xp.gstride, gpacked ? 1 : 0, U.p, flag.p, lam, r0, rows, k};
-            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3((rows + 3) / 4), dim3(256), 0, stream, fa); }))
-                return unsupported_rank();
-            AssimChainArgs ca{W.p, Wn.p, Wout ? flat.p : nullptr, Bv.p, U.p, lag_set.p, theta.p, lamAR, first_row, r0, rows, k, KP, NT, nlag, reach};
-            hipLaunchKernelGGL(assim_chain_kernel, dim3(1), dim3(256), lds, stream, ca);
-            TRMF_HIP_CHECK(hipGetLastError());
-        }
-        {   // the squared errors of the range with W as it is and as it will be
-            AssimErrArgs ea{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr, H.p,
-                            W.p, Wn.p, 0, first_row, errs.p, first_row, nr, n, KP, full ? 1 : 0};
-            hipLaunchKernelGGL(assim_err_kernel, dim3(nr), dim3(256), 0, stream, ea);
-            TRMF_HIP_CHECK(hipGetLastError());
-        }
-        int bad = kAssimNoBadRow;
-        std::vector<double> herr((size_t)2 * nr);
-        std::vector<real> hflat(Wout ? (size_t)nr * k : 0);
-        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, herr.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (Wout) TRMF_HIP_CHECK(hipMemcpyAsync(hflat.data(), flat.p, hflat.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        if (bad != kAssimNoBadRow) { res->bad_row = bad; return 0; }
-        // ---- commit ----
-        TRMF_HIP_CHECK(hipMemcpyAsync(W.p + (size_t)first_row * KP, Wn.p, (size_t)nr * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-        if (first_row < ad_rows) adapt_stale();                     // rows the series statistics absorbed have changed
-        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new W
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        res->rows = (uint64_t)nr;
-        res->entries = full ? (uint64_t)nr * (uint64_t)n : host_row_ptr[T] - host_row_ptr[first_row];
-        for (int r = 0; r < nr; r++) { res->sq_err_before += herr[2 * r]; res->sq_err_after += herr[2 * r + 1]; }
-        if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
-        return 0;
-    }
-    // ---- outlier-robust online updates (trmf_session_assimilate_robust; robust_kernels.hpp) -------------------------------------
-    // assimilate() with Huber weights (the caller has validated first_row, the lag set, the rank, the storage, c, the sweep count and
-    // the n scales, which arrive as host values on every rank).  The weights depend on the iterate, so the Gram cache is of no use:
-    // per row and sweep one part launch over the row's slices and one solve launch, 2 * sweeps * rows launches on the session's
-    // stream with no host synchronisation before the one flag read.  Neither G nor Bv is touched.  Failure-atomic like assimilate():
-    // rows, weights and sums land in scratch / host staging and are handed over after the flag has been read.
-    struct RobustResult {
-        uint64_t rows = 0, entries = 0, downweighted = 0;
-        double weight_sum = 0, sq_err_before = 0, sq_err_after = 0;
-        int bad_row = -1;
-    };
-    int assimilate_robust(int first_row, double c, int sweeps, const double *scale, RobustResult *res, real *Wout, real *weights_out) {
-        *res = RobustResult{};
-        if (sync()) return kFail;
-        const int nr = T - first_row;
-        if (nr <= 0) return 0;
-        FillStreamScope fill(stream);
-        int slice = kAssimRobustSlice;
-        if (const char *e = test_env("TRMF_ASSIM_ROBUST_SLICE")) slice = std::max(1, atoi(e));      // tests: several slices per row on a small shape
-        const uint64_t nw = dense ? (uint64_t)nr * (uint64_t)n : host_row_ptr[T] - host_row_ptr[first_row];
-        auto slices_of = [&](int i) { const uint64_t len = dense ? (uint64_t)n : host_row_ptr[i + 1] - host_row_ptr[i]; return (int)((len + slice - 1) / slice); };
-        int max_slices = 1;
-        for (int i = first_row; i < T; i++) max_slices = std::max(max_slices, slices_of(i));
-        std::vector<real> hthr((size_t)n);
-        for (int j = 0; j < n; j++) hthr[j] = (real)c * (real)scale[j];
-        DevBuf<real> Wn, flat, wcur, prior, thr, wts, slab;
-        DevBuf<int> flag;
-        DevBuf<double> errs, slab_d, rowsum;
-        SyncStreamOnExit drain(stream);
-        if (Wn.alloc((size_t)nr * KP) || (Wout && flat.alloc((size_t)nr * k, false)) || wcur.alloc(KP) || prior.alloc(KP) || thr.upload(hthr.data(), n) ||
-            wts.alloc(nw, false) || slab.alloc((size_t)max_slices * assim_robust_slot_reals(KP), false) || slab_d.alloc((size_t)2 * max_slices, false) ||
-            rowsum.alloc((size_t)2 * nr, false) || flag.alloc(1, false) || errs.alloc((size_t)2 * nr, false)) return kFail;
-        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
-        AssimRobustArgs ra{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr, H.p, W.p, Wn.p,
-                           Wout ? flat.p : nullptr, wcur.p, prior.p, thr.p, wts.p, slab.p, slab_d.p, rowsum.p, lag_set.p, theta.p, flag.p,
-                           (real)lambdaI + (real)lambdaAR, (real)lambdaAR, first_row, T, first_row, n, k, KP, nlag, slice, 0, 0};
-        hipLaunchKernelGGL(assim_robust_prior_kernel, dim3(1), dim3(64), 0, stream, ra);
-        TRMF_HIP_CHECK(hipGetLastError());
-        for (int i = first_row; i < T; i++) {
-            ra.i = i; ra.nslices = slices_of(i);
-            for (int s = 1; s <= sweeps; s++) {
-                ra.last = s == sweeps ? 1 : 0;
-                if (!with_nt(NT, [&](auto N) {
-                        if (ra.nslices > 0) hipLaunchKernelGGL(assim_robust_part_kernel<decltype(N)::value>, dim3(ra.nslices), dim3(256), 0, stream, ra);
-                        hipLaunchKernelGGL(assim_robust_solve_kernel<decltype(N)::value>, dim3(1), dim3(256), 0, stream, ra);
-                    })) return unsupported_rank();
-            }
-            TRMF_HIP_CHECK(hipGetLastError());
-        }
-        {   // the squared errors of the range with W as it is and as it will be (unweighted)
-            AssimErrArgs ea{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr, H.p,
-                            W.p, Wn.p, 0, first_row, errs.p, first_row, nr, n, KP, full ? 1 : 0};
-            hipLaunchKernelGGL(assim_err_kernel, dim3(nr), dim3(256), 0, stream, ea);
-            TRMF_HIP_CHECK(hipGetLastError());
-        }
-        int bad = kAssimNoBadRow;
-        std::vector<double> herr((size_t)2 * nr), hsum((size_t)2 * nr);
-        std::vector<real> hflat(Wout ? (size_t)nr * k : 0), hwts(weights_out ? (size_t)nw : 0);
-        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, herr.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(hsum.data(), rowsum.p, hsum.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (Wout) TRMF_HIP_CHECK(hipMemcpyAsync(hflat.data(), flat.p, hflat.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
-        if (weights_out && nw) TRMF_HIP_CHECK(hipMemcpyAsync(hwts.data(), wts.p, hwts.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        if (bad != kAssimNoBadRow) { res->bad_row = bad; return 0; }
-        // ---- commit ----
-        TRMF_HIP_CHECK(hipMemcpyAsync(W.p + (size_t)first_row * KP, Wn.p, (size_t)nr * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-        if (first_row < ad_rows) adapt_stale();                     // rows the series statistics absorbed have changed
-        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new W
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        res->rows = (uint64_t)nr;
-        res->entries = nw;
-        double down = 0;
-        for (int r = 0; r < nr; r++) {                              // row order: the same sums on every rank and every call
-            res->sq_err_before += herr[2 * r]; res->sq_err_after += herr[2 * r + 1];
-            down += hsum[2 * r]; res->weight_sum += hsum[2 * r + 1];
-        }
-        res->downweighted = (uint64_t)down;
-        if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
-        if (weights_out && nw) std::memcpy(weights_out, hwts.data(), hwts.size() * sizeof(real));
-        return 0;
-    }
-    // ---- the fixed-interval smoother (trmf_session_smooth; smooth_kernels.hpp) ------------------------------------------------------
-    // Rows [first_row, T) of W become the joint minimiser of the objective restricted to them (the caller has validated first_row,
-    // the lag set, the rank, the window against the cap, rtol and max_iter).  Stage A is assimilate()'s: Grams and right-hand sides
-    // of the window by the X phase's builders, the factors of ALL rows at once (they precondition every step).  Stage B is the
-    // PCG, three launches per step on the session's stream; the stop is decided on the device, and the host only follows it
-    // through one pinned word: it stays kSmoothLook steps ahead of the device and stops enqueuing when it sees the stop (launches
-    // after the stop return at once, so the bits do not depend on how far ahead it was).  A word that does not move for 2 s is answered
-    // by a stream synchronisation and a re-read, never by enqueuing the remaining steps blind.  Everything lands in scratch; W changes
-    // by ONE device copy after the flag and the sums have been read.  A call that reaches max_iter commits as well: every CG
-    // iterate lowers J_win.  No collective: every rank holds the whole Y and W and computes the same bits.
-    struct SmoothResult {
-        uint64_t rows = 0, entries = 0;
-        int iterations = 0, converged = 0;
-        double residual = 0, sq_err_before = 0, sq_err_after = 0, objective_before = 0, objective_after = 0;
-        int bad_row = -1;
-    };
-    static int smooth_max_rows() {
-        int cap = kSmoothMaxRows;
-        if (const char *e = test_env("TRMF_SMOOTH_MAX_ROWS")) cap = std::max(1, atoi(e));      // tests: the refusal on a small shape
-        return cap;
-    }
-    static constexpr int kSmoothLook = 4;
-    unsigned int smooth_seq = 0;
-    // The PCG of one system: INIT, the steps with the pinned-word pacing described above, and the closing stop test.  `sa` carries
-    // the system (W, x0, Bv, G, U), the vectors and a zeroed SmoothState of this solve's own; the word and its sequence number are set here.
-    int smooth_pcg(SmoothArgs &sa, int max_iter) {
-        const int m = sa.m;
-        unsigned int *note = cg_note + 8;                       // a word of its own in the X-solve's pinned line
-        const unsigned int seq = ++smooth_seq & 0x1ffffu;
-        __atomic_store_n(note, 0u, __ATOMIC_RELEASE);
-        sa.note = note; sa.note_seq = seq;
-        sa.lds_theta = smooth_theta_lds_bytes(nlag) <= kLdsDefault && !test_env("TRMF_FORECAST_GLOBAL") ? 1 : 0;
-        const size_t lds_th = sa.lds_theta ? smooth_theta_lds_bytes(nlag) : 0, lds_up = smooth_update_lds_bytes(k);
-        const dim3 rows4((m + 3) / 4);
-        auto step = [&](int mode, int j) {
-            hipLaunchKernelGGL(smooth_ar_kernel, mode == SMOOTH_LAST ? dim3(1) : rows4, dim3(256), lds_th, stream, sa, mode, j);
-            if (mode == SMOOTH_LAST) return;
-            hipLaunchKernelGGL(smooth_apply_kernel, rows4, dim3(256), lds_th, stream, sa, mode, j);
-            hipLaunchKernelGGL(smooth_update_kernel, dim3(m), dim3(64), lds_up, stream, sa, mode, j);
-        };
-        step(SMOOTH_INIT, 0);
-        TRMF_HIP_CHECK(hipGetLastError());
-        bool note_live = true;
-        for (int j = 0; j < max_iter; j++) {
-            step(SMOOTH_STEP, j);
-            TRMF_HIP_CHECK(hipGetLastError());
-            if (j < kSmoothLook) continue;
-            if (!note_live) {                                   // without the word: read the stop itself every kSmoothLook steps
-                if (j % kSmoothLook) continue;
-                int done = 0;
-                TRMF_HIP_CHECK(hipMemcpyAsync(&done, &sa.st->done, sizeof(int), hipMemcpyDeviceToHost, stream));
-                TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-                if (done) break;
-                continue;
-            }
-            // wait until step j - kSmoothLook has been decided: the device is then still kSmoothLook steps behind the queue's end
-            const unsigned int need = (unsigned int)(j - kSmoothLook);
-            const double t_wait = now_s();
-            bool stopped = false;
-            for (unsigned int spins = 0;; spins++) {
-                const unsigned int v = __atomic_load_n(note, __ATOMIC_ACQUIRE);
-                if ((v >> 15) == seq) {
-                    if (v & 1u) { stopped = true; break; }
-                    if (((v >> 1) & 0x3fffu) >= need) break;
-                }
-                if ((spins & 1023u) == 1023u && now_s() - t_wait > 2.0) {
-                    // the word has not moved for 2 s (a loaded device): drain the queue and read it again instead of running ahead blind
-                    TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-                    const unsigned int w = __atomic_load_n(note, __ATOMIC_ACQUIRE);
-                    if ((w >> 15) != seq) note_live = false;        // the device never wrote it: pace by synchronising from here on
-                    stopped = (w >> 15) == seq && (w & 1u);
-                    break;
-                }
-                __builtin_ia32_pause();
-            }
-            if (stopped) break;
-        }
-        step(SMOOTH_LAST, max_iter);                             // the last step's r.z and its stop test (a no-op after a stop)
-        return 0;
-    }
-    int smooth(int first_row, double rtol, int max_iter, SmoothResult *res, real *Wout) {
-        *res = SmoothResult{};
-        if (sync()) return kFail;
-        const int m = T - first_row;
-        if (m <= 0) return 0;
-        if (ensure_cg_note()) { set_error("smooth: no pinned host memory for the word the stop is followed through"); return kFail; }
-        FillStreamScope fill(stream);
-        DevBuf<real> Wn, flat, U, vec, part;
-        DevBuf<int> flag;
-        DevBuf<double> errs, objs;
-        DevBuf<SmoothState> state;
-        SyncStreamOnExit drain(stream);
-        const size_t V = (size_t)m * 64;
-        if (Wn.alloc((size_t)m * KP) || (Wout && flat.alloc((size_t)m * k, false)) || U.alloc((size_t)m * k * k, false) || vec.alloc(7 * V) ||
-            part.alloc((size_t)2 * m) || flag.alloc(1, false) || errs.alloc((size_t)2 * m, false) || objs.alloc((size_t)4 * m, false) || state.alloc(1))
-            return kFail;
-        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
-        // stage A
-        if (full) {
-            if (y_times_factor(false, H.p, Bv.p, dense ? 0u : (uint32_t)first_row, (uint32_t)T)) return kFail;        // rows of Y H
-            if (small_gram(H.p, n, real(0), GSx.p, stream)) return kFail;                                             // H^T H
-        } else if (launch_gram_x_rows((uint32_t)first_row, (uint32_t)T)) return kFail;
-        TRMF_HIP_CHECK(hipGetLastError());
-        const real lamAR = (real)lambdaAR, lamI = (real)lambdaI;
-        {
-            AssimFactorArgs fa{Gmat(), full ? (size_t)0 : xp.gstride, gpacked ? 1 : 0, U.p, flag.p, lamI + lamAR, first_row, m, k};
-            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3((m + 3) / 4), dim3(256), 0, stream, fa); }))
-                return unsupported_rank();
-            TRMF_HIP_CHECK(hipGetLastError());
-        }
-        // stage B
-        SmoothArgs sa{};
-        sa.W = W.p; sa.x0 = W.p + (size_t)first_row * KP; sa.Bv = Bv.p; sa.G = Gmat(); sa.gstride = full ? (size_t)0 : xp.gstride; sa.packed = gpacked ? 1 : 0;
-        sa.grow = first_row; sa.U = U.p;
-        sa.lag_set = lag_set.p; sa.theta = theta.p;
-        sa.x = vec.p; sa.r = vec.p + V; sa.z = vec.p + 2 * V; sa.q = vec.p + 3 * V; sa.e = vec.p + 4 * V; sa.p[0] = vec.p + 5 * V; sa.p[1] = vec.p + 6 * V;
-        sa.part_rz = part.p; sa.part_pq = part.p + m; sa.st = state.p; sa.flag = flag.p;
-        sa.tol2 = rtol * rtol; sa.lamI = lamI; sa.lamAR = lamAR;
-        sa.first_row = first_row; sa.m = m; sa.k = k; sa.KP = KP; sa.NT = NT; sa.nlag = nlag;
-        if (smooth_pcg(sa, max_iter)) return kFail;
-        const dim3 rows4((m + 3) / 4);
-        {
-            SmoothFinishArgs fa{W.p, sa.x, lag_set.p, theta.p, Wn.p, Wout ? flat.p : nullptr, objs.p, first_row, m, k, KP, NT, nlag};
-            hipLaunchKernelGGL(smooth_finish_kernel, rows4, dim3(256), 0, stream, fa);
-            AssimErrArgs ea{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr, H.p,
-                            W.p, Wn.p, 0, first_row, errs.p, first_row, m, n, KP, full ? 1 : 0};
-            hipLaunchKernelGGL(assim_err_kernel, dim3(m), dim3(256), 0, stream, ea);
-            TRMF_HIP_CHECK(hipGetLastError());
-        }
-        int bad = kAssimNoBadRow;
-        SmoothState hst{};
-        std::vector<double> herr((size_t)2 * m), hobj((size_t)4 * m);
-        std::vector<real> hflat(Wout ? (size_t)m * k : 0);
-        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(&hst, state.p, sizeof(SmoothState), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, herr.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(hobj.data(), objs.p, hobj.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (Wout) TRMF_HIP_CHECK(hipMemcpyAsync(hflat.data(), flat.p, hflat.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        if (bad != kAssimNoBadRow) { res->bad_row = bad; return 0; }
-        // ---- commit ----
-        TRMF_HIP_CHECK(hipMemcpyAsync(W.p + (size_t)first_row * KP, Wn.p, (size_t)m * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-        if (first_row < ad_rows) adapt_stale();                     // rows the series statistics absorbed have changed
-        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new W
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        res->rows = (uint64_t)m;
-        res->entries = full ? (uint64_t)m * (uint64_t)n : host_row_ptr[T] - host_row_ptr[first_row];
-        res->converged = hst.done ? 1 : 0;
-        res->iterations = hst.done ? hst.iters : max_iter;
-        const double rz_end = hst.rz[res->iterations & 1];
-        res->residual = hst.rz0 > 0 ? std::sqrt(std::max(rz_end, 0.0) / hst.rz0) : 0.0;
-        double w2[2] = {0, 0}, e2[2] = {0, 0};
-        for (int r = 0; r < m; r++) {                               // row order: the same sums on every rank and every call
-            res->sq_err_before += herr[2 * r]; res->sq_err_after += herr[2 * r + 1];
-            w2[0] += hobj[4 * r]; e2[0] += hobj[4 * r + 1]; w2[1] += hobj[4 * r + 2]; e2[1] += hobj[4 * r + 3];
-        }
-        res->objective_before = 0.5 * (res->sq_err_before + (double)lamI * w2[0] + (double)lamAR * e2[0]);
-        res->objective_after = 0.5 * (res->sq_err_after + (double)lamI * w2[1] + (double)lamAR * e2[1]);
-        if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
-        return 0;
-    }
-    // ---- the robust fixed-interval smoother (trmf_session_smooth_robust; smooth_robust_kernels.hpp) -----------------------------------
-    // smooth() on the Huber form of the objective by `sweeps` rounds of reweighting (the caller has validated what smooth() and
-    // assimilate_robust() ask for; the n scales arrive as host values on every rank).  Per sweep: one part launch over the items of
-    // the whole window and one fold launch build the weighted G_i, b_i in scratch of this call's own (the session's G / Bv cache is
-    // not touched), assim_factor_kernel factors the blocks, smooth_pcg() solves from the rows of the sweep before, and
-    // smooth_finish_kernel lays the rows out for the next sweep's part kernel.  Two more part launches in score-only mode give
-    // J_rob's data term before and after.  The host synchronises only where smooth_pcg() follows its word; W changes by ONE device
-    // copy after the flag and the sums have been read.  A sweep that reaches max_iter is kept (converged = 0): every CG iterate
-    // lowers the sweep's majoriser of J_rob.
-    struct RobustSmoothResult {
-        uint64_t rows = 0, entries = 0, downweighted = 0;
-        int sweeps = 0, iterations = 0, converged = 0;
-        double residual = 0, weight_sum = 0, sq_err_before = 0, sq_err_after = 0, objective_before = 0, objective_after = 0;
-        int bad_row = -1;
-    };
-    int smooth_robust(int first_row, double c, int sweeps, const double *scale, double rtol, int max_iter, RobustSmoothResult *res, real *Wout,
-                      real *weights_out) {
-        *res = RobustSmoothResult{};
-        if (sync()) return kFail;
-        const int m = T - first_row;
-        if (m <= 0) return 0;
-        if (ensure_cg_note()) { set_error("smooth_robust: no pinned host memory for the word the stop is followed through"); return kFail; }
-        FillStreamScope fill(stream);
-        int slice = kSmoothRobustSlice;
-        if (const char *e = test_env("TRMF_SMOOTH_ROBUST_SLICE")) slice = std::max(1, atoi(e));      // tests: several items per row on a small shape
-        const uint64_t nw = dense ? (uint64_t)m * (uint64_t)n : host_row_ptr[T] - host_row_ptr[first_row];
-        // the items: a row's entries in spans that depend on its length only
-        std::vector<uint32_t> hitems, hrow((size_t)m + 1);
-        for (int r = 0; r < m; r++) {
-            hrow[r] = (uint32_t)(hitems.size() / 3);
-            const uint64_t e0 = dense ? 0 : host_row_ptr[first_row + r], e1 = dense ? (uint64_t)n : host_row_ptr[first_row + r + 1];
-            const uint64_t span = smooth_robust_span(e1 - e0, slice);
-            for (uint64_t b = e0; b < e1; b += span) {
-                hitems.push_back((uint32_t)r); hitems.push_back((uint32_t)b); hitems.push_back((uint32_t)std::min(b + span, e1));
-            }
-        }
-        const uint32_t nitems = (uint32_t)(hitems.size() / 3);
-        hrow[m] = nitems;
-        if (hitems.empty()) hitems.assign(3, 0u);
-        std::vector<real> hthr((size_t)n);
-        for (int j = 0; j < n; j++) hthr[j] = (real)c * (real)scale[j];
-        DevBuf<real> xc, flat, U, vec, part, thr, wts, slab, Gs, bs;
-        DevBuf<uint32_t> d_items, d_row;
-        DevBuf<int> flag;
-        DevBuf<double> objs, slab_d, score, rowsum;
-        DevBuf<SmoothState> state;
-        SyncStreamOnExit drain(stream);
-        const size_t V = (size_t)m * 64, ni = std::max<size_t>(nitems, 1);
-        if (xc.alloc((size_t)m * KP, false) || (Wout && flat.alloc((size_t)m * k, false)) || U.alloc((size_t)m * k * k, false) || vec.alloc(7 * V) ||
-            part.alloc((size_t)2 * m) || thr.upload(hthr.data(), n) || wts.alloc(std::max<uint64_t>(nw, 1), false) ||
-            slab.alloc(ni * smooth_robust_slot_reals(KP), false) || Gs.alloc((size_t)m * k * k, false) || bs.alloc((size_t)m * KP, false) ||
-            d_items.upload(hitems.data(), hitems.size()) || d_row.upload(hrow.data(), hrow.size()) || flag.alloc(1, false) ||
-            objs.alloc((size_t)4 * m, false) || slab_d.alloc(ni * kSmoothRobustSlotD, false) || score.alloc(2 * ni * kSmoothRobustSlotD, false) ||
-            rowsum.alloc((size_t)2 * m, false) || state.alloc((size_t)sweeps)) return kFail;
-        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(xc.p, W.p + (size_t)first_row * KP, (size_t)m * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-        const real lamAR = (real)lambdaAR, lamI = (real)lambdaI;
-        SmoothRobustArgs ra{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr, H.p, xc.p, thr.p,
-                            wts.p, d_items.p, d_row.p, slab.p, slab_d.p, Gs.p, bs.p, rowsum.p, first_row, m, n, k, KP, 0};
-        auto part_launch = [&](int score_only, double *sums) {
-            if (!nitems) return true;
-            SmoothRobustArgs a = ra;
-            a.score = score_only; a.slab_d = sums;
-            return with_nt(NT, [&](auto N) { hipLaunchKernelGGL(smooth_robust_part_kernel<decltype(N)::value>, dim3(nitems), dim3(256), 0, stream, a); });
-        };
-        if (!part_launch(1, score.p)) return unsupported_rank();
-        SmoothArgs sa{};
-        sa.W = W.p; sa.x0 = xc.p; sa.Bv = bs.p; sa.G = Gs.p; sa.gstride = (size_t)k * k; sa.packed = 0; sa.grow = 0; sa.U = U.p;
-        sa.lag_set = lag_set.p; sa.theta = theta.p;
-        sa.x = vec.p; sa.r = vec.p + V; sa.z = vec.p + 2 * V; sa.q = vec.p + 3 * V; sa.e = vec.p + 4 * V; sa.p[0] = vec.p + 5 * V; sa.p[1] = vec.p + 6 * V;
-        sa.part_rz = part.p; sa.part_pq = part.p + m; sa.flag = flag.p;
-        sa.tol2 = rtol * rtol; sa.lamI = lamI; sa.lamAR = lamAR;
-        sa.first_row = first_row; sa.m = m; sa.k = k; sa.KP = KP; sa.NT = NT; sa.nlag = nlag;
-        const dim3 rows4((m + 3) / 4);
-        for (int s = 0; s < sweeps; s++) {
-            if (!part_launch(0, slab_d.p)) return unsupported_rank();
-            AssimFactorArgs fa{Gs.p, (size_t)k * k, 0, U.p, flag.p, lamI + lamAR, 0, m, k};
-            if (!with_nt(NT, [&](auto N) {
-                    hipLaunchKernelGGL(smooth_robust_fold_kernel<decltype(N)::value>, dim3(m), dim3(256), 0, stream, ra);
-                    hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3((m + 3) / 4), dim3(256), 0, stream, fa);
-                })) return unsupported_rank();
-            TRMF_HIP_CHECK(hipGetLastError());
-            sa.st = state.p + s;
-            if (smooth_pcg(sa, max_iter)) return kFail;
-            SmoothFinishArgs fin{W.p, sa.x, lag_set.p, theta.p, xc.p, Wout && s == sweeps - 1 ? flat.p : nullptr, objs.p, first_row, m, k, KP, NT, nlag};
-            hipLaunchKernelGGL(smooth_finish_kernel, rows4, dim3(256), 0, stream, fin);
-            TRMF_HIP_CHECK(hipGetLastError());
-        }
-        if (!part_launch(1, score.p + ni * kSmoothRobustSlotD)) return unsupported_rank();
-        TRMF_HIP_CHECK(hipGetLastError());
-        int bad = kAssimNoBadRow;
-        std::vector<SmoothState> hst((size_t)sweeps);
-        std::vector<double> hobj((size_t)4 * m), hsum((size_t)2 * m), hscore(2 * ni * kSmoothRobustSlotD, 0.0);
-        std::vector<real> hflat(Wout ? (size_t)m * k : 0), hwts(weights_out ? (size_t)nw : 0);
-        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(hst.data(), state.p, hst.size() * sizeof(SmoothState), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(hobj.data(), objs.p, hobj.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(hsum.data(), rowsum.p, hsum.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (nitems) TRMF_HIP_CHECK(hipMemcpyAsync(hscore.data(), score.p, hscore.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (Wout) TRMF_HIP_CHECK(hipMemcpyAsync(hflat.data(), flat.p, hflat.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
-        if (weights_out && nw) TRMF_HIP_CHECK(hipMemcpyAsync(hwts.data(), wts.p, hwts.size() * sizeof(real), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        if (bad != kAssimNoBadRow) { res->bad_row = first_row + bad; return 0; }
-        // ---- commit ----
-        TRMF_HIP_CHECK(hipMemcpyAsync(W.p + (size_t)first_row * KP, xc.p, (size_t)m * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-        if (first_row < ad_rows) adapt_stale();                     // rows the series statistics absorbed have changed
-        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new W
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        res->rows = (uint64_t)m;
-        res->entries = nw;
-        res->sweeps = sweeps;
-        res->converged = 1;
-        for (int s = 0; s < sweeps; s++) {
-            const int it = hst[s].done ? hst[s].iters : max_iter;
-            res->iterations += it;
-            if (!hst[s].done) res->converged = 0;
-            if (s == sweeps - 1) res->residual = hst[s].rz0 > 0 ? std::sqrt(std::max(hst[s].rz[it & 1], 0.0) / hst[s].rz0) : 0.0;
-        }
-        double down = 0, w2[2] = {0, 0}, e2[2] = {0, 0}, rho[2] = {0, 0};
-        for (int r = 0; r < m; r++) {                               // row order, then item order: the same sums on every rank and every call
-            down += hsum[2 * r]; res->weight_sum += hsum[2 * r + 1];
-            w2[0] += hobj[4 * r]; e2[0] += hobj[4 * r + 1]; w2[1] += hobj[4 * r + 2]; e2[1] += hobj[4 * r + 3];
-        }
-        for (uint32_t it = 0; it < nitems; it++) {
-            const double *a0 = hscore.data() + (size_t)it * kSmoothRobustSlotD, *a1 = a0 + ni * kSmoothRobustSlotD;
-            rho[0] += a0[2]; res->sq_err_before += a0[3]; rho[1] += a1[2]; res->sq_err_after += a1[3];
-        }
-        res->downweighted = (uint64_t)down;
-        res->objective_before = rho[0] + 0.5 * ((double)lamI * w2[0] + (double)lamAR * e2[0]);
-        res->objective_after = rho[1] + 0.5 * ((double)lamI * w2[1] + (double)lamAR * e2[1]);
-        if (Wout) std::memcpy(Wout, hflat.data(), hflat.size() * sizeof(real));
-        if (weights_out && nw) std::memcpy(weights_out, hwts.data(), hwts.size() * sizeof(real));
-        return 0;
-    }
-    // ---- online loading updates (trmf_session_series_stats_init / _adapt_series; adapt_kernels.hpp) -----------------------------------
-    // One pass for both calls (the caller has validated the rank, gamma and the state of the tables).  init: the tables over all
-    // rows from zero, H untouched (the pass's solve is discarded with its flag).  Otherwise: the active generation scaled by gamma^m
-    // plus the entries not yet absorbed, then every h_j.  Everything lands in the inactive generation and in scratch; the generation,
-    // the absorbed counts and H move after the one flag read.  No collective: every rank holds the whole Y and W and computes the
-    // same bits.  A bad pivot or a pool that cannot hold the tables is not a failure of this rank's task (res->bad_series /
-    // res->no_memory; nothing is committed): the entry point reports it on the calling thread, so the barrier of a TRMF_DEVICES
-    // group stays whole.
-    struct AdaptResult {
-        uint64_t series = 0, rows = 0, entries = 0;
-        double sq_err_before = 0, sq_err_after = 0, max_abs_change = 0;
-        int bad_series = -1, no_memory = 0;
-    };
-    int adapt_series(bool init, double forget, AdaptResult *res, real *Hout) {
-        *res = AdaptResult{};
-        if (sync()) return kFail;
-        FillStreamScope fill(stream);
-        const double gam = init ? forget : ad_gamma;
-        const int row0 = init ? 0 : ad_rows, m = T - row0;
-        const size_t PK = adapt_packed(k), nS = full ? PK : (size_t)n * PK, nR = (size_t)n * k;
-        if (init && (!ad_exists || ad_S[0].n != nS || ad_r[0].n != nR)) {      // (change_series releases stale tables: the series count moved)
-            if (ad_S[0].alloc(nS, false) || ad_S[1].alloc(nS, false) || ad_r[0].alloc(nR, false) || ad_r[1].alloc(nR, false)) {
-                for (int q = 0; q < 2; q++) { ad_S[q].release(); ad_r[q].release(); }
-                res->no_memory = 1;
-                return 0;
-            }
-            ad_exists = true; ad_valid = false; ad_cur = 0;
-        }
-        const int in = ad_cur, out = 1 - ad_cur;
-        // the weights of the rows walked, gamma^(T - 1 - t), and the decay of what the tables hold
-        std::vector<real> hom;
-        if (gam != 1.0) {
-            hom.resize((size_t)std::max(m, 1));
-            for (int i = 0; i < m; i++) hom[i] = (real)std::pow(gam, (double)(T - 1 - (row0 + i)));
-        }
-        const real decay = (real)std::pow(gam, (double)m);
-        // sparse storage: where each column's walk starts; the init pass cuts long columns into items
-        std::vector<uint32_t> hstart, hfirst, hitems;
-        if (!dense) {
-            hstart.resize((size_t)n);
-            for (int j = 0; j < n; j++) hstart[j] = (uint32_t)(host_col_ptr[j] + (init ? 0u : ad_cnt[j]));
-        }
-        if (init && !full) {
-            uint64_t chunk = std::max<uint64_t>(kAdaptChunk, (nnz + kAdaptMaxItems - 1) / kAdaptMaxItems);
-            if (const char *e = test_env("TRMF_ADAPT_CHUNK")) chunk = (uint64_t)std::max(1, atoi(e));      // tests: several items per series on a small shape
-            hfirst.resize((size_t)n + 1);
-            for (int j = 0; j < n; j++) {
-                hfirst[j] = (uint32_t)(hitems.size() / 2);
-                if (host_col_ptr[j + 1] - host_col_ptr[j] > chunk)
-                    for (uint64_t b = host_col_ptr[j]; b < host_col_ptr[j + 1]; b += chunk) {
-                        hitems.push_back((uint32_t)b); hitems.push_back((uint32_t)std::min<uint64_t>(b + chunk, host_col_ptr[j + 1]));
-                    }
-            }
-            hfirst[n] = (uint32_t)(hitems.size() / 2);
-        }
-        const uint32_t nitems = (uint32_t)(hitems.size() / 2);
-        DevBuf<real> Hn, chg, mx, om, slab, U;
-        DevBuf<uint32_t> d_start, d_first, d_items;
-        DevBuf<int> flag;
-        DevBuf<double> errs;
-        SyncStreamOnExit drain(stream);
-        if (Hn.alloc((size_t)n * KP) || chg.alloc(n, false) || mx.alloc(1) || flag.alloc(1, false) || errs.alloc((size_t)4 * std::max(m, 1), false) ||
-            (!hom.empty() && om.upload(hom.data(), hom.size())) || (!dense && d_start.upload(hstart.data(), hstart.size())) ||
-            (nitems && (d_first.upload(hfirst.data(), hfirst.size()) || d_items.upload(hitems.data(), hitems.size()) ||
-                        slab.alloc((size_t)nitems * adapt_part_reals(k), false))) ||
-            (full && U.alloc((size_t)k * k, false))) return kFail;
-        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
-        const real *omp = hom.empty() ? nullptr : om.p;
-        const real *Sin = init ? nullptr : ad_S[in].p, *rin = init ? nullptr : ad_r[in].p;
-        if (!full) {
-            AdaptArgs a{Yc_ptr.p, Yc_idx.p, Yc_val.p, d_start.p, W.p, omp, Sin, rin, ad_S[out].p, ad_r[out].p, nitems ? d_first.p : nullptr,
-                        nitems ? d_items.p : nullptr, nitems ? slab.p : nullptr, H.p, Hn.p, chg.p, flag.p, decay, (real)lambdaI, row0, n, k, KP};
-            if (!with_nt(NT, [&](auto N) {
-                    if (nitems) hipLaunchKernelGGL(adapt_part_kernel<decltype(N)::value>, dim3(nitems), dim3(64), 0, stream, a);
-                    hipLaunchKernelGGL(adapt_series_kernel<decltype(N)::value>, dim3(n), dim3(64), 0, stream, a);
-                })) return unsupported_rank();
-        } else {
-            AdaptFullArgs a{dense ? nullptr : Yc_ptr.p, dense ? nullptr : Yc_idx.p, dense ? nullptr : Yc_val.p, dense ? nullptr : d_start.p,
-                            dense ? Yd_nt.p : nullptr, W.p, omp, Sin, rin, ad_S[out].p, ad_r[out].p, U.p, H.p, Hn.p, chg.p, decay, row0, T, n, k, KP, NT};
-            hipLaunchKernelGGL(adapt_full_gram_kernel, dim3((unsigned)((PK + 255) / 256)), dim3(256), 0, stream, a);
-            hipLaunchKernelGGL(adapt_full_rhs_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, a);
-            AssimFactorArgs fa{ad_S[out].p, (size_t)0, 1, U.p, flag.p, (real)lambdaI, 0, 1, k};       // the one shared system: "series 0" names it
-            if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(assim_factor_kernel<decltype(N)::value>, dim3(1), dim3(256), 0, stream, fa); }))
-                return unsupported_rank();
-            hipLaunchKernelGGL(adapt_full_subst_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, a);
-        }
-        TRMF_HIP_CHECK(hipGetLastError());
-        if (init) {                                                 // H stays: only the tables are handed over
-            TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-            ad_cur = out; ad_valid = true; ad_gamma = forget; ad_rows = T;
-            if (!dense) { ad_cnt.resize((size_t)n); for (int j = 0; j < n; j++) ad_cnt[j] = (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j]); }
-            res->series = (uint64_t)n; res->rows = (uint64_t)T;
-            res->entries = full ? (uint64_t)T * (uint64_t)n : nnz;
-            return 0;
-        }
-        hipLaunchKernelGGL(adapt_max_kernel, dim3(1), dim3(256), 0, stream, chg.p, n, mx.p);
-        if (m > 0) {   // the squared errors of the absorbed rows with H as it is and as it will be (assim_err_kernel's reading of an entry)
-            for (int pass = 0; pass < 2; pass++) {
-                AssimErrArgs ea{dense ? nullptr : Yr_ptr.p, dense ? nullptr : Yr_idx.p, dense ? nullptr : Yr_val.p, dense ? Yd_tn.p : nullptr,
-                                pass ? Hn.p : H.p, W.p, W.p, 0, 0, errs.p + (size_t)2 * m * pass, row0, m, n, KP, full ? 1 : 0};
-                hipLaunchKernelGGL(assim_err_kernel, dim3(m), dim3(256), 0, stream, ea);
-            }
-        }
-        TRMF_HIP_CHECK(hipGetLastError());
-        int bad = kAdaptNoBadSeries;
-        real hmx = 0;
-        std::vector<double> herr((size_t)4 * std::max(m, 1), 0.0);
-        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(&hmx, mx.p, sizeof(real), hipMemcpyDeviceToHost, stream));
-        if (m > 0) TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, (size_t)4 * m * sizeof(double), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        if (bad != kAdaptNoBadSeries) { res->bad_series = bad; return 0; }
-        if (Hout && download_padded(Hn, Hout, (size_t)n)) return kFail;
-        // ---- commit ----
-        TRMF_HIP_CHECK(hipMemcpyAsync(H.p, Hn.p, (size_t)n * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new H
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        ad_cur = out; ad_rows = T;
-        if (!dense) for (int j = 0; j < n; j++) ad_cnt[j] = (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j]);
-        res->series = (uint64_t)n; res->rows = (uint64_t)m;
-        res->entries = full ? (uint64_t)m * (uint64_t)n : host_row_ptr[T] - host_row_ptr[row0];
-        for (int r = 0; r < m; r++) { res->sq_err_before += herr[2 * r]; res->sq_err_after += herr[(size_t)2 * m + 2 * r]; }
-        res->max_abs_change = (double)hmx;
-        return 0;
-    }
-    // ---- robust online loading updates (trmf_session_adapt_series_robust; adapt_robust_kernels.hpp) -----------------------------------
-    // adapt_series() with Huber weights on the entries not yet absorbed (the caller has validated the rank, the storage -- sparse
-    // with missing != 0 --, the state of the tables, c, the sweep count and the n scales, which arrive as host values on every
-    // rank).  One launch of the per-series kernel runs every sweep; one launch of the objective kernel gives J_j before and after.
-    // Everything lands in the inactive generation and in scratch; the generation, the absorbed counts and H move after the one
-    // flag read.  The weights always come back to the host: downweighted and weight_sum are folded from them in series order.
-    struct RobustAdaptResult {
-        uint64_t series = 0, rows = 0, entries = 0, downweighted = 0;
-        double sq_err_before = 0, sq_err_after = 0, max_abs_change = 0, weight_sum = 0, objective_before = 0, objective_after = 0;
-        int bad_series = -1;
-    };
-    int adapt_series_robust(double c, int sweeps, const double *scale, RobustAdaptResult *res, real *Hout, uint64_t *wptr_out, uint32_t *wrows_out,
-                            real *weights_out) {
-        *res = RobustAdaptResult{};
-        if (sync()) return kFail;
-        FillStreamScope fill(stream);
-        const double gam = ad_gamma;
-        const int row0 = ad_rows, m = T - row0;
-        const int in = ad_cur, out = 1 - ad_cur;
-        std::vector<real> hom;
-        if (gam != 1.0) {
-            hom.resize((size_t)std::max(m, 1));
-            for (int i = 0; i < m; i++) hom[i] = (real)std::pow(gam, (double)(T - 1 - (row0 + i)));
-        }
-        const real decay = (real)std::pow(gam, (double)m);
-        std::vector<uint32_t> hstart((size_t)n), hwptr((size_t)n + 1);
-        std::vector<real> hthr((size_t)n);
-        hwptr[0] = 0;
-        for (int j = 0; j < n; j++) {
-            hstart[j] = (uint32_t)(host_col_ptr[j] + ad_cnt[j]);
-            hwptr[j + 1] = hwptr[j] + (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j] - ad_cnt[j]);
-            hthr[j] = (real)c * (real)scale[j];
-        }
-        const size_t nw = hwptr[n];
-        DevBuf<real> Hn, chg, mx, om, thr, wts;
-        DevBuf<uint32_t> d_start, d_wptr, wrw;
-        DevBuf<int> flag;
-        DevBuf<double> errs, obj;
-        SyncStreamOnExit drain(stream);
-        if (Hn.alloc((size_t)n * KP) || chg.alloc(n, false) || mx.alloc(1) || flag.alloc(1, false) || errs.alloc((size_t)4 * std::max(m, 1), false) ||
-            (!hom.empty() && om.upload(hom.data(), hom.size())) || d_start.upload(hstart.data(), hstart.size()) ||
-            d_wptr.upload(hwptr.data(), hwptr.size()) || thr.upload(hthr.data(), hthr.size()) || wts.alloc(std::max<size_t>(nw, 1), false) ||
-            wrw.alloc(std::max<size_t>(nw, 1), false) || obj.alloc((size_t)2 * n, false)) return kFail;
-        TRMF_HIP_CHECK(hipMemsetAsync(flag.p, 0x7f, sizeof(int), stream));
-        AdaptRobustArgs a{Yc_ptr.p, Yc_idx.p, Yc_val.p, d_start.p, W.p, hom.empty() ? nullptr : om.p, ad_S[in].p, ad_r[in].p, ad_S[out].p, ad_r[out].p,
-                          H.p, Hn.p, chg.p, flag.p, thr.p, d_wptr.p, wts.p, wrw.p, obj.p, decay, (real)lambdaI, row0, n, k, KP, NT, sweeps};
-        if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(adapt_robust_series_kernel<decltype(N)::value>, dim3(n), dim3(64), 0, stream, a); }))
-            return unsupported_rank();
-        hipLaunchKernelGGL(adapt_robust_objective_kernel, dim3(n), dim3(64), 0, stream, a);
-        hipLaunchKernelGGL(adapt_max_kernel, dim3(1), dim3(256), 0, stream, chg.p, n, mx.p);
-        if (m > 0) {   // the squared errors of the absorbed rows with H as it is and as it will be (unweighted; adapt_series' sums)
-            for (int pass = 0; pass < 2; pass++) {
-                AssimErrArgs ea{Yr_ptr.p, Yr_idx.p, Yr_val.p, nullptr, pass ? Hn.p : H.p, W.p, W.p, 0, 0, errs.p + (size_t)2 * m * pass, row0, m, n, KP, 0};
-                hipLaunchKernelGGL(assim_err_kernel, dim3(m), dim3(256), 0, stream, ea);
-            }
-        }
-        TRMF_HIP_CHECK(hipGetLastError());
-        int bad = kAdaptNoBadSeries;
-        real hmx = 0;
-        std::vector<double> herr((size_t)4 * std::max(m, 1), 0.0), hobj((size_t)2 * n);
-        std::vector<real> hwts(nw);
-        std::vector<uint32_t> hwrw(wrows_out ? nw : 0);
-        TRMF_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(&hmx, mx.p, sizeof(real), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipMemcpyAsync(hobj.data(), obj.p, hobj.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (m > 0) TRMF_HIP_CHECK(hipMemcpyAsync(herr.data(), errs.p, (size_t)4 * m * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (nw) TRMF_HIP_CHECK(hipMemcpyAsync(hwts.data(), wts.p, nw * sizeof(real), hipMemcpyDeviceToHost, stream));
-        if (wrows_out && nw) TRMF_HIP_CHECK(hipMemcpyAsync(hwrw.data(), wrw.p, nw * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        if (bad != kAdaptNoBadSeries) { res->bad_series = bad; return 0; }
-        if (Hout && download_padded(Hn, Hout, (size_t)n)) return kFail;
-        // ---- commit ----
-        TRMF_HIP_CHECK(hipMemcpyAsync(H.p, Hn.p, (size_t)n * KP * sizeof(real), hipMemcpyDeviceToDevice, stream));
-        if (snap_iter >= 0 && take_snapshot()) return kFail;       // the recovery snapshot follows the new H
-        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
-        ad_cur = out; ad_rows = T;
-        for (int j = 0; j < n; j++) ad_cnt[j] = (uint32_t)(host_col_ptr[j + 1] - host_col_ptr[j]);
-        res->series = (uint64_t)n; res->rows = (uint64_t)m;
-        res->entries = (uint64_t)nw;
-        for (int r = 0; r < m; r++) { res->sq_err_before += herr[2 * r]; res->sq_err_after += herr[(size_t)2 * m + 2 * r]; }
-        for (int j = 0; j < n; j++) { res->objective_before += hobj[2 * j]; res->objective_after += hobj[2 * j + 1]; }       // series order
-        for (size_t e = 0; e < nw; e++) { res->downweighted += hwts[e] < real(1) ? 1u : 0u; res->weight_sum += (double)hwts[e]; }
-        res->max_abs_change = (double)hmx;
-        if (wptr_out) for (int j = 0; j <= n; j++) wptr_out[j] = (uint64_t)hwptr[j];
-        if (wrows_out && nw) std::memcpy(wrows_out, hwrw.data(), nw * sizeof(uint32_t));
-        if (weights_out && nw) std::memcpy(weights_out, hwts.data(), nw * sizeof(real));
         return 0;
     }
     // New regularisation weights for the iterations enqueued from now on: the session's own copies (F-solve, Theta-solve, the

@@ -21,7 +21,7 @@
 #include <map>
 #include <thread>
 
-#include "session.hpp"
+#include "session_online.hpp"
 
 namespace trmf {
 

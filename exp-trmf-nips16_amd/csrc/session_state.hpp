@@ -3,7 +3,8 @@
 //   SessionState  ->  SessionTransport (session_transport.hpp: communicator gathers, peer-to-peer arenas, exchanges)
 //                 ->  SessionFPhase    (session_fphase.hpp: the F-solve and its sharding / overlap)
 //                 ->  SessionXPhase    (session_xphase.hpp: X-side Gram build, the forms of the CG, Theta)
-//                 ->  TrmfSessionImpl  (session.hpp: set-up, growth, measure-once decisions, the ALS loop, recovery, statistics)
+//                 ->  SessionCore      (session.hpp: set-up, measure-once decisions, the ALS loop, recovery, statistics, forecasts)
+//                 ->  TrmfSessionImpl  (session_online.hpp: growth and the sliding window, series churn, the online solves)
 //
 // HBM layout (all resident for the lifetime of a session):
 //   Yc_*   CSC of Y viewed as CSR over items   (F-solve rows):  ptr u32[n+1], idx u32[nnz], val[nnz]

@@ -138,6 +138,15 @@ struct SessionHandle {
     int rank0(const std::function<int(TrmfSessionImpl *)> &f) const {
         return group ? group->on_rank0([&](int) { return f(group->impl[0]); }) : f(single);
     }
+    // call(session, slot, &result[slot]) on every rank's session, one result per rank of a group (one otherwise); slot 0 is the
+    // session whose outputs go to the caller.  Every rank computes the same bits, so a condition that every rank finds alike (a bad
+    // pivot) is read from the results on the calling thread, not raised by a failing worker task.  Empty: a task failed.
+    template <class R, class F>
+    std::vector<R> per_rank(F &&call) const {
+        std::vector<R> res(group ? (size_t)group->world() : 1);
+        if (all([&](TrmfSessionImpl *t) { const int slot = group ? t->comm->rank : 0; return call(t, slot, &res[slot]); })) res.clear();
+        return res;
+    }
     ~SessionHandle() {
         if (group) SessionGroup::release(group);      // the sessions go; threads + communicators wait for the next call (session_group.hpp)
         else if (single) { (void)single->sync(false); delete single; }
@@ -171,6 +180,76 @@ static SessionHandle *make_session(const PyMatrix *Y, const uint32_t *lag_set, u
     if (rc) { fprintf(stderr, "[ERR MSG]: %s\n", trmf_last_error()); return nullptr; }    // (~SessionHandle tears the group down)
     if (verbose) fprintf(stderr, ">> %d ranks as threads of this process on devices TRMF_DEVICES; communicator: %s\n", h->group->world(), h->group->comm_kind.c_str());
     return h.release();
+}
+
+// ---- the checks of the online entry points ------------------------------------------------------------------------------------
+// Each returns true, with the error set, when the call is refused.  All of them run on the calling thread, before DeviceGuard and
+// before any rank's worker (a rejected call must not break the barrier of a TRMF_DEVICES group); `what` is the call's name as its
+// messages spell it, and what differs between the calls' messages is passed in.
+static bool refused(const std::string &why) { set_error(why); return true; }
+static bool rank_refusal(const TrmfSessionImpl *f, const std::string &what) {
+    return f->k > kMaxRank && refused(what + ": online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
+}
+static bool online_refusal(const TrmfSessionImpl *f, const std::string &what) {
+    return rank_refusal(f, what) || (f->has_lag0 && refused(what + ": the lag set contains lag 0 (a row would be its own prior)"));
+}
+// the calls that report a weight per stored entry
+static bool weight_slot_refusal(const TrmfSessionImpl *f, const std::string &what) {
+    return f->full && !f->dense && refused(what + ": sparse storage with missing == 0 is not covered (an absent entry there is an observation without a slot "
+                                                  "to report its weight in); store the matrix dense");
+}
+static bool first_row_refusal(const TrmfSessionImpl *f, const std::string &what, int32_t first_row) {
+    return (first_row < f->midx || first_row > f->T) &&
+           refused(what + ": first_row " + std::to_string(first_row) + " outside [" + std::to_string(f->midx) + " (the largest lag), " + std::to_string(f->T) + " (rows)]");
+}
+// The smoothers' window: its cap, and the PCG's stop with the defaults put in (the robust smoother checks c and sweeps between the two).
+static bool window_refusal(const TrmfSessionImpl *f, const std::string &what, int32_t first_row) {
+    const int cap = TrmfSessionImpl::smooth_max_rows();
+    return f->T - first_row > cap && refused(what + ": a window of " + std::to_string(f->T - first_row) + " rows is above the cap of " + std::to_string(cap) +
+                                             " rows (the factors of every window row stay resident for the solve)");
+}
+static bool window_refusal(const std::string &what, double &rtol, int32_t &max_iter) {
+    if (!std::isfinite(rtol)) return refused(what + ": rtol must be finite (<= 0: the default of the element type)");
+    if (max_iter > kSmoothMaxIter) return refused(what + ": max_iter " + std::to_string(max_iter) + " above " + std::to_string(kSmoothMaxIter));
+    if (rtol <= 0) rtol = kSmoothDefaultRtol;
+    if (max_iter <= 0) max_iter = kSmoothDefaultMaxIter;
+    return false;
+}
+// plain: what c == infinity amounts to, in the call's own words
+static bool huber_refusal(const std::string &what, double c, int32_t sweeps, int max_sweeps, const char *plain) {
+    if (!(c > 0)) return refused(what + ": c must be positive (infinity: " + plain + ")");
+    return (sweeps < 1 || sweeps > max_sweeps) && refused(what + ": sweeps " + std::to_string(sweeps) + " outside 1.." + std::to_string(max_sweeps));
+}
+static bool scale_refusal(const TrmfSessionImpl *f, const std::string &what, const double *scale) {
+    return !scale && !f->nz_set && refused(what + ": no scale given and no noise fitted or set (trmf_session_fit_noise / _set_noise)");
+}
+static bool stats_refusal(const TrmfSessionImpl *f, const std::string &what) {
+    if (!f->ad_exists) return refused(what + ": no series statistics (trmf_session_series_stats_init first)");
+    return !f->ad_valid && refused(what + ": the series statistics are stale: rows they absorbed may have changed (run, rewind, assimilate below the absorbed "
+                                          "rows, or a new series transform); initialise them again (trmf_session_series_stats_init)");
+}
+// The n scales every rank receives as the same host values: the caller's, or the square roots of the resident noise (read from rank
+// 0's device, hence after DeviceGuard); each must be finite and positive.
+static bool resolve_scales(const SessionHandle *s, const TrmfSessionImpl *f, const std::string &what, const double *scale, std::vector<double> &sc) {
+    sc.resize((size_t)f->n);
+    if (scale) std::copy(scale, scale + f->n, sc.begin());
+    else {
+        if (s->rank0([&](TrmfSessionImpl *t) { return t->noise(sc.data(), nullptr); })) return true;
+        for (double &v : sc) v = std::sqrt(v);
+    }
+    for (int j = 0; j < f->n; j++)
+        if (!(std::isfinite(sc[j]) && sc[j] > 0))
+            return refused(what + ": the scale of series " + std::to_string(j) + " is not finite and positive" + (scale ? "" : " (the square root of the resident sigma2)"));
+    return false;
+}
+// A bad pivot of a row's system, found by every rank alike.  gram: "G", or "the weighted G" of the robust calls.
+template <class R>
+static bool pivot_refusal(const std::string &what, const std::vector<R> &res, const char *gram) {
+    for (const R &r : res)
+        if (r.bad_row >= 0)
+            return refused(what + ": row " + std::to_string(r.bad_row) + ": a pivot of " + gram + " + (lambdaI + lambdaAR) I is not positive and finite "
+                           "(lambdaI + lambdaAR == 0 and a rank-deficient row?); nothing was changed");
+    return false;
 }
 
 }  // namespace trmf
@@ -385,18 +464,15 @@ int32_t trmf_session_slide(TrmfSession *s, const PyMatrix *Ynew, int32_t retire,
     if (!why.empty()) { set_error(why); return kFail; }
     DeviceGuard guard;
     if (!guard.ok) return kFail;
-    TrmfSessionImpl::SlideResult res;
-    const int rc = HND(s)->all([&](TrmfSessionImpl *t) {
-        TrmfSessionImpl::SlideResult r;
-        const int c = t->slide(Ynew, retire, downdate_stats != 0, &r);
-        if (c == 0 && t->comm->rank == 0) res = r;
-        return c;
-    });
-    if (rc == 0 && out) {
+    const auto all = HND(s)->per_rank<TrmfSessionImpl::SlideResult>(
+        [&](TrmfSessionImpl *t, int, TrmfSessionImpl::SlideResult *r) { return t->slide(Ynew, retire, downdate_stats != 0, r); });
+    if (all.empty()) return kFail;
+    if (out) {
+        const auto &res = all[0];
         out->rows_retired = res.rows_retired; out->entries_retired = res.entries_retired; out->rows_appended = res.rows_appended;
         out->entries_appended = res.entries_appended; out->rows = res.rows; out->entries = res.entries;
     }
-    return rc;
+    return 0;
 }
 // Series churn: validated here like slide; a pivot of the cold-start fit that is not positive is found by every rank alike and
 // reported here, not by a failing worker task.
@@ -407,11 +483,10 @@ int32_t trmf_session_change_series(TrmfSession *s, const uint8_t *keep, const Py
     if (!why.empty()) { set_error(why); return kFail; }
     DeviceGuard guard;
     if (!guard.ok) return kFail;
-    const bool grouped = HND(s)->group != nullptr;
-    std::vector<TrmfSessionImpl::ChurnResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
-    if (HND(s)->all([&](TrmfSessionImpl *t) {
-            return t->change_series(keep, Ynew, fit != 0, (const real *)Hnew, (const real *)tr_a_new, (const real *)tr_b_new, &res[grouped ? t->comm->rank : 0]);
-        })) return kFail;
+    const auto res = HND(s)->per_rank<TrmfSessionImpl::ChurnResult>([&](TrmfSessionImpl *t, int, TrmfSessionImpl::ChurnResult *r) {
+        return t->change_series(keep, Ynew, fit != 0, (const real *)Hnew, (const real *)tr_a_new, (const real *)tr_b_new, r);
+    });
+    if (res.empty()) return kFail;
     for (const auto &r : res)
         if (r.bad_series >= 0) {
             const TrmfSessionImpl *f = HND(s)->first();
@@ -592,92 +667,38 @@ int32_t trmf_session_lag_stats(TrmfSession *s, int32_t *per_dim, int32_t *capped
     return HND(s)->rank0([&](TrmfSessionImpl *t) { return t->lag_stats(per_dim, capped, refit_skipped); });
 }
 
-// Online update: the arguments are checked on the calling thread before any rank's worker runs (see trmf_session_set_heldout); a
-// bad pivot is found on the device by every rank alike and reported here, not by a failing worker task.
+// The online solves.  Every argument -- the scales included, which every rank receives as the same host values -- is checked on the
+// calling thread before any rank's worker runs (the helpers above; see trmf_session_set_heldout); a bad pivot or a pool without
+// room is found on the device by every rank alike and reported here, not by a failing worker task.
 int32_t trmf_session_assimilate(TrmfSession *s, int32_t first_row, TrmfAssimilateSums *out, void *Wnew) {
     if (!s) { set_error("null session"); return kFail; }
     const TrmfSessionImpl *f = HND(s)->first();
-    if (f->k > kMaxRank) {
-        set_error("assimilate: online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
-        return kFail;
-    }
-    if (f->has_lag0) { set_error("assimilate: the lag set contains lag 0 (a row would be its own prior)"); return kFail; }
-    if (first_row < f->midx || first_row > f->T) {
-        set_error("assimilate: first_row " + std::to_string(first_row) + " outside [" + std::to_string(f->midx) + " (the largest lag), " +
-                  std::to_string(f->T) + " (rows)]");
-        return kFail;
-    }
+    const std::string what = "assimilate";
+    if (online_refusal(f, what) || first_row_refusal(f, what, first_row)) return kFail;
     DeviceGuard guard;
     if (!guard.ok) return kFail;
-    const bool grouped = HND(s)->group != nullptr;
-    std::vector<TrmfSessionImpl::AssimResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
-    if (HND(s)->all([&](TrmfSessionImpl *t) {
-            const int slot = grouped ? t->comm->rank : 0;
-            return t->assimilate(first_row, &res[slot], slot == 0 ? (real *)Wnew : nullptr);
-        })) return kFail;
-    for (const auto &r : res)
-        if (r.bad_row >= 0) {
-            set_error("assimilate: row " + std::to_string(r.bad_row) + ": a pivot of G + (lambdaI + lambdaAR) I is not positive and finite "
-                      "(lambdaI + lambdaAR == 0 and a rank-deficient row?); nothing was changed");
-            return kFail;
-        }
+    const auto res = HND(s)->per_rank<TrmfSessionImpl::AssimResult>(
+        [&](TrmfSessionImpl *t, int slot, TrmfSessionImpl::AssimResult *r) { return t->assimilate(first_row, r, slot == 0 ? (real *)Wnew : nullptr); });
+    if (res.empty() || pivot_refusal(what, res, "G")) return kFail;
     if (out) { out->rows = res[0].rows; out->entries = res[0].entries; out->sq_err_before = res[0].sq_err_before; out->sq_err_after = res[0].sq_err_after; }
     return 0;
 }
 
-// Robust online update: like trmf_session_assimilate, every argument -- the scales included, which every rank receives as the same
-// host values -- is checked on the calling thread before any rank's worker runs.
 int32_t trmf_session_assimilate_robust(TrmfSession *s, int32_t first_row, double c, int32_t sweeps, const double *scale, TrmfRobustSums *out,
                                        void *Wnew, void *weights) {
     if (!s) { set_error("null session"); return kFail; }
     const TrmfSessionImpl *f = HND(s)->first();
-    if (f->k > kMaxRank) {
-        set_error("assimilate_robust: online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
-        return kFail;
-    }
-    if (f->has_lag0) { set_error("assimilate_robust: the lag set contains lag 0 (a row would be its own prior)"); return kFail; }
-    if (f->full && !f->dense) {
-        set_error("assimilate_robust: sparse storage with missing == 0 is not covered (an absent entry there is an observation without a slot "
-                  "to report its weight in); store the matrix dense");
-        return kFail;
-    }
-    if (first_row < f->midx || first_row > f->T) {
-        set_error("assimilate_robust: first_row " + std::to_string(first_row) + " outside [" + std::to_string(f->midx) + " (the largest lag), " +
-                  std::to_string(f->T) + " (rows)]");
-        return kFail;
-    }
-    if (!(c > 0)) { set_error("assimilate_robust: c must be positive (infinity: the plain filter)"); return kFail; }
-    if (sweeps < 1 || sweeps > kAssimRobustMaxSweeps) {
-        set_error("assimilate_robust: sweeps " + std::to_string(sweeps) + " outside 1.." + std::to_string(kAssimRobustMaxSweeps));
-        return kFail;
-    }
-    if (!scale && !f->nz_set) { set_error("assimilate_robust: no scale given and no noise fitted or set (trmf_session_fit_noise / _set_noise)"); return kFail; }
+    const std::string what = "assimilate_robust";
+    if (online_refusal(f, what) || weight_slot_refusal(f, what) || first_row_refusal(f, what, first_row) ||
+        huber_refusal(what, c, sweeps, kAssimRobustMaxSweeps, "the plain filter") || scale_refusal(f, what, scale)) return kFail;
     DeviceGuard guard;
     if (!guard.ok) return kFail;
-    std::vector<double> sc((size_t)f->n);
-    if (scale) std::copy(scale, scale + f->n, sc.begin());
-    else {
-        if (HND(s)->rank0([&](TrmfSessionImpl *t) { return t->noise(sc.data(), nullptr); })) return kFail;
-        for (double &v : sc) v = std::sqrt(v);
-    }
-    for (int j = 0; j < f->n; j++)
-        if (!(std::isfinite(sc[j]) && sc[j] > 0)) {
-            set_error("assimilate_robust: the scale of series " + std::to_string(j) + " is not finite and positive" +
-                      (scale ? "" : " (the square root of the resident sigma2)"));
-            return kFail;
-        }
-    const bool grouped = HND(s)->group != nullptr;
-    std::vector<TrmfSessionImpl::RobustResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
-    if (HND(s)->all([&](TrmfSessionImpl *t) {
-            const int slot = grouped ? t->comm->rank : 0;
-            return t->assimilate_robust(first_row, c, sweeps, sc.data(), &res[slot], slot == 0 ? (real *)Wnew : nullptr, slot == 0 ? (real *)weights : nullptr);
-        })) return kFail;
-    for (const auto &r : res)
-        if (r.bad_row >= 0) {
-            set_error("assimilate_robust: row " + std::to_string(r.bad_row) + ": a pivot of the weighted G + (lambdaI + lambdaAR) I is not positive and "
-                      "finite (lambdaI + lambdaAR == 0 and a rank-deficient row?); nothing was changed");
-            return kFail;
-        }
+    std::vector<double> sc;
+    if (resolve_scales(HND(s), f, what, scale, sc)) return kFail;
+    const auto res = HND(s)->per_rank<TrmfSessionImpl::RobustResult>([&](TrmfSessionImpl *t, int slot, TrmfSessionImpl::RobustResult *r) {
+        return t->assimilate_robust(first_row, c, sweeps, sc.data(), r, slot == 0 ? (real *)Wnew : nullptr, slot == 0 ? (real *)weights : nullptr);
+    });
+    if (res.empty() || pivot_refusal(what, res, "the weighted G")) return kFail;
     if (out) {
         out->rows = res[0].rows; out->entries = res[0].entries; out->downweighted = res[0].downweighted;
         out->weight_sum = res[0].weight_sum; out->sq_err_before = res[0].sq_err_before; out->sq_err_after = res[0].sq_err_after;
@@ -685,45 +706,19 @@ int32_t trmf_session_assimilate_robust(TrmfSession *s, int32_t first_row, double
     return 0;
 }
 
-// Fixed-interval smoother: like trmf_session_assimilate, every argument is checked on the calling thread before any rank's worker
-// runs; a bad pivot of a preconditioner block is found on the device by every rank alike and reported here.
+// Fixed-interval smoother: a bad pivot is one of a preconditioner block.
 int32_t trmf_session_smooth(TrmfSession *s, int32_t first_row, double rtol, int32_t max_iter, TrmfSmoothSums *out, void *Wnew) {
     if (!s) { set_error("null session"); return kFail; }
     const TrmfSessionImpl *f = HND(s)->first();
-    if (f->k > kMaxRank) {
-        set_error("smooth: online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
+    const std::string what = "smooth";
+    if (online_refusal(f, what) || first_row_refusal(f, what, first_row) || window_refusal(f, what, first_row) || window_refusal(what, rtol, max_iter))
         return kFail;
-    }
-    if (f->has_lag0) { set_error("smooth: the lag set contains lag 0 (a row would be its own prior)"); return kFail; }
-    if (first_row < f->midx || first_row > f->T) {
-        set_error("smooth: first_row " + std::to_string(first_row) + " outside [" + std::to_string(f->midx) + " (the largest lag), " +
-                  std::to_string(f->T) + " (rows)]");
-        return kFail;
-    }
-    const int cap = TrmfSessionImpl::smooth_max_rows();
-    if (f->T - first_row > cap) {
-        set_error("smooth: a window of " + std::to_string(f->T - first_row) + " rows is above the cap of " + std::to_string(cap) +
-                  " rows (the factors of every window row stay resident for the solve)");
-        return kFail;
-    }
-    if (!std::isfinite(rtol)) { set_error("smooth: rtol must be finite (<= 0: the default of the element type)"); return kFail; }
-    if (max_iter > kSmoothMaxIter) { set_error("smooth: max_iter " + std::to_string(max_iter) + " above " + std::to_string(kSmoothMaxIter)); return kFail; }
-    if (rtol <= 0) rtol = kSmoothDefaultRtol;
-    if (max_iter <= 0) max_iter = kSmoothDefaultMaxIter;
     DeviceGuard guard;
     if (!guard.ok) return kFail;
-    const bool grouped = HND(s)->group != nullptr;
-    std::vector<TrmfSessionImpl::SmoothResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
-    if (HND(s)->all([&](TrmfSessionImpl *t) {
-            const int slot = grouped ? t->comm->rank : 0;
-            return t->smooth(first_row, rtol, max_iter, &res[slot], slot == 0 ? (real *)Wnew : nullptr);
-        })) return kFail;
-    for (const auto &r : res)
-        if (r.bad_row >= 0) {
-            set_error("smooth: row " + std::to_string(r.bad_row) + ": a pivot of G + (lambdaI + lambdaAR) I is not positive and finite "
-                      "(lambdaI + lambdaAR == 0 and a rank-deficient row?); nothing was changed");
-            return kFail;
-        }
+    const auto res = HND(s)->per_rank<TrmfSessionImpl::SmoothResult>([&](TrmfSessionImpl *t, int slot, TrmfSessionImpl::SmoothResult *r) {
+        return t->smooth(first_row, rtol, max_iter, r, slot == 0 ? (real *)Wnew : nullptr);
+    });
+    if (res.empty() || pivot_refusal(what, res, "G")) return kFail;
     if (out) {
         const auto &r = res[0];
         out->rows = r.rows; out->entries = r.entries; out->iterations = r.iterations; out->converged = r.converged; out->residual = r.residual;
@@ -733,70 +728,23 @@ int32_t trmf_session_smooth(TrmfSession *s, int32_t first_row, double rtol, int3
     return 0;
 }
 
-// Robust smoother: the checks of trmf_session_smooth and of trmf_session_assimilate_robust, all on the calling thread before any
-// rank's worker runs.
+// Robust smoother: the checks of trmf_session_smooth and of trmf_session_assimilate_robust.
 int32_t trmf_session_smooth_robust(TrmfSession *s, int32_t first_row, double c, int32_t sweeps, const double *scale, double rtol, int32_t max_iter,
                                    TrmfRobustSmoothSums *out, void *Wnew, void *weights) {
     if (!s) { set_error("null session"); return kFail; }
     const TrmfSessionImpl *f = HND(s)->first();
-    if (f->k > kMaxRank) {
-        set_error("smooth_robust: online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
-        return kFail;
-    }
-    if (f->has_lag0) { set_error("smooth_robust: the lag set contains lag 0 (a row would be its own prior)"); return kFail; }
-    if (f->full && !f->dense) {
-        set_error("smooth_robust: sparse storage with missing == 0 is not covered (an absent entry there is an observation without a slot "
-                  "to report its weight in); store the matrix dense");
-        return kFail;
-    }
-    if (first_row < f->midx || first_row > f->T) {
-        set_error("smooth_robust: first_row " + std::to_string(first_row) + " outside [" + std::to_string(f->midx) + " (the largest lag), " +
-                  std::to_string(f->T) + " (rows)]");
-        return kFail;
-    }
-    const int cap = TrmfSessionImpl::smooth_max_rows();
-    if (f->T - first_row > cap) {
-        set_error("smooth_robust: a window of " + std::to_string(f->T - first_row) + " rows is above the cap of " + std::to_string(cap) +
-                  " rows (the factors of every window row stay resident for the solve)");
-        return kFail;
-    }
-    if (!(c > 0)) { set_error("smooth_robust: c must be positive (infinity: the plain smoother's objective)"); return kFail; }
-    if (sweeps < 1 || sweeps > kSmoothRobustMaxSweeps) {
-        set_error("smooth_robust: sweeps " + std::to_string(sweeps) + " outside 1.." + std::to_string(kSmoothRobustMaxSweeps));
-        return kFail;
-    }
-    if (!std::isfinite(rtol)) { set_error("smooth_robust: rtol must be finite (<= 0: the default of the element type)"); return kFail; }
-    if (max_iter > kSmoothMaxIter) { set_error("smooth_robust: max_iter " + std::to_string(max_iter) + " above " + std::to_string(kSmoothMaxIter)); return kFail; }
-    if (!scale && !f->nz_set) { set_error("smooth_robust: no scale given and no noise fitted or set (trmf_session_fit_noise / _set_noise)"); return kFail; }
-    if (rtol <= 0) rtol = kSmoothDefaultRtol;
-    if (max_iter <= 0) max_iter = kSmoothDefaultMaxIter;
+    const std::string what = "smooth_robust";
+    if (online_refusal(f, what) || weight_slot_refusal(f, what) || first_row_refusal(f, what, first_row) || window_refusal(f, what, first_row) ||
+        huber_refusal(what, c, sweeps, kSmoothRobustMaxSweeps, "the plain smoother's objective") || window_refusal(what, rtol, max_iter) ||
+        scale_refusal(f, what, scale)) return kFail;
     DeviceGuard guard;
     if (!guard.ok) return kFail;
-    std::vector<double> sc((size_t)f->n);
-    if (scale) std::copy(scale, scale + f->n, sc.begin());
-    else {
-        if (HND(s)->rank0([&](TrmfSessionImpl *t) { return t->noise(sc.data(), nullptr); })) return kFail;
-        for (double &v : sc) v = std::sqrt(v);
-    }
-    for (int j = 0; j < f->n; j++)
-        if (!(std::isfinite(sc[j]) && sc[j] > 0)) {
-            set_error("smooth_robust: the scale of series " + std::to_string(j) + " is not finite and positive" +
-                      (scale ? "" : " (the square root of the resident sigma2)"));
-            return kFail;
-        }
-    const bool grouped = HND(s)->group != nullptr;
-    std::vector<TrmfSessionImpl::RobustSmoothResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
-    if (HND(s)->all([&](TrmfSessionImpl *t) {
-            const int slot = grouped ? t->comm->rank : 0;
-            return t->smooth_robust(first_row, c, sweeps, sc.data(), rtol, max_iter, &res[slot], slot == 0 ? (real *)Wnew : nullptr,
-                                    slot == 0 ? (real *)weights : nullptr);
-        })) return kFail;
-    for (const auto &r : res)
-        if (r.bad_row >= 0) {
-            set_error("smooth_robust: row " + std::to_string(r.bad_row) + ": a pivot of the weighted G + (lambdaI + lambdaAR) I is not positive and "
-                      "finite (lambdaI + lambdaAR == 0 and a rank-deficient row?); nothing was changed");
-            return kFail;
-        }
+    std::vector<double> sc;
+    if (resolve_scales(HND(s), f, what, scale, sc)) return kFail;
+    const auto res = HND(s)->per_rank<TrmfSessionImpl::RobustSmoothResult>([&](TrmfSessionImpl *t, int slot, TrmfSessionImpl::RobustSmoothResult *r) {
+        return t->smooth_robust(first_row, c, sweeps, sc.data(), rtol, max_iter, r, slot == 0 ? (real *)Wnew : nullptr, slot == 0 ? (real *)weights : nullptr);
+    });
+    if (res.empty() || pivot_refusal(what, res, "the weighted G")) return kFail;
     if (out) {
         const auto &r = res[0];
         out->rows = r.rows; out->entries = r.entries; out->downweighted = r.downweighted;
@@ -808,30 +756,19 @@ int32_t trmf_session_smooth_robust(TrmfSession *s, int32_t first_row, double c, 
     return 0;
 }
 
-// Online loading updates: the arguments and the state of the tables are checked on the calling thread before any rank's worker runs
-// (see trmf_session_set_heldout); a bad pivot or a pool without room is found by every rank alike and reported here.
+// Online loading updates: the state of the tables is checked like an argument.
 static int adapt_call(TrmfSession *s, bool init, double forget, TrmfAdaptSums *out, void *Hnew) {
     const std::string what = init ? "series_stats_init" : "adapt_series";
     const TrmfSessionImpl *f = HND(s)->first();
-    if (f->k > kMaxRank) {
-        set_error(what + ": online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
-        return kFail;
-    }
+    if (rank_refusal(f, what)) return kFail;
     if (init && !(forget > 0 && forget <= 1)) { set_error("series_stats_init: forget must lie in (0, 1]"); return kFail; }
-    if (!init && !f->ad_exists) { set_error("adapt_series: no series statistics (trmf_session_series_stats_init first)"); return kFail; }
-    if (!init && !f->ad_valid) {
-        set_error("adapt_series: the series statistics are stale: rows they absorbed may have changed (run, rewind, assimilate below the absorbed "
-                  "rows, or a new series transform); initialise them again (trmf_session_series_stats_init)");
-        return kFail;
-    }
+    if (!init && stats_refusal(f, what)) return kFail;
     DeviceGuard guard;
     if (!guard.ok) return kFail;
-    const bool grouped = HND(s)->group != nullptr;
-    std::vector<TrmfSessionImpl::AdaptResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
-    if (HND(s)->all([&](TrmfSessionImpl *t) {
-            const int slot = grouped ? t->comm->rank : 0;
-            return t->adapt_series(init, forget, &res[slot], slot == 0 ? (real *)Hnew : nullptr);
-        })) return kFail;
+    const auto res = HND(s)->per_rank<TrmfSessionImpl::AdaptResult>([&](TrmfSessionImpl *t, int slot, TrmfSessionImpl::AdaptResult *r) {
+        return t->adapt_series(init, forget, r, slot == 0 ? (real *)Hnew : nullptr);
+    });
+    if (res.empty()) return kFail;
     for (const auto &r : res) {
         if (r.no_memory) {
             const size_t PK = adapt_packed(f->k);
@@ -860,56 +797,30 @@ int32_t trmf_session_adapt_series(TrmfSession *s, TrmfAdaptSums *out, void *Hnew
     if (!s) { set_error("null session"); return kFail; }
     return adapt_call(s, false, 1.0, out, Hnew);
 }
-// Robust online loading update: the checks of adapt_series and of assimilate_robust's c, sweeps and scale, all on the calling thread
-// before any rank's worker runs; the scales reach every rank as the same host values.
+// Robust online loading update: the checks of adapt_series and of assimilate_robust's c, sweeps and scale.
 int32_t trmf_session_adapt_series_robust(TrmfSession *s, double c, int32_t sweeps, const double *scale, TrmfRobustAdaptSums *out, void *Hnew,
                                          uint64_t *wptr, uint32_t *wrows, void *weights) {
     if (!s) { set_error("null session"); return kFail; }
     const TrmfSessionImpl *f = HND(s)->first();
-    if (f->k > kMaxRank) {
-        set_error("adapt_series_robust: online updates cover the register-tiled ranks 1..64, this session has rank " + std::to_string(f->k));
-        return kFail;
-    }
+    const std::string what = "adapt_series_robust";
+    if (rank_refusal(f, what)) return kFail;
     if (f->full) {
         set_error(std::string("adapt_series_robust: ") + (f->dense ? "dense storage" : "sparse storage with missing == 0") +
                   " is a full-observation form: it keeps ONE shared S for all series, and a weight per cell needs a table per series "
                   "(sparse storage with missing != 0); use adapt_series");
         return kFail;
     }
-    if (!f->ad_exists) { set_error("adapt_series_robust: no series statistics (trmf_session_series_stats_init first)"); return kFail; }
-    if (!f->ad_valid) {
-        set_error("adapt_series_robust: the series statistics are stale: rows they absorbed may have changed (run, rewind, assimilate below the "
-                  "absorbed rows, or a new series transform); initialise them again (trmf_session_series_stats_init)");
-        return kFail;
-    }
-    if (!(c > 0)) { set_error("adapt_series_robust: c must be positive (infinity: the plain update)"); return kFail; }
-    if (sweeps < 1 || sweeps > kAdaptRobustMaxSweeps) {
-        set_error("adapt_series_robust: sweeps " + std::to_string(sweeps) + " outside 1.." + std::to_string(kAdaptRobustMaxSweeps));
-        return kFail;
-    }
-    if (!scale && !f->nz_set) { set_error("adapt_series_robust: no scale given and no noise fitted or set (trmf_session_fit_noise / _set_noise)"); return kFail; }
+    if (stats_refusal(f, what) || huber_refusal(what, c, sweeps, kAdaptRobustMaxSweeps, "the plain update") || scale_refusal(f, what, scale)) return kFail;
     DeviceGuard guard;
     if (!guard.ok) return kFail;
-    std::vector<double> sc((size_t)f->n);
-    if (scale) std::copy(scale, scale + f->n, sc.begin());
-    else {
-        if (HND(s)->rank0([&](TrmfSessionImpl *t) { return t->noise(sc.data(), nullptr); })) return kFail;
-        for (double &v : sc) v = std::sqrt(v);
-    }
-    for (int j = 0; j < f->n; j++)
-        if (!(std::isfinite(sc[j]) && sc[j] > 0)) {
-            set_error("adapt_series_robust: the scale of series " + std::to_string(j) + " is not finite and positive" +
-                      (scale ? "" : " (the square root of the resident sigma2)"));
-            return kFail;
-        }
-    const bool grouped = HND(s)->group != nullptr;
-    std::vector<TrmfSessionImpl::RobustAdaptResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
-    if (HND(s)->all([&](TrmfSessionImpl *t) {
-            const int slot = grouped ? t->comm->rank : 0;
-            const bool lead = slot == 0;
-            return t->adapt_series_robust(c, sweeps, sc.data(), &res[slot], lead ? (real *)Hnew : nullptr, lead ? wptr : nullptr, lead ? wrows : nullptr,
-                                          lead ? (real *)weights : nullptr);
-        })) return kFail;
+    std::vector<double> sc;
+    if (resolve_scales(HND(s), f, what, scale, sc)) return kFail;
+    const auto res = HND(s)->per_rank<TrmfSessionImpl::RobustAdaptResult>([&](TrmfSessionImpl *t, int slot, TrmfSessionImpl::RobustAdaptResult *r) {
+        const bool lead = slot == 0;
+        return t->adapt_series_robust(c, sweeps, sc.data(), r, lead ? (real *)Hnew : nullptr, lead ? wptr : nullptr, lead ? wrows : nullptr,
+                                      lead ? (real *)weights : nullptr);
+    });
+    if (res.empty()) return kFail;
     for (const auto &r : res)
         if (r.bad_series >= 0) {
             set_error("adapt_series_robust: series " + std::to_string(r.bad_series) + ": a pivot of the weighted S + lambdaI I is not positive and finite "
@@ -944,9 +855,8 @@ int32_t trmf_session_fit_noise(TrmfSession *s, TrmfNoiseStats *out) {
     }
     DeviceGuard guard;
     if (!guard.ok) return kFail;
-    const bool grouped = HND(s)->group != nullptr;
-    std::vector<TrmfSessionImpl::NoiseResult> res(grouped ? (size_t)HND(s)->group->world() : 1);
-    if (HND(s)->all([&](TrmfSessionImpl *t) { return t->fit_noise(&res[grouped ? t->comm->rank : 0]); })) return kFail;
+    const auto res = HND(s)->per_rank<TrmfSessionImpl::NoiseResult>([&](TrmfSessionImpl *t, int, TrmfSessionImpl::NoiseResult *r) { return t->fit_noise(r); });
+    if (res.empty()) return kFail;
     for (const auto &r : res)
         if (r.no_entries) { set_error("fit_noise: the training matrix has no stored entry; nothing was changed"); return kFail; }
     if (out) {

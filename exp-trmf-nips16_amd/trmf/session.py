@@ -521,6 +521,35 @@ class Session(object):
         """Bytes of device memory that live buffers of this process hold in the library's pool right now."""
         return int(self.lib.trmf_device_pool_live_bytes())
 
+    # ---- what the online calls share: scale normalisation, output buffers, pointers, the returned tuple --------------------------
+    def _series_scales(self, what, scale):
+        """``scale`` as n float64 values (one value stands for all series); ``None`` stays ``None`` (the resident noise)."""
+        if scale is None:
+            return None
+        n = self.model.n
+        sc = np.asarray(scale, dtype=np.float64)
+        if sc.ndim == 0:
+            sc = np.full(n, float(sc))
+        if sc.shape != (n,):
+            raise ValueError('{}: scale has shape {}, one value per series ({}) was expected'.format(what, sc.shape, n))
+        return np.ascontiguousarray(sc)
+
+    def _row_weight_buffer(self, first_row, nr, dt):
+        """Room for one weight per stored entry of rows ``first_row ..`` in CSR order, or ``nr`` x n under dense storage."""
+        if self._stored is not None:
+            return np.empty(int(self._stored[first_row:].sum()) if nr and first_row >= 0 else 0, dtype=dt)
+        return np.empty((nr, self.model.n), dtype=dt)
+
+    @staticmethod
+    def _ptr(a):
+        return a.ctypes.data if a is not None and a.size else None
+
+    @staticmethod
+    def _pack(sums, *extras):
+        """``sums`` alone, or a tuple of it and every ``value`` whose ``wanted`` is set."""
+        out = (sums,) + tuple(value for wanted, value in extras if wanted)
+        return out if len(out) > 1 else out[0]
+
     def assimilate(self, first_row, return_latent=False):
         """Online update on the device: rows ``first_row .. rows()-1`` of W are re-solved in ascending order from their own
         observations and the AR prior of the rows before them, with H and the lag weights fixed (``trmf.online.filter_rows``
@@ -536,9 +565,9 @@ class Session(object):
         Wnew = None
         if return_latent:
             Wnew = np.empty((max(self.rows() - first_row, 0), self.model.k), dtype=self.model.W.dtype)
-        self._check(self.lib.trmf_session_assimilate(self.handle, first_row, byref(sums), Wnew.ctypes.data if Wnew is not None and Wnew.size else None),
+        self._check(self.lib.trmf_session_assimilate(self.handle, first_row, byref(sums), self._ptr(Wnew)),
                     'trmf_session_assimilate')
-        return (sums.as_dict(), Wnew) if return_latent else sums.as_dict()
+        return self._pack(sums.as_dict(), (return_latent, Wnew))
 
     def assimilate_robust(self, first_row, c=3.0, sweeps=4, scale=None, return_latent=False, return_weights=False):
         """``assimilate`` with Huber weights (``trmf.online.robust_filter_rows`` is the same computation in NumPy): an entry whose
@@ -554,27 +583,13 @@ class Session(object):
         first_row = int(first_row)
         dt = self.model.W.dtype
         nr = max(self.rows() - first_row, 0)
-        sc = None
-        if scale is not None:
-            sc = np.asarray(scale, dtype=np.float64)
-            if sc.ndim == 0:
-                sc = np.full(self.model.n, float(sc))
-            if sc.shape != (self.model.n,):
-                raise ValueError('assimilate_robust: scale has shape {}, one value per series ({}) was expected'.format(sc.shape, self.model.n))
-            sc = np.ascontiguousarray(sc)
+        sc = self._series_scales('assimilate_robust', scale)
         sums = TrmfRobustSums()
         Wnew = np.empty((nr, self.model.k), dtype=dt) if return_latent else None
-        weights = None
-        if return_weights:
-            if self._stored is not None:
-                weights = np.empty(int(self._stored[first_row:].sum()) if nr and first_row >= 0 else 0, dtype=dt)
-            else:
-                weights = np.empty((nr, self.model.n), dtype=dt)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
-        self._check(self.lib.trmf_session_assimilate_robust(self.handle, first_row, float(c), int(sweeps), ptr(sc), byref(sums), ptr(Wnew), ptr(weights)),
+        weights = self._row_weight_buffer(first_row, nr, dt) if return_weights else None
+        self._check(self.lib.trmf_session_assimilate_robust(self.handle, first_row, float(c), int(sweeps), self._ptr(sc), byref(sums), self._ptr(Wnew), self._ptr(weights)),
                     'trmf_session_assimilate_robust')
-        out = (sums.as_dict(),) + ((Wnew,) if return_latent else ()) + ((weights,) if return_weights else ())
-        return out if len(out) > 1 else out[0]
+        return self._pack(sums.as_dict(), (return_latent, Wnew), (return_weights, weights))
 
     def smooth(self, first_row, rtol=None, max_iter=None, return_latent=False):
         """Fixed-interval smoother on the device: rows ``first_row .. rows()-1`` of W become the JOINT minimiser of the training
@@ -591,8 +606,8 @@ class Session(object):
         if return_latent:
             Wnew = np.empty((max(self.rows() - first_row, 0), self.model.k), dtype=self.model.W.dtype)
         self._check(self.lib.trmf_session_smooth(self.handle, first_row, 0.0 if rtol is None else float(rtol), 0 if max_iter is None else int(max_iter),
-                                                 byref(sums), Wnew.ctypes.data if Wnew is not None and Wnew.size else None), 'trmf_session_smooth')
-        return (sums.as_dict(), Wnew) if return_latent else sums.as_dict()
+                                                 byref(sums), self._ptr(Wnew)), 'trmf_session_smooth')
+        return self._pack(sums.as_dict(), (return_latent, Wnew))
 
     def smooth_robust(self, first_row, c=3.0, sweeps=4, scale=None, rtol=None, max_iter=None, return_latent=False, return_weights=False):
         """``smooth`` on Huber's loss (``trmf.online.robust_smooth_rows`` is the same statement in NumPy, every sweep solved
@@ -608,28 +623,14 @@ class Session(object):
         first_row = int(first_row)
         dt = self.model.W.dtype
         nr = max(self.rows() - first_row, 0)
-        sc = None
-        if scale is not None:
-            sc = np.asarray(scale, dtype=np.float64)
-            if sc.ndim == 0:
-                sc = np.full(self.model.n, float(sc))
-            if sc.shape != (self.model.n,):
-                raise ValueError('smooth_robust: scale has shape {}, one value per series ({}) was expected'.format(sc.shape, self.model.n))
-            sc = np.ascontiguousarray(sc)
+        sc = self._series_scales('smooth_robust', scale)
         sums = TrmfRobustSmoothSums()
         Wnew = np.empty((nr, self.model.k), dtype=dt) if return_latent else None
-        weights = None
-        if return_weights:
-            if self._stored is not None:
-                weights = np.empty(int(self._stored[first_row:].sum()) if nr and first_row >= 0 else 0, dtype=dt)
-            else:
-                weights = np.empty((nr, self.model.n), dtype=dt)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
-        self._check(self.lib.trmf_session_smooth_robust(self.handle, first_row, float(c), int(sweeps), ptr(sc), 0.0 if rtol is None else float(rtol),
-                                                        0 if max_iter is None else int(max_iter), byref(sums), ptr(Wnew), ptr(weights)),
+        weights = self._row_weight_buffer(first_row, nr, dt) if return_weights else None
+        self._check(self.lib.trmf_session_smooth_robust(self.handle, first_row, float(c), int(sweeps), self._ptr(sc), 0.0 if rtol is None else float(rtol),
+                                                        0 if max_iter is None else int(max_iter), byref(sums), self._ptr(Wnew), self._ptr(weights)),
                     'trmf_session_smooth_robust')
-        out = (sums.as_dict(),) + ((Wnew,) if return_latent else ()) + ((weights,) if return_weights else ())
-        return out if len(out) > 1 else out[0]
+        return self._pack(sums.as_dict(), (return_latent, Wnew), (return_weights, weights))
 
     def _reach(self):
         return int(self.model.lag_set.max()) if len(self.model.lag_set) else 0
@@ -651,9 +652,9 @@ class Session(object):
         with ``lambdaI == 0``) raises and leaves the session as it was."""
         sums = TrmfAdaptSums()
         Hnew = np.empty((self.model.n, self.model.k), dtype=self.model.W.dtype) if return_loadings else None
-        self._check(self.lib.trmf_session_adapt_series(self.handle, byref(sums), Hnew.ctypes.data if Hnew is not None and Hnew.size else None),
+        self._check(self.lib.trmf_session_adapt_series(self.handle, byref(sums), self._ptr(Hnew)),
                     'trmf_session_adapt_series')
-        return (sums.as_dict(), Hnew) if return_loadings else sums.as_dict()
+        return self._pack(sums.as_dict(), (return_loadings, Hnew))
 
     def adapt_series_robust(self, c=3.0, sweeps=4, scale=None, return_loadings=False, return_weights=False):
         """``adapt_series`` with Huber weights on the entries it absorbs (``trmf.online.SeriesStats.absorb_robust`` is the same
@@ -670,14 +671,7 @@ class Session(object):
         shared S) raises and leaves the session as it was."""
         dt = self.model.W.dtype
         n = self.model.n
-        sc = None
-        if scale is not None:
-            sc = np.asarray(scale, dtype=np.float64)
-            if sc.ndim == 0:
-                sc = np.full(n, float(sc))
-            if sc.shape != (n,):
-                raise ValueError('adapt_series_robust: scale has shape {}, one value per series ({}) was expected'.format(sc.shape, n))
-            sc = np.ascontiguousarray(sc)
+        sc = self._series_scales('adapt_series_robust', scale)
         sums = TrmfRobustAdaptSums()
         Hnew = np.empty((n, self.model.k), dtype=dt) if return_loadings else None
         row0 = self.series_stats_info()['absorbed_rows']
@@ -686,13 +680,10 @@ class Session(object):
         if return_weights:
             cap = int(self._stored[row0:].sum()) if self._stored is not None and m else 0
             wptr, wrows, weights = np.zeros(n + 1, dtype=np.uint64), np.zeros(cap, dtype=np.uint32), np.ones(cap, dtype=dt)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
-        self._check(self.lib.trmf_session_adapt_series_robust(self.handle, float(c), int(sweeps), ptr(sc), byref(sums), ptr(Hnew), ptr(wptr), ptr(wrows),
-                                                              ptr(weights)), 'trmf_session_adapt_series_robust')
-        out = (sums.as_dict(),) + ((Hnew,) if return_loadings else ())
-        if return_weights:
-            out += (smat.csc_matrix((weights, wrows.astype(np.int64) - row0, wptr.astype(np.int64)), shape=(m, n)),)
-        return out if len(out) > 1 else out[0]
+        self._check(self.lib.trmf_session_adapt_series_robust(self.handle, float(c), int(sweeps), self._ptr(sc), byref(sums), self._ptr(Hnew), self._ptr(wptr), self._ptr(wrows),
+                                                              self._ptr(weights)), 'trmf_session_adapt_series_robust')
+        wmat = smat.csc_matrix((weights, wrows.astype(np.int64) - row0, wptr.astype(np.int64)), shape=(m, n)) if return_weights else None
+        return self._pack(sums.as_dict(), (return_loadings, Hnew), (return_weights, wmat))
 
     def series_stats_info(self):
         """``{'valid', 'stale', 'absorbed_rows', 'forget'}`` of the resident series statistics (absent ones: neither valid nor stale)."""

@@ -166,7 +166,7 @@ def doubled(raw, seed=0):
 
 
 def stacked(head, tail):
-    """The arrays a session holds after append_rows(tail) on a session created over `head` (csrc/session.hpp append_rows): the
+    """The arrays a session holds after append_rows(tail) on a session created over `head` (csrc/session_online.hpp append_rows): the
     CSR is the old rows followed by the new ones; every column of the CSC is its old entries followed by the block's entries of
     that column with their timestamps shifted."""
     T0, n = head.shape
