@@ -23,12 +23,13 @@
 //   unit_adapt_robust.hip   adapt_robust_series_kernel (4), adapt_robust_objective_kernel: trmf_session_adapt_series_robust
 //   unit_slide.hip     csc_slide_count_kernel, csc_slide_kernel, series_downdate_kernel (4): the sliding window of trmf_session_slide
 //   unit_churn.hip     csr_churn_count_kernel, csr_churn_kernel, csc_gather_kernel, dense_churn_kernel, row_gather_kernel: trmf_session_change_series
+//   unit_revise.hip    revise_count_kernel, revise_kernel, dense_revise_kernel, series_revise_kernel (4): the cell revisions of trmf_session_revise
 //
 // A unit defines TRMF_UNIT before including this file; the non-template kernels of the shared headers are compiled by the main
 // unit only (#if !defined(TRMF_UNIT) around them).
 #pragma once
 
-// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online, 10 online loadings, 11 smoother, 12 robust smoother, 13 robust online loadings, 14 sliding window, 15 series churn; the kernels of these families
+// (a unit includes only the headers of its own family: TRMF_UNIT = 1 gram, 2 hv_tile, 3 persist, 4 full, 5 held-out, 6 forecast, 7 online, 8 uncertainty, 9 robust online, 10 online loadings, 11 smoother, 12 robust smoother, 13 robust online loadings, 14 sliding window, 15 series churn, 16 cell revisions; the kernels of these families
 // have their BODIES only where TRMF_UNIT_BODIES is defined -- the main unit sees declarations, so that it neither compiles them
 // nor runs them through the optimiser as `extern template` would (available_externally bodies: 3 of its 3.5 minutes))
 #if defined(TRMF_UNIT) || defined(TRMF_SINGLE_UNIT)
@@ -77,6 +78,9 @@
 #endif
 #if !defined(TRMF_UNIT) || TRMF_UNIT == 15
 #include "churn_kernels.hpp"
+#endif
+#if !defined(TRMF_UNIT) || TRMF_UNIT == 16
+#include "revise_kernels.hpp"           // (includes adapt_kernels.hpp for the shared rank-1 update)
 #endif
 #if !defined(TRMF_UNIT)
 #include "cg_persist_args.hpp"     // the declaration only: the body is unit_persist.hip's business
@@ -217,6 +221,11 @@ namespace trmf {
 #define TRMF_UNIT_SLIDE(X)                                                                                                   \
     X void series_downdate_kernel<1>(DowndateArgs); X void series_downdate_kernel<2>(DowndateArgs);                          \
     X void series_downdate_kernel<3>(DowndateArgs); X void series_downdate_kernel<4>(DowndateArgs);
+
+// cell revisions (revise_kernels.hpp): the update of the loading statistics as NT = 1..4 (k <= 64); the compaction and scatter kernels are not templates
+#define TRMF_UNIT_REVISE(X)                                                                                                  \
+    X void series_revise_kernel<1>(SeriesReviseArgs); X void series_revise_kernel<2>(SeriesReviseArgs);                      \
+    X void series_revise_kernel<3>(SeriesReviseArgs); X void series_revise_kernel<4>(SeriesReviseArgs);
 
 #define TRMF_DEFINE_KERNEL template __global__
 

@@ -686,6 +686,219 @@ struct TrmfSessionImpl : SessionCore {
         TRMF_HIP_CHECK(hipDeviceSynchronize());
         return autotune();
     }
+    // ---- cell revisions (trmf_session_revise; revise_kernels.hpp) -------------------------------------------------------------------
+    // Sets and deletes cells INSIDE the rows and series held, in ONE new generation of storage.  Sparse storage: every stored copy
+    // of an edited cell leaves both orientations by a stable compaction (revise_count_kernel / revise_kernel, one pair for both
+    // orientations), each set then places one entry at the end of its row (the sets of a row in ascending series order) and of its
+    // column (ascending timestamp) -- so the result depends on the set of edits, not on their order in the batch.  Dense storage: the
+    // cells are overwritten in copies of both orientations (dense_revise_kernel); under a transform the raw copy is edited and the
+    // current coefficients are re-applied, as slide re-applies them.  update_stats: the loading statistics lose the removed entries'
+    // terms and gain the sets' (series_revise_kernel over the touched series: storage of BEFORE the edit, W as it is, active
+    // generation -> the other one).  Afterwards the session is the one trmf_session_create would build from the revised entries in
+    // that stored order and the current W, H, lag weights and transform.  W, H, the lag weights, the mark, the held-out set and the
+    // per-series score and noise tables are not touched.  Failure-atomic like slide: everything is built in locals and committed at
+    // the end.  revise_refusal() is the validation, run by the entry point on the calling thread before any rank's worker starts.
+    struct ReviseResult {
+        uint64_t edits = 0, inserted = 0, replaced = 0, deleted = 0, missed = 0, copies_removed = 0, entries_before = 0, entries = 0;
+        int first_row = -1, last_row = -1, stats_carried = 0;
+    };
+    // The batch bucketed by its major index: ptr (nmajor + 1), the minor indices ascending within a major index, values and flags.
+    struct ReviseBucket { std::vector<uint32_t> ptr, idx; std::vector<real> val; std::vector<uint8_t> del; };
+    static ReviseBucket revise_bucket(uint64_t count, const uint32_t *major, const uint32_t *minor, const real *vals, const uint8_t *del, int nmajor) {
+        ReviseBucket b;
+        b.ptr.assign((size_t)nmajor + 1, 0u); b.idx.resize(count); b.val.resize(count); b.del.resize(count);
+        for (uint64_t e = 0; e < count; e++) b.ptr[(size_t)major[e] + 1]++;
+        for (int i = 0; i < nmajor; i++) b.ptr[(size_t)i + 1] += b.ptr[i];
+        // a counting pass places every edit in its major index's range; each range is then sorted by the minor index
+        std::vector<uint32_t> next(b.ptr.begin(), b.ptr.end() - 1), slot(count);
+        for (uint64_t e = 0; e < count; e++) slot[next[major[e]]++] = (uint32_t)e;
+        for (int i = 0; i < nmajor; i++)
+            if (b.ptr[(size_t)i + 1] - b.ptr[i] > 1)
+                std::sort(slot.begin() + b.ptr[i], slot.begin() + b.ptr[(size_t)i + 1],
+                          [&](uint32_t x, uint32_t y) { return minor[x] != minor[y] ? minor[x] < minor[y] : x < y; });
+        for (uint64_t q = 0; q < count; q++) {
+            const uint32_t e = slot[q];
+            b.idx[q] = minor[e]; b.del[q] = (del && del[e]) ? 1 : 0; b.val[q] = (b.del[q] || !vals) ? real(0) : vals[e];
+        }
+        return b;
+    }
+    bool revise_carries_stats() const { return ad_exists && ad_valid && ad_rows == T && !full; }
+    std::string revise_refusal(uint64_t count, const uint32_t *rows, const uint32_t *cols, const void *vals, const uint8_t *del, int update_stats) const {
+        if (update_stats != 0 && update_stats != 1) return "revise: update_stats must be 0 or 1";
+        if (count == 0) return "";
+        // (the size is judged before the arrays are read: every edit may be an insert)
+        if (count >= (1ull << 32) || (!dense && nnz + count >= (1ull << 32))) return "revise: problem would exceed 32-bit device indices";
+        if (!rows || !cols) return "revise: rows and cols are needed";
+        if (dense && del)
+            for (uint64_t e = 0; e < count; e++)
+                if (del[e]) return "revise: a delete on dense storage (every cell of a dense Y is observed; set a value instead)";
+        bool any_set = false;
+        for (uint64_t e = 0; e < count; e++) {
+            if (rows[e] >= (uint32_t)T) return "revise: edit " + std::to_string(e) + " names row " + std::to_string(rows[e]) + ", the session holds " + std::to_string(T);
+            if (cols[e] >= (uint32_t)n) return "revise: edit " + std::to_string(e) + " names series " + std::to_string(cols[e]) + ", the session holds " + std::to_string(n);
+            any_set = any_set || !del || !del[e];
+        }
+        if (any_set && !vals) return "revise: vals is needed (the batch holds sets)";
+        {   // a cell named twice: neighbours in the batch bucketed by row
+            const ReviseBucket b = revise_bucket(count, rows, cols, nullptr, nullptr, T);
+            for (int i = 0; i < T; i++)
+                for (uint32_t q = b.ptr[i] + 1; q < b.ptr[(size_t)i + 1]; q++)
+                    if (b.idx[q] == b.idx[q - 1])
+                        return "revise: cell (" + std::to_string(i) + ", " + std::to_string(b.idx[q]) + ") is named twice in one batch";
+        }
+        if (update_stats) {
+            if (full) return "revise: update_stats needs per-series statistics (sparse storage with missing != 0); the full-observation forms share one S";
+            if (!ad_exists || !ad_valid) return "revise: update_stats without valid series statistics (trmf_session_series_stats_init)";
+        }
+        return "";
+    }
+    // d_src (count values on the device) -> host, through the library's pinned staging when it is to be had
+    int revise_fetch(const uint32_t *d_src, std::vector<uint32_t> &dst, size_t count) {
+        dst.assign(count, 0u);
+        if (!count) return 0;
+        const size_t bytes = count * sizeof(uint32_t);
+        std::unique_lock<std::mutex> lease;
+        unsigned char *pin = HostStager::current().staging(bytes, lease);
+        TRMF_HIP_CHECK(hipMemcpyAsync(pin ? (void *)pin : (void *)dst.data(), d_src, bytes, hipMemcpyDeviceToHost, stream));
+        TRMF_HIP_CHECK(hipStreamSynchronize(stream));
+        if (pin) std::memcpy(dst.data(), pin, bytes);
+        return 0;
+    }
+    // One orientation's bucket on the device.
+    struct ReviseBucketDev {
+        DevBuf<uint32_t> ptr, idx; DevBuf<real> val; DevBuf<uint8_t> del;
+        int upload(const ReviseBucket &b) { return ptr.upload(b.ptr.data(), b.ptr.size()) || idx.upload(b.idx.data(), b.idx.size()) || val.upload(b.val.data(), b.val.size()) || del.upload(b.del.data(), b.del.size()) ? kFail : 0; }
+    };
+    int revise(uint64_t count, const uint32_t *rows, const uint32_t *cols, const real *vals, const uint8_t *del, bool update_stats, ReviseResult *res) {
+        ReviseResult out{};
+        out.entries_before = out.entries = nnz;
+        if (count == 0) { if (res) *res = out; return 0; }
+        if (sync()) return kFail;
+        FillStreamScope fill(stream);
+        out.edits = count;
+        uint64_t nsets = 0;
+        uint32_t rmin = rows[0], rmax = rows[0];
+        for (uint64_t e = 0; e < count; e++) { nsets += (!del || !del[e]) ? 1 : 0; rmin = std::min(rmin, rows[e]); rmax = std::max(rmax, rows[e]); }
+        out.first_row = (int)rmin; out.last_row = (int)rmax;
+        {   // the new generation of buffers in ONE slab (the pool returns the previous generation's slab once it is wholly free)
+            const uint64_t nzsave = nnz;
+            if (!dense) nnz += nsets;
+            const size_t fp = footprint_estimate();
+            nnz = nzsave;
+            DevicePool::current().reserve(fp);
+        }
+        const bool carry = update_stats && revise_carries_stats();
+        bool changed = true;                          // a column has changed (a batch of deletes that all miss changes nothing)
+        std::vector<uint64_t> new_row_ptr, new_col_ptr;
+        uint64_t new_nnz = nnz;
+        double new_ysq = ysq_acc;
+        DevBuf<uint32_t> ptr2, idx2, cptr2, cidx2; DevBuf<real> val2, cval2, tn2, nt2, raw2;
+        SyncStreamOnExit drain(stream);
+        if (!dense) {
+            const ReviseBucket br = revise_bucket(count, rows, cols, vals, del, T), bc = revise_bucket(count, cols, rows, vals, del, n);
+            ReviseBucketDev dr, dc;
+            DevBuf<uint32_t> d_kept_r, d_kept_c, d_hits;
+            SyncStreamOnExit drain_batch(stream);
+            if (dr.upload(br) || dc.upload(bc) || d_kept_r.alloc((size_t)T, false) || d_kept_c.alloc((size_t)n, false) || d_hits.alloc(count)) return kFail;
+            ReviseArgs ra{Yr_ptr.p, Yr_idx.p, Yr_val.p, dr.ptr.p, dr.idx.p, dr.val.p, dr.del.p, nullptr, nullptr, nullptr, d_kept_r.p, d_hits.p, T};
+            ReviseArgs ca{Yc_ptr.p, Yc_idx.p, Yc_val.p, dc.ptr.p, dc.idx.p, dc.val.p, dc.del.p, nullptr, nullptr, nullptr, d_kept_c.p, nullptr, n};
+            hipLaunchKernelGGL(revise_count_kernel, dim3((T + 3) / 4), dim3(256), 0, stream, ra);
+            hipLaunchKernelGGL(revise_count_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, ca);
+            TRMF_HIP_CHECK(hipGetLastError());
+            std::vector<uint32_t> kept_r, kept_c, hits;
+            if (revise_fetch(d_kept_r.p, kept_r, (size_t)T) || revise_fetch(d_kept_c.p, kept_c, (size_t)n) || revise_fetch(d_hits.p, hits, count)) return kFail;
+            // the hits of every edit, in the row bucket's order: what the batch did
+            for (uint64_t q = 0; q < count; q++) {
+                out.copies_removed += hits[q];
+                if (br.del[q]) { if (hits[q]) out.deleted++; else out.missed++; }
+                else if (hits[q]) out.replaced++; else out.inserted++;
+            }
+            changed = nsets > 0 || out.copies_removed > 0;
+            new_row_ptr.assign((size_t)T + 1, 0); new_col_ptr.assign((size_t)n + 1, 0);
+            {
+                std::vector<uint32_t> sets_r((size_t)T, 0u), sets_c((size_t)n, 0u);
+                for (uint64_t e = 0; e < count; e++) if (!del || !del[e]) { sets_r[rows[e]]++; sets_c[cols[e]]++; }
+                for (int i = 0; i < T; i++) new_row_ptr[(size_t)i + 1] = new_row_ptr[i] + kept_r[i] + sets_r[i];
+                for (int j = 0; j < n; j++) new_col_ptr[(size_t)j + 1] = new_col_ptr[j] + kept_c[j] + sets_c[j];
+            }
+            new_nnz = new_row_ptr[T];
+            if (new_col_ptr[n] != new_nnz || nnz - out.copies_removed + nsets != new_nnz) { set_error("revise: the two orientations of Y do not hold the same entries"); return kFail; }
+            if (new_nnz >= (1ull << 32)) { set_error("revise: problem would exceed 32-bit device indices"); return kFail; }
+            std::vector<uint32_t> np32((size_t)n + 1);
+            for (int j = 0; j <= n; j++) np32[j] = (uint32_t)new_col_ptr[j];
+            if (upload_ptr32(ptr2, (const size_t *)new_row_ptr.data(), (size_t)T + 1) || idx2.alloc(new_nnz, false) || val2.alloc(new_nnz, false) ||
+                cptr2.upload(np32.data(), np32.size()) || cidx2.alloc(new_nnz, false) || cval2.alloc(new_nnz, false)) return kFail;
+            ra.nptr = ptr2.p; ra.nidx = idx2.p; ra.nval = val2.p;
+            ca.nptr = cptr2.p; ca.nidx = cidx2.p; ca.nval = cval2.p;
+            hipLaunchKernelGGL(revise_kernel, dim3((T + 3) / 4), dim3(256), 0, stream, ra);
+            hipLaunchKernelGGL(revise_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, ca);
+            TRMF_HIP_CHECK(hipGetLastError());
+            if (carry && changed) {   // the tables follow: untouched series copied, touched ones walked (old storage, W as it is)
+                const size_t PK = adapt_packed(k);
+                std::vector<uint32_t> touched;
+                for (int j = 0; j < n; j++) if (bc.ptr[(size_t)j + 1] > bc.ptr[j]) touched.push_back((uint32_t)j);
+                const std::vector<real> hom = forget_weights(ad_gamma, 0, T, T).w;
+                DevBuf<uint32_t> d_list; DevBuf<real> om;
+                SyncStreamOnExit drain_stats(stream);
+                if (d_list.upload(touched.data(), touched.size()) || (!hom.empty() && om.upload(hom.data(), hom.size()))) return kFail;
+                TRMF_HIP_CHECK(hipMemcpyAsync(ad_S[1 - ad_cur].p, ad_S[ad_cur].p, (size_t)n * PK * sizeof(real), hipMemcpyDeviceToDevice, stream));
+                TRMF_HIP_CHECK(hipMemcpyAsync(ad_r[1 - ad_cur].p, ad_r[ad_cur].p, (size_t)n * k * sizeof(real), hipMemcpyDeviceToDevice, stream));
+                SeriesReviseArgs sa{Yc_ptr.p, Yc_idx.p, Yc_val.p, d_list.p, dc.ptr.p, dc.idx.p, dc.val.p, dc.del.p, W.p, hom.empty() ? nullptr : om.p,
+                                    ad_S[ad_cur].p, ad_r[ad_cur].p, ad_S[1 - ad_cur].p, ad_r[1 - ad_cur].p, (int)touched.size(), k, KP};
+                if (!with_nt(NT, [&](auto N) { hipLaunchKernelGGL(series_revise_kernel<decltype(N)::value>, dim3((unsigned)touched.size()), dim3(64), 0, stream, sa); }))
+                    return unsupported_rank();
+                TRMF_HIP_CHECK(hipGetLastError());
+            }
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // (the buckets are locals)
+            if (device_sum_squares(val2.p, new_nnz, &new_ysq)) return kFail;
+        } else {
+            const size_t N = (size_t)T * n;
+            DevBuf<uint32_t> d_rows, d_cols; DevBuf<real> d_vals;
+            SyncStreamOnExit drain_batch(stream);
+            if (d_rows.upload(rows, count) || d_cols.upload(cols, count) || d_vals.upload(vals, count)) return kFail;
+            DenseReviseArgs da{d_rows.p, d_cols.p, d_vals.p, nullptr, nullptr, (uint32_t)count, T, n};
+            if (has_transform) {                        // the values are RAW data: edit the raw copy, re-derive below
+                if (raw2.alloc(N, false)) return kFail;
+                TRMF_HIP_CHECK(hipMemcpyAsync(raw2.p, Yraw.p, N * sizeof(real), hipMemcpyDeviceToDevice, stream));
+                da.tn = raw2.p;
+            } else {
+                if (tn2.alloc(N, false) || nt2.alloc(N, false)) return kFail;
+                TRMF_HIP_CHECK(hipMemcpyAsync(tn2.p, Yd_tn.p, N * sizeof(real), hipMemcpyDeviceToDevice, stream));
+                TRMF_HIP_CHECK(hipMemcpyAsync(nt2.p, Yd_nt.p, N * sizeof(real), hipMemcpyDeviceToDevice, stream));
+                da.tn = tn2.p; da.nt = nt2.p;
+            }
+            hipLaunchKernelGGL(dense_revise_kernel, dim3((unsigned)std::min<uint64_t>(4096, (count + 255) / 256)), dim3(256), 0, stream, da);
+            TRMF_HIP_CHECK(hipGetLastError());
+            TRMF_HIP_CHECK(hipStreamSynchronize(stream));      // (the batch's device copies are locals)
+            if (!has_transform && device_sum_squares(tn2.p, N, &new_ysq)) return kFail;    // over the new matrix, like a fresh session's
+            out.replaced = count; out.copies_removed = count;
+        }
+        // ---- commit ----
+        if (!dense) {
+            Yr_ptr.swap(ptr2); Yr_idx.swap(idx2); Yr_val.swap(val2);
+            Yc_ptr.swap(cptr2); Yc_idx.swap(cidx2); Yc_val.swap(cval2);
+            host_row_ptr.swap(new_row_ptr); host_col_ptr.swap(new_col_ptr);
+        } else if (has_transform) Yraw.swap(raw2);
+        else { Yd_tn.swap(tn2); Yd_nt.swap(nt2); }
+        if (ad_exists && changed) {
+            if (carry) {
+                ad_cur = 1 - ad_cur;
+                for (int j = 0; j < n; j++) ad_cnt[j] = (uint32_t)(host_col_ptr[(size_t)j + 1] - host_col_ptr[j]);
+            } else adapt_stale();                     // a column the tables absorbed has changed
+        }
+        out.stats_carried = carry ? 1 : 0;
+        out.entries = new_nnz;
+        if (res) *res = out;
+        nnz = new_nnz; ysq_acc = new_ysq;
+        if (dense && has_transform && apply_series_transform()) return kFail;     // current coefficients over the new raw matrix
+        set_trYTY();
+        iter = 0;
+        if (gramx_mode != kGramxReplicate && comm->world > 1 && !test_env("TRMF_GRAMX")) { gramx_mode = kGramxMeasure; gramx_calls = 0; }
+        if (fs_mode != kShardOff && comm->world > 1 && !test_env("TRMF_FSHARD")) { fs_mode = kShardMeasure; fs_calls = 0; }
+        if (alloc_time_scratch()) return kFail;
+        TRMF_HIP_CHECK(hipDeviceSynchronize());
+        return autotune();
+    }
     // ---- online updates (trmf_session_assimilate; online_kernels.hpp) ---------------------------------------------------------
     // Rows [first_row, T) of W re-solved in ascending order with H and Theta fixed (the caller has validated first_row, the lag set
     // and the rank).  Stage A rebuilds the Gram cache rows and right-hand sides of the range with the X phase's own builders -- every

@@ -503,6 +503,26 @@ int32_t trmf_session_change_series(TrmfSession *s, const uint8_t *keep, const Py
     }
     return 0;
 }
+// Cell revisions: validated here like slide and change_series.
+int32_t trmf_session_revise(TrmfSession *s, uint64_t count, const uint32_t *rows, const uint32_t *cols, const void *vals, const uint8_t *del,
+                            int32_t update_stats, TrmfReviseSums *out) {
+    if (!s) { set_error("null session"); return kFail; }
+    const std::string why = HND(s)->first()->revise_refusal(count, rows, cols, vals, del, update_stats);
+    if (!why.empty()) { set_error(why); return kFail; }
+    DeviceGuard guard;
+    if (!guard.ok) return kFail;
+    const auto all = HND(s)->per_rank<TrmfSessionImpl::ReviseResult>([&](TrmfSessionImpl *t, int, TrmfSessionImpl::ReviseResult *r) {
+        return t->revise(count, rows, cols, (const real *)vals, del, update_stats != 0, r);
+    });
+    if (all.empty()) return kFail;
+    if (out) {
+        const auto &r = all[0];
+        out->edits = r.edits; out->inserted = r.inserted; out->replaced = r.replaced; out->deleted = r.deleted; out->missed = r.missed;
+        out->copies_removed = r.copies_removed; out->entries_before = r.entries_before; out->entries = r.entries;
+        out->first_row = r.first_row; out->last_row = r.last_row; out->stats_carried = r.stats_carried;
+    }
+    return 0;
+}
 int32_t trmf_session_row_entries(TrmfSession *s, uint64_t *per_row) {
     if (!s || !per_row) { set_error("null argument"); return kFail; }
     const TrmfSessionImpl *f = HND(s)->first();

@@ -323,6 +323,46 @@ class Model(object):
         Hn = series_ridge(self.W, Ynew, lambdaI, forget, missing)
         return Model.from_arrays(self.W.copy(), np.ascontiguousarray(np.vstack([self.H, Hn])), self.lag_val.copy(), self.lag_set.copy(), transform=tr)
 
+    # ---- cell revisions ----------------------------------------------------------------------------
+    def revise(self, Y, rows, cols, vals=None, delete=None, update_stats=False):
+        """The host form of ``Session.revise``: ``(model, Y_revised)`` for the training matrix ``Y`` (raw values) with the cells
+        ``(rows[i], cols[i])`` set to ``vals[i]`` or, where ``delete[i]`` is set, removed.  A sparse ``Y`` comes back as a
+        ``scipy.sparse.csr_matrix`` holding ``trmf.revise_entries`` of its entries in CSR order (every stored copy of an edited
+        cell removed, the sets at the end of their rows); an array comes back as a copy with the cells overwritten (deletes are
+        refused, as on the device).  The factors are carried over.  ``update_stats``: attached series statistics follow by
+        ``SeriesStats.revise`` (values in the trained scale); without it they are not carried, as the device leaves them stale."""
+        from .online import revise_entries, _revise_edits
+        import copy
+        if Y.shape != (self.m, self.n):
+            raise ValueError('revise: Y is {}, the model {} x {}'.format(Y.shape, self.m, self.n))
+        er, ec, ev, dl = _revise_edits((rows, cols, vals, delete), 'revise')
+        if er.size and (er.max() >= self.m or ec.max() >= self.n):
+            raise ValueError('revise: a cell lies outside {} x {}'.format(self.m, self.n))
+        out = Model.from_arrays(self.W.copy(), self.H.copy(), self.lag_val.copy(), self.lag_set.copy(), transform=self.transform)
+        stats = getattr(self, 'series_stats', None)
+        if smat.issparse(Y):
+            Yr = Y.tocsr()
+            r0 = np.repeat(np.arange(self.m, dtype=np.int64), np.diff(Yr.indptr))
+            r, c, v = revise_entries(r0, Yr.indices.astype(np.int64), Yr.data, (er, ec, ev, dl), major='row')
+            ptr = np.zeros(self.m + 1, dtype=np.int64)
+            np.cumsum(np.bincount(r, minlength=self.m), out=ptr[1:])
+            Y2 = smat.csr_matrix((v, c, ptr), shape=Y.shape)
+            trained, tv = Y, ev
+        else:
+            if dl.any():
+                raise ValueError('revise: a delete on a dense Y (every cell is observed; set a value instead)')
+            Y2 = np.array(Y, copy=True)
+            Y2[er, ec] = ev.astype(Y2.dtype)
+            trained, tv = Y, ev
+            if self.transform is not None:
+                trained = self.transform.preprocess(np.asarray(Y)).astype(self.W.dtype)
+                tv = self.transform.preprocess(np.asarray(Y2)).astype(self.W.dtype)[er, ec]
+        if update_stats:
+            if stats is None:
+                raise ValueError('revise: update_stats needs series statistics (Model.init_series_stats)')
+            out.series_stats = copy.deepcopy(stats).revise(self.W, trained, (er, ec, tv, dl))
+        return out, Y2
+
     # ---- construction ------------------------------------------------------------------------------
     @staticmethod
     def syn_gen(m, n, k, lag_set, seed=None, noise=0.01, dtype=np.float32):

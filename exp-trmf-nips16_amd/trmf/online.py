@@ -464,6 +464,65 @@ def churn_entries(rows, cols, vals, keep, n, block=None, major='row'):
     return r[order], c[order], v[order]
 
 
+# ---- cell revisions (trmf_session_revise) -----------------------------------------------------------------------------------------
+def _revise_edits(edits, what):
+    """``edits`` as ``(rows, cols, vals, delete)``: int64 cells, values (zeros where none were given), a boolean mask."""
+    if len(edits) not in (3, 4):
+        raise ValueError('{}: edits must be (rows, cols, vals) or (rows, cols, vals, delete)'.format(what))
+    er, ec = np.asarray(edits[0]).astype(np.int64), np.asarray(edits[1]).astype(np.int64)
+    dl = np.zeros(er.shape, dtype=bool) if len(edits) == 3 or edits[3] is None else np.asarray(edits[3]).astype(bool)
+    ev = np.zeros(er.shape) if edits[2] is None else np.asarray(edits[2])
+    if not (er.shape == ec.shape == ev.shape == dl.shape and er.ndim == 1):
+        raise ValueError('{}: the edits must be one-dimensional arrays of one length'.format(what))
+    if edits[2] is None and not dl.all():
+        raise ValueError('{}: vals is needed (the batch holds sets)'.format(what))
+    if er.size and (er.min() < 0 or ec.min() < 0):
+        raise ValueError('{}: an edit names a negative index'.format(what))
+    if np.unique(np.stack([er, ec]), axis=1).shape[1] != er.size:
+        raise ValueError('{}: a cell is named twice in one batch'.format(what))
+    return er, ec, ev, dl
+
+
+def revise_entries(rows, cols, vals, edits, major='row', return_counts=False):
+    """What a stored list of entries becomes when cells are set or deleted: the stored-order rule of ``trmf_session_revise``.
+    ``edits = (rows, cols, vals)`` or ``(rows, cols, vals, delete)`` names distinct cells; ``delete`` flags the ones that leave
+    (``None``: every edit is a set; ``vals`` may be ``None`` when all are deletes).  EVERY stored copy of an edited cell is
+    removed -- a stable filter: the other entries keep their stored order, the lists need not be sorted and a cell may be stored
+    twice -- and each set then places one entry behind the survivors of its ``major`` index: ``major='row'`` (the CSR arrays: the
+    sets of a row follow it in ascending column order) or ``major='col'`` (the CSC arrays: the sets of a column follow it in
+    ascending row order).  The result therefore depends on the set of edits, not on their order.  The lists are expected in the
+    stored order of that orientation (grouped by the major index).  Returns ``(rows, cols, vals)`` as new arrays; with
+    ``return_counts`` also ``{'inserted', 'replaced', 'deleted', 'missed', 'copies_removed'}``: a set of a stored cell replaces,
+    of an unstored one inserts; a delete of an unstored cell is a no-op counted in ``missed``; ``copies_removed`` counts the
+    stored entries that left (a cell stored twice counts twice)."""
+    rows, cols, vals = np.asarray(rows), np.asarray(cols), np.asarray(vals)
+    if not (rows.shape == cols.shape == vals.shape and rows.ndim == 1):
+        raise ValueError('revise_entries: rows, cols and vals must be one-dimensional arrays of one length')
+    if major not in ('row', 'col'):
+        raise ValueError("revise_entries: major must be 'row' or 'col', not {!r}".format(major))
+    er, ec, ev, dl = _revise_edits(edits, 'revise_entries')
+    span = int(max(cols.max() if cols.size else 0, ec.max() if ec.size else 0)) + 1
+    key, ekey = rows.astype(np.int64) * span + cols.astype(np.int64), er * span + ec
+    order = np.argsort(ekey, kind='stable')
+    pos = np.searchsorted(ekey[order], key)
+    hit = (pos < ekey.size) & (ekey[order][np.minimum(pos, max(ekey.size - 1, 0))] == key) if ekey.size else np.zeros(key.shape, dtype=bool)
+    stay = ~hit
+    sets = np.flatnonzero(~dl)
+    sets = sets[np.lexsort((ec[sets], er[sets]) if major == 'row' else (er[sets], ec[sets]))]
+    r = np.concatenate([rows[stay], er[sets].astype(rows.dtype)])
+    c = np.concatenate([cols[stay], ec[sets].astype(cols.dtype)])
+    v = np.concatenate([vals[stay], ev[sets].astype(vals.dtype)])
+    merged = np.argsort(r if major == 'row' else c, kind='stable')
+    out = (r[merged], c[merged], v[merged])
+    if not return_counts:
+        return out
+    copies = np.bincount(pos[hit], minlength=ekey.size)[np.argsort(order, kind='stable')] if ekey.size else np.zeros(0, dtype=np.int64)
+    stored = copies > 0
+    counts = {'inserted': int(np.count_nonzero(~dl & ~stored)), 'replaced': int(np.count_nonzero(~dl & stored)),
+              'deleted': int(np.count_nonzero(dl & stored)), 'missed': int(np.count_nonzero(dl & ~stored)), 'copies_removed': int(copies.sum())}
+    return out + (counts,)
+
+
 # ---- online loading updates: the rows of H refitted from new rows (trmf_session_series_stats_init / _adapt_series) ---------------
 def _series_entries(Y, missing):
     """Per series the (timestamps, values) of its observations in stored order.  Sparse ``Y``: the stored entries of the column
@@ -616,6 +675,48 @@ class SeriesStats(object):
                         self.S[j] += np.outer(aw, W[t])
                     self.r[j] += aw * y[e]
         self.rows -= count
+        return self
+
+    def revise(self, W, Y, edits):
+        """The cell-revision form (``trmf_session_revise`` with ``update_stats``): cells of the absorbed rows are set or deleted.
+        ``W`` (``self.rows`` x k, as it is now) and ``Y`` (the observations of BEFORE the edit, every row absorbed) as for
+        ``retire``; ``edits = (rows, cols, vals)`` or ``(rows, cols, vals, delete)`` as for ``trmf.revise_entries``.  Per touched
+        series every stored entry of an edited cell is subtracted in stored order, then the sets are added in ascending row order ::
+
+            S_j <- S_j -/+ om_t w_t w_t^T,   r_j <- r_j -/+ om_t y w_t,   om_t = forget^(rows - 1 - t)
+
+        one rank-1 update per entry in the dtype of ``W`` (the absorb step; the sign of the weight flipped for the removed
+        entries): the tables then describe the revised matrix.  Per-series tables only (``missing``)."""
+        W = np.asarray(W)
+        if not self.missing:
+            raise ValueError('SeriesStats.revise: per-series statistics only (missing); the full-observation forms share one S')
+        if W.shape != (self.rows, self.k) or W.dtype != self.dtype:
+            raise ValueError('SeriesStats.revise: W is {} {}, {} x {} of {} was expected'.format(W.shape, W.dtype, self.rows, self.k, self.dtype))
+        if Y.shape != (self.rows, self.n):
+            raise ValueError('SeriesStats.revise: Y is {}, {} x {} (every row absorbed) was expected'.format(Y.shape, self.rows, self.n))
+        er, ec, ev, dl = _revise_edits(edits, 'SeriesStats.revise')
+        if er.size and (er.max() >= self.rows or ec.max() >= self.n):
+            raise ValueError('SeriesStats.revise: an edit lies outside {} x {}'.format(self.rows, self.n))
+        dt = self.dtype
+        om = (self.forget ** (self.rows - 1 - np.arange(self.rows, dtype=np.float64))).astype(dt)
+        columns = _series_entries(Y, True)
+        for j in np.unique(ec):
+            mine = np.flatnonzero(ec == j)
+            mine = mine[np.argsort(er[mine], kind='stable')]
+            rows, y = columns[j]
+            y = np.asarray(y, dtype=dt)
+            gone = set(int(t) for t in er[mine])
+            for e, t in enumerate(rows):
+                if int(t) in gone:
+                    aw = -om[t] * W[t]
+                    self.S[j] += np.outer(aw, W[t])
+                    self.r[j] += aw * y[e]
+            for e in mine:
+                if not dl[e]:
+                    t = er[e]
+                    aw = om[t] * W[t]
+                    self.S[j] += np.outer(aw, W[t])
+                    self.r[j] += aw * dt.type(ev[e])
         return self
 
     def solve(self, lambdaI):

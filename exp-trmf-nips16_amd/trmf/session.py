@@ -113,6 +113,17 @@ class TrmfChurnSums(ctypes.Structure):
         return out
 
 
+class TrmfReviseSums(ctypes.Structure):
+    _fields_ = [('edits', c_uint64), ('inserted', c_uint64), ('replaced', c_uint64), ('deleted', c_uint64), ('missed', c_uint64),
+                ('copies_removed', c_uint64), ('entries_before', c_uint64), ('entries', c_uint64), ('first_row', c_int32), ('last_row', c_int32),
+                ('stats_carried', c_int32)]
+
+    def as_dict(self):
+        out = {name: int(getattr(self, name)) for name, _ in self._fields_[:10]}
+        out.update(stats_carried=bool(self.stats_carried))
+        return out
+
+
 class TrmfRobustAdaptSums(ctypes.Structure):
     """Sums of a robust online loading update (include/trmf_abi.h): those of ``TrmfAdaptSums``, the number of down-weighted
     entries and the sum of the weights of the last sweep, the Huber objective ``sum_j J_j`` before / after."""
@@ -236,6 +247,9 @@ def bind(lib):
         lib.trmf_session_change_series.argtypes = [c_void_p, c_void_p, P, c_int32, c_void_p, c_void_p, c_void_p, POINTER(TrmfChurnSums)]
         lib.trmf_session_change_series.restype = c_int32
         lib.trmf_session_row_entries.argtypes = [c_void_p, c_void_p]; lib.trmf_session_row_entries.restype = c_int32
+    if hasattr(lib, 'trmf_session_revise'):           # (absent from libraries built before the cell revisions)
+        lib.trmf_session_revise.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, POINTER(TrmfReviseSums)]
+        lib.trmf_session_revise.restype = c_int32
     if hasattr(lib, 'trmf_session_fit_noise'):        # (absent from libraries built before the forecast uncertainty)
         lib.trmf_session_fit_noise.argtypes = [c_void_p, POINTER(TrmfNoiseStats)]; lib.trmf_session_fit_noise.restype = c_int32
         lib.trmf_session_noise.argtypes = [c_void_p, c_void_p, c_void_p]; lib.trmf_session_noise.restype = c_int32
@@ -356,6 +370,7 @@ class Session(object):
         if not self.handle:
             raise RuntimeError('trmf_session_create failed: ' + self.lib.trmf_last_error().decode())
         self._stored = _stored_per_row(self.pyY)
+        self._per_series_stats = self._stored is not None and bool(missing)      # (the full-observation forms share one S)
         if not log_norms:       # the reference computes the ||.||^2 log lines only under verbose
             self.lib.trmf_session_log_norms(self.handle, 0)
         if timing != 1:         # phase events (ms_* of stats()) on every `timing`-th iteration only / never (0): they cost ~25 us apiece
@@ -516,6 +531,59 @@ class Session(object):
     def retire_series(self, which):
         """``change_series`` that only retires: ``which`` is a list of series indices or a boolean mask of the series that leave."""
         return self.change_series(check_keep(which, self.model.n, retire=True))
+
+    def revise(self, rows, cols, vals=None, delete=None, update_stats=False):
+        """Cell revisions on the device: set the cells ``(rows[i], cols[i])`` of the resident problem to ``vals[i]`` -- a reading
+        that arrives late, a provisional value that is corrected -- or, where ``delete[i]`` is set, retract them.  The cells of one
+        batch are distinct and lie inside the rows and series the session holds; ``vals`` are raw values (a series transform is
+        applied on the device) and may be ``None`` when every edit is a delete.  Sparse storage: every stored copy of an edited cell
+        leaves both orientations, the other entries keep their stored order, and each set places one entry at the end of its row
+        and of its column (``trmf.revise_entries`` is the same statement in NumPy), so the result does not depend on the order
+        of the batch.  Dense storage: sets overwrite the cell; deletes are refused.  Afterwards the session is the one a fresh
+        ``Session`` would be on the revised entries with the current W, H, lag weights and transform.  W, H and the lag weights are
+        not touched -- ``smooth``, ``assimilate``, ``adapt_series`` or ``run`` is the caller's next call -- the mark stays valid, the
+        noise and score tables stay, and the held-out set is untouched: a revised cell that is also held out stays held out.
+        ``update_stats`` (sparse storage with ``missing``, valid series statistics): the removed entries' terms leave ``S_j`` and
+        ``r_j`` and the sets' terms join them (``trmf.SeriesStats.revise``), so the next ``adapt_series`` refits on the revised
+        data; without it -- or when the statistics have not absorbed every row -- statistics whose columns changed become stale.
+        Returns ``{'edits', 'inserted', 'replaced', 'deleted', 'missed', 'copies_removed', 'entries_before', 'entries', 'first_row',
+        'last_row', 'stats_carried'}``.  A refused call (a cell outside the session, a cell named twice, a delete on dense storage,
+        ``update_stats`` without valid per-series statistics, sizes beyond the 32-bit device indices) raises and leaves the session
+        as it was."""
+        if not hasattr(self.lib, 'trmf_session_revise'):
+            raise RuntimeError('revise: the loaded library was built before the cell revisions')
+        dt = self.model.W.dtype
+        r, c = np.asarray(rows), np.asarray(cols)
+        if r.ndim != 1 or r.shape != c.shape or (r.size and not (np.issubdtype(r.dtype, np.integer) and np.issubdtype(c.dtype, np.integer))):
+            raise ValueError('revise: rows and cols must be one-dimensional integer arrays of one length')
+        if r.size and (r.min() < 0 or c.min() < 0 or r.max() >= 2 ** 32 or c.max() >= 2 ** 32):
+            raise ValueError('revise: a cell index is negative or does not fit 32 bits')
+        r32, c32 = np.ascontiguousarray(r.astype(np.uint32)), np.ascontiguousarray(c.astype(np.uint32))
+        flags = None
+        if delete is not None:
+            d = np.asarray(delete)
+            if d.shape != r.shape:
+                raise ValueError('revise: delete must hold one flag per cell')
+            flags = np.ascontiguousarray(d.astype(bool).astype(np.uint8))
+        v = None
+        if vals is not None:
+            v = np.ascontiguousarray(np.asarray(vals, dtype=dt))
+            if v.shape != r.shape:
+                raise ValueError('revise: vals must hold one value per cell')
+        elif flags is None or not flags.all():
+            raise ValueError('revise: vals is needed (the batch holds sets)')
+        sums = TrmfReviseSums()
+        self._check(self.lib.trmf_session_revise(self.handle, int(r32.size), self._ptr(r32), self._ptr(c32), self._ptr(v), self._ptr(flags),
+                                                 1 if update_stats else 0, byref(sums)), 'trmf_session_revise')
+        if self._stored is not None and r32.size:      # sparse storage: the entries of a row are known to the library
+            per_row = np.zeros(self.rows(), dtype=np.uint64)
+            self._check(self.lib.trmf_session_row_entries(self.handle, per_row.ctypes.data), 'trmf_session_row_entries')
+            self._stored = per_row.astype(np.int64)
+        return sums.as_dict()
+
+    def retract(self, rows, cols, update_stats=False):
+        """``revise`` that only deletes: the cells ``(rows[i], cols[i])`` leave the resident problem (sparse storage)."""
+        return self.revise(rows, cols, None, np.ones(np.asarray(rows).shape, dtype=bool), update_stats)
 
     def pool_live_bytes(self):
         """Bytes of device memory that live buffers of this process hold in the library's pool right now."""
@@ -692,7 +760,7 @@ class Session(object):
         return {'valid': v.value == 1, 'stale': v.value == -1, 'absorbed_rows': int(rows.value), 'forget': float(g.value)}
 
     def update(self, Ynew, iters=0, robust_c=None, robust_sweeps=4, scale=None, adapt=False, forget=1.0, smooth_back=0, smooth_robust=False,
-               adapt_robust=False, window=None, downdate_stats=False):
+               adapt_robust=False, window=None, downdate_stats=False, revisions=None):
         """Absorb the new timestamps ``Ynew`` (as for ``append_rows``): append them, assimilate the new block, run ``iters``
         ALS iterations if asked for.  ``self.model`` is replaced by a host model of ``rows()`` timestamps (H, lag weights, lag
         set and transform carried over; its arrays are filled by the next ``download()``).  Returns the sums of ``assimilate``;
@@ -709,7 +777,11 @@ class Session(object):
         ``robust_c``, ``scale`` and ``robust_sweeps``.  ``adapt_robust=True`` without both ``robust_c`` and ``adapt`` is refused.  With ``window=N`` the session is a
         sliding window of at most N rows: the append becomes ``slide(Ynew, max(0, rows() + Tn - N), downdate_stats)`` and every later
         step runs on the shifted row numbers; an N smaller than the block + ``smooth_back`` + the largest lag + 1 is refused before the
-        session is touched.  Without ``window`` the session grows as before."""
+        session is touched.  Without ``window`` the session grows as before.  ``revisions=(rows, cols, vals)``: late or corrected
+        cells of the rows already held, applied by ``revise`` BEFORE the block is appended (under ``adapt`` with ``update_stats`` where the
+        statistics are per series, so that they follow); with ``smooth_back`` the smoothed window is widened back to the first revised row (clipped at
+        the largest lag), and a window beyond the smoother's cap raises the smoother's own error.  Its sums are returned as
+        ``sums['revise']``."""
         smooth_back = int(smooth_back)
         if smooth_back < 0:
             raise ValueError('update: smooth_back must not be negative, not {}'.format(smooth_back))
@@ -739,6 +811,11 @@ class Session(object):
                                    'transform since they were built); initialise them again (init_series_stats)')
             if not info['valid']:
                 self.init_series_stats(forget)
+        revised = None
+        if revisions is not None:
+            if len(revisions) != 3:
+                raise ValueError('update: revisions must be (rows, cols, vals)')
+            revised = self.revise(revisions[0], revisions[1], revisions[2], update_stats=bool(adapt) and getattr(self, '_per_series_stats', False))
         if window is not None:
             self.slide(Ynew, retire, downdate_stats)
             before -= retire                                 # the block's first row, counted from the new first row
@@ -750,12 +827,17 @@ class Session(object):
             self.model = type(old).from_arrays(grown, old.H.copy(), old.lag_val.copy(), old.lag_set.copy(), transform=old.transform)
         sums = self.assimilate(before) if robust_c is None else self.assimilate_robust(before, robust_c, robust_sweeps, scale)
         if smooth_back > 0:
-            first = max(before - smooth_back, self._reach())
+            first = before - smooth_back
+            if revised is not None and revised['first_row'] >= 0:
+                first = min(first, revised['first_row'] - retire)     # the window reaches back to the first revised row
+            first = max(first, self._reach())
             sums['smooth'] = self.smooth_robust(first, robust_c, robust_sweeps, scale) if smooth_robust else self.smooth(first)
         if adapt_robust:
             adapted = self.adapt_series_robust(robust_c, robust_sweeps, scale)
         else:
             adapted = self.adapt_series() if adapt else None
+        if revised is not None:
+            sums['revise'] = revised
         if iters:
             self.run(int(iters))
         return (sums, adapted) if adapt else sums

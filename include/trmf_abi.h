@@ -290,6 +290,53 @@ TRMF_API int32_t trmf_session_change_series(TrmfSession *s, const uint8_t *keep 
                                             const void *Hnew /* m x k row-major, or NULL (fit == 0: NULL means zeros) */,
                                             const void *tr_a_new, const void *tr_b_new /* m each: needed iff a series transform is set */,
                                             TrmfChurnSums *out /* or NULL */);
+/* Cell revisions: set or delete cells INSIDE the rows and series a resident session holds -- a reading that arrives after later
+ * rows have been appended, a provisional value that is corrected, a reading that is retracted -- in one new generation of storage;
+ * only the batch crosses PCIe.  rows / cols: the `count` cells, distinct; vals: their values in the library's element type (raw
+ * data under a series transform; ignored where del[i]); del: non-zero flags the cells to delete, NULL: every edit is a set.
+ *
+ * Semantics -- the result depends on the SET of edits, not on their order in the batch.  Sparse storage: every stored copy of an
+ * edited cell is removed from both orientations by a stable compaction (the other entries keep their stored order; the input need
+ * not be a canonical CSR/CSC pair and a cell may be stored twice); each set then places ONE entry at the end of its CSR row and at
+ * the end of its CSC column, the sets of one row in ascending series order, the sets of one column in ascending timestamp order.
+ * A set on a stored cell is a replace, a set on an unstored cell an insert, a delete of an unstored cell a no-op counted in
+ * `missed`.  Dense storage: sets overwrite the cell in both orientations -- under a series transform the RAW copy is edited and the
+ * current coefficients are re-applied, as slide re-applies them -- and deletes are refused.
+ *
+ * Contract: afterwards the session is, bit for bit, the one trmf_session_create would build from the revised entries in that stored
+ * order and the current W, H, lag weights, lambdas, lag penalty and series transform (sum y^2 is recomputed as a fresh session
+ * computes it; split rows, the F-row partition, scratch and the measure-once decisions are re-derived as create derives them), and
+ * every later call returns the bits it returns on that fresh session.  The iteration counter restarts, as after slide.  Blocking;
+ * with a communicator active every rank makes the same call.  Failure-atomic: a refused or failed call leaves the session exactly
+ * as it was.  No floating-point atomics.  count == 0 returns 0 and changes nothing.
+ *
+ * Refused (trmf_last_error(); the session stays usable): a row >= rows() or a series >= n; the same cell twice in one batch; a
+ * delete on dense storage; update_stats not 0 or 1; update_stats == 1 without valid series statistics or on a full-observation
+ * form (dense storage, sparse storage with missing == 0: one shared S); sizes beyond the 32-bit device indices (judged with every
+ * edit counted as an insert).
+ *
+ * Other resident state.  W, H and the lag weights are not touched: re-solving (assimilate*, smooth*, adapt_series*, run) is the
+ * caller's next call.  The mark stays valid.  Noise, forecast and interval tables are per series and stay.  The held-out set is
+ * untouched: a revised cell that is also held out stays held out.  Series statistics: update_stats == 1 with tables that have
+ * absorbed every row (absorbed_rows == rows()) subtracts every removed entry's om_t w_t w_t^T and om_t y w_t from S_j and r_j in
+ * stored order and then adds the sets' terms in ascending timestamp, om_t = forget^(rows() - 1 - t), W as it is now; the per-series
+ * absorbed counts become the new column lengths and stats_carried = 1.  H is not refitted, the next adapt_series does that.  With
+ * update_stats == 0, or with tables that have not absorbed every row, existing tables become stale if a column has changed.
+ *
+ * out: edits = count; inserted / replaced / deleted / missed classify the edits; copies_removed counts stored entries removed (a
+ * cell stored twice counts twice; dense: the cells overwritten); entries_before / entries the stored entries (dense: cells);
+ * first_row / last_row the smallest / largest timestamp named by the batch (-1 for an empty batch). */
+typedef struct {
+    uint64_t edits, inserted, replaced, deleted, missed;   /* missed: a delete of a cell that is not stored (a no-op) */
+    uint64_t copies_removed;                               /* stored entries removed (a cell stored twice counts twice) */
+    uint64_t entries_before, entries;
+    int32_t  first_row, last_row;                          /* smallest / largest timestamp touched, -1 if none */
+    int32_t  stats_carried;
+} TrmfReviseSums;
+TRMF_API int32_t trmf_session_revise(TrmfSession *s, uint64_t count, const uint32_t *rows, const uint32_t *cols,
+                                     const void *vals /* count values of the element type; ignored where del[i] */,
+                                     const uint8_t *del /* count flags or NULL: all are sets */,
+                                     int32_t update_stats, TrmfReviseSums *out /* or NULL */);
 /* Stored entries per timestamp of a sparse session's Y right now (rows() values; what sizes the per-entry weights of the robust
  * calls after series have been retired).  -1 for dense storage. */
 TRMF_API int32_t trmf_session_row_entries(TrmfSession *s, uint64_t *per_row /* rows() */);

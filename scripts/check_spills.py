@@ -15,7 +15,7 @@ HOT = ('fsolve_', 'gram_x_kernel', 'hv_tile_kernel', 'cg_persist_kernel', 'apply
        'theta_', 'dense_tn_mfma_kernel', 'small_gram_mfma_kernel', 'cg_close_kernel',
        'heldout_eval_kernel', 'forecast_rollout_kernel', 'forecast_score_kernel', 'assim_',
        'noise_', 'forecast_psi_kernel', 'forecast_dist_kernel', 'adapt_', 'smooth_', 'csc_slide_', 'series_downdate_kernel',
-       'csr_churn_', 'csc_gather_kernel', 'dense_churn_kernel', 'row_gather_kernel')
+       'csr_churn_', 'csc_gather_kernel', 'dense_churn_kernel', 'row_gather_kernel', 'revise_')
 ALLOW = {}
 
 
